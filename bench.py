@@ -8,6 +8,10 @@ BASELINE.json (configs[2]: n = 50 000, 1000 second-order cones of 1 + 99 rows =>
 
 A "step" is one solver iteration (SolverCore::solve loop body, totsu_core/src/solver/solver.rs:364-457:
 update_vecs + criteria).  Inputs are generated on the device before the timed region.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the line can carry
+(time-to-eps legs and their f64 gate, cpu_baseline, roofline, the row-sharded and two-copy legs, objective_gate).
+--dump-outputs DIR writes the iterate of the last timed step as DIR/*.npy, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -21,6 +25,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+T_START = time.perf_counter()   # --full-budget counts from here
+FULL_RESERVE_S = 30.0           # what a to-eps leg may still spend past its budget: one 5000-iteration chunk, the f64 gate, teardown
 
 HBM_PEAK_GBPS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 
@@ -97,15 +103,77 @@ def parse():
     ap.add_argument("--state", default="compensated", choices=["compensated", "plain"],
                     help="thip_param.state_arith: compensated (Kahan) or plain f32 iterate updates")
     ap.add_argument("--watchdog", type=float, default=1500.0,
-                    help="N > 1: seconds after which rank 0 prints the line as far as it has got and every rank leaves (a leg behind "
-                         "the timed region that hangs in a collective must not cost the line); 0 = off")
+                    help="N > 1: seconds after which rank 0 prints the line as far as it has got and leaves, the other ranks 20 s "
+                         "later (a leg behind the timed region that hangs in a collective must not cost the line); 0 = off")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no HIP library: run the control path only -- rank spawn, process group (gloo), the column-shard "
                          "agreement, the shard plan with its HBM budget, the barrier / max-over-ranks timing bracket, the ONE JSON line")
     ap.add_argument("--cpu-cones", type=int, default=328,
                     help="cones in the CPU sample: the first 328 of the instance by default (A_sub 13 GB of f64), a FIXED "
                          "count so that the baseline reproduces from host to host")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the default time-to-eps legs (f32 and mixed) and the "
+                         "f64 gate of their answer, cpu_baseline, the row-sharded leg of column-sharded runs, the two-copy A/B leg "
+                         "of the sparse workloads, roofline / roofline_eig (HIP events in the timed region, the box's bare read) and "
+                         "objective_gate.  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--full-budget", type=float, default=585.0,
+                    help="--full: seconds from start by which the time-to-eps legs stop (budget_hit in their record; within "
+                         "%d s of it the mixed leg is not started), so that the whole run ends inside 10 minutes" % FULL_RESERVE_S)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (f32 / "
+                         "f64, at most 64 MB in all): the iterate (iterate_x, iterate_y) and the loop's status")
+    a = ap.parse_args()
+    if a.dump_outputs and (a.dry_run or a.path == "trait"):
+        ap.error("--dump-outputs needs the fused path on a GPU (the trait host and --dry-run hand no iterate back)")
+    if not a.full:
+        # a plain run measures the headline and nothing else: every other leg and check is --full's (an explicit --to-eps or
+        # --mixed-leg still runs, without the f64 gate)
+        a.no_cpu = a.no_gate = a.no_row_leg = a.no_two_copy = a.no_mixed_leg = True
+        if a.to_eps is None:
+            a.no_to_eps = True
+    return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def leg_budget(a, budget_s):
+    """seconds a time-to-eps leg may run: budget_s, and under --full no later than --full-budget seconds from start less
+    FULL_RESERVE_S (the cpu_baseline leg runs before the to-eps legs, so this bounds the whole run)"""
+    if a.full:
+        budget_s = min(budget_s, a.full_budget - (time.perf_counter() - T_START) - FULL_RESERVE_S)
+    return budget_s
+
+
+def dump_outputs(d, arrays, rank=0, world=1):
+    """--dump-outputs: each array as d/<name>.npy (float32 / float64).  Beyond DUMP_BYTES in all, every array of more than
+    64 KB keeps a fixed, seeded sample of its entries (<name>.npy) beside their positions (<name>_index.npy, float64), so that
+    two builds of the project write the same entries.  Ranks of a multi-GPU run write <name>_rank<r>.npy, each within its
+    1 / world share of DUMP_BYTES."""
+    cap = DUMP_BYTES // world
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v).reshape(-1) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    big = {k for k, v in arrays.items() if v.nbytes > 64 << 10}
+    room = cap - sum(v.nbytes for k, v in arrays.items() if k not in big)
+    sample = sum(v.nbytes for v in arrays.values()) > cap
+    sfx = "" if world == 1 else "_rank%d" % rank
+    for k, v in arrays.items():
+        if sample and k in big:
+            keep = int(v.size * room / sum(arrays[b].size * (arrays[b].itemsize + 8) for b in big))
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=keep, replace=False))
+            np.save(os.path.join(d, k + "_index" + sfx + ".npy"), idx.astype(np.float64))
+            v = v[idx]
+        np.save(os.path.join(d, k + sfx + ".npy"), v)
+
+
+def loop_outputs(fs, r):
+    """what a caller of the fused loop receives after the last step: the iterate (x: x_x, x_y, x_s, tau; y: u, v, kappa;
+    thip_solver_iterate) and the status of the run (FusedSolver.run)"""
+    x, y = fs.iterate()
+    status = np.array([r.state, r.iters, r.tau, r.kappa, r.cri[0], r.cri[1], r.cri[2]], dtype=np.float64)
+    return {"iterate_x": x, "iterate_y": y, "status": status}
 
 
 class _CAI:
@@ -678,7 +746,7 @@ def run_sparse(a, rank, T, lib, _lib):
     # what THIS box streams: a bare read of as many bytes as one product reads
     box_read = None
     nbytes = min(info["bytes_per_product"], 20_000_000_000) // 16 * 16
-    if nbytes >= 1 << 20:
+    if a.full and nbytes >= 1 << 20:
         scratch = T.DeviceBuffer(nbytes // 4)
         pb, pa = C.c_float(), C.c_float()
         lib.thip_stream_probe(scratch.ptr, nbytes, 5, C.byref(pb), C.byref(pa))
@@ -688,7 +756,7 @@ def run_sparse(a, rank, T, lib, _lib):
     fs.run(a.warmup, poll_every=max(a.warmup, 1))
     torch.cuda.synchronize()
     prof_period = max(1, a.steps // 32)
-    lib.thip_prof_enable(0 if os.environ.get("THIP_BENCH_NO_PROF") else prof_period)
+    lib.thip_prof_enable(prof_period if (a.full and not os.environ.get("THIP_BENCH_NO_PROF")) else 0)
     t0 = time.perf_counter()
     r = fs.run(a.steps, poll_every=a.steps)
     torch.cuda.synchronize()
@@ -703,6 +771,8 @@ def run_sparse(a, rank, T, lib, _lib):
     # alike -- and the convergence criteria are then reported as inf: solver.rs:573-656 evaluates the infeasibility pair instead)
     xi, yi = fs.iterate()
     assert math.isfinite(r.tau) and np.isfinite(xi).all() and np.isfinite(yi).all(), "iterate blew up"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, loop_outputs(fs, r))
     passes, bytes_per_pass = fs.passes()
     # one product = one launch over the stored entries (8 B each; 4 B in a tile held dense, without indices) + its in-vectors
     # (2 per product) and the slices' partial sums
@@ -730,7 +800,7 @@ def run_sparse(a, rank, T, lib, _lib):
         "frac_of_box_read": (achieved / box_read["best_GBps"]) if (box_read and nl.value) else None,
     }
     prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(prof):
+    if a.full and os.path.exists(prof):
         try:
             tr = json.load(open(prof))
             key = "%s_n%d_m%d_%s" % (a.workload, n, m, fs.schedule_in_use())
@@ -741,7 +811,7 @@ def run_sparse(a, rank, T, lib, _lib):
         except Exception:
             pass
     roofline_eig = None
-    if a.workload == "sparse-sdp" and npsd.value:
+    if a.full and a.workload == "sparse-sdp" and npsd.value:
         roofline_eig = eig_record(a.k, psd_ms.value / npsd.value, npsd.value, 1e3 * elapsed / a.steps)
     out = {
         "metric": "solver iterations/sec, %s" % ("sparse LP (l1reg_lp construction)" if a.workload == "sparse-lp"
@@ -754,8 +824,8 @@ def run_sparse(a, rank, T, lib, _lib):
                    "passes_over_A_per_iter": passes, "storage": "one tiled copy (thip_sptile): 4096 x 4096 tiles, 8 B per entry",
                    "sptile": info, "host_gen_seconds": round(t_host, 2), "tile_build_and_upload_seconds": round(t_build, 2),
                    "parallelism": "none: one GPU"},
-        "roofline": roofline, "roofline_eig": roofline_eig,
-        "objective_gate": {"tolerance": 1e-4, "this_run": None,
+        "roofline": roofline if a.full else None, "roofline_eig": roofline_eig,
+        "objective_gate": None if not a.full else {"tolerance": 1e-4, "this_run": None,
                            "asserted_in_tests": "tests/test_gpu_sparse.py::test_sparse_%s_workload_iterates_vs_oracle (iterates 0, 1, 2, 9 "
                                                 "of this construction against the f64 oracle on the dense-ified matrix), "
                                                 "::test_sparse_sweep_converges_to_the_dense_answer_multi_tile"
@@ -768,7 +838,7 @@ def run_sparse(a, rank, T, lib, _lib):
         p2 = T.SolverParam()
         p2.eps_acc = to_eps
         p2.state_arith = a.state
-        budget = a.to_eps_budget if a.to_eps is not None else min(a.to_eps_budget, 240.0)      # (the default leg stays short)
+        budget = leg_budget(a, a.to_eps_budget if a.to_eps is not None else min(a.to_eps_budget, 240.0))   # (the default leg stays short)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         fs3 = T.FusedSolver(n, m, spt, inst["b"], inst["c"], inst["seg_type"], inst["seg_len"], p2, a.schedule)
@@ -788,19 +858,21 @@ def run_sparse(a, rank, T, lib, _lib):
             pobj = float(inst["c"].astype(np.float64) @ xs.astype(np.float64))
             dobj = -float(inst["b"].astype(np.float64) @ ys.astype(np.float64))
             rec["primal_objective"], rec["dual_objective"] = pobj, dobj
-            out["objective_gate"]["this_run"] = {"what": "primal vs dual objective of THIS run's answer (f64 dot products on the host)",
-                                                 "rel_gap": abs(pobj - dobj) / max(1.0, abs(pobj))}
+            this_run = {"what": "primal vs dual objective of THIS run's answer (f64 dot products on the host)",
+                        "rel_gap": abs(pobj - dobj) / max(1.0, abs(pobj))}
             # north_star's gate -- the f64 CPU reference's objective within 1e-4 -- where the oracle's answer for this very
             # instance is on file (tools/sparse_sdp_oracle_objective.py: 10 minutes of 8 CPU threads for k = 500)
             try:
                 ev = json.load(open(os.path.join(ROOT, "profiles", "r06_sparse_sdp_oracle_objective.json")))
                 if a.workload == "sparse-sdp" and ev["workload"] == inst["what"] and ev["eps_acc"] == to_eps:
-                    out["objective_gate"]["this_run"].update({
+                    this_run.update({
                         "oracle_primal_objective": ev["primal_objective"], "oracle_iterations": ev["iterations"],
                         "rel_diff_vs_f64_oracle": abs(pobj - ev["primal_objective"]) / max(1.0, abs(ev["primal_objective"])),
                         "oracle_source": "profiles/r06_sparse_sdp_oracle_objective.json (oracle through its sparse user-operator, same instance, same eps_acc)"})
             except Exception:
                 pass
+            if out["objective_gate"] is not None:
+                out["objective_gate"]["this_run"] = this_run
         out["time_to_eps"] = rec
         fs3.destroy()
     # ---- A/B: the same instance on round 5's two CSR copies (carried schedule: 2 dual gathers per iteration) ----
@@ -1006,12 +1078,14 @@ def spawn_ranks(a):
 
 # the line as far as it has got (rank 0): what the watchdog prints when a later leg of a multi-rank run never comes back
 _PARTIAL = {"out": None, "fd": None, "timer": None}
+WATCHDOG_GRACE_S = 20.0
 
 
 def _watchdog():
     """N > 1 only: the legs behind the timed region (the row-sharded leg, time-to-eps) each hold collectives, and a first run on
     a node nobody has had may hang in one.  After --watchdog seconds rank 0 prints the line with whatever it holds (the timed
-    region's value is complete by then or the line says it is not) and leaves; the launcher then takes the other ranks down.
+    region's value is complete by then or the line says it is not) and leaves with status 0; the other ranks' timers fire
+    WATCHDOG_GRACE_S later and each leaves with status 3 (the launcher waits for every rank).
     A timer THREAD, not SIGALRM: a Python signal handler does not run while the main thread sits inside a collective's C call."""
     out = _PARTIAL["out"]
     rank = int(os.environ.get("RANK", "0"))
@@ -1038,7 +1112,10 @@ def main():
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and a.watchdog > 0:
         import threading
         _PARTIAL["fd"] = saved_stdout
-        _PARTIAL["timer"] = threading.Timer(a.watchdog, _watchdog)
+        # the other ranks' timers are the backstop and fire later: one that left first would make the launcher take rank 0
+        # down before rank 0 had printed its line
+        grace = 0.0 if os.environ.get("RANK", "0") == "0" else WATCHDOG_GRACE_S
+        _PARTIAL["timer"] = threading.Timer(a.watchdog + grace, _watchdog)
         _PARTIAL["timer"].daemon = True
         _PARTIAL["timer"].start()
     try:
@@ -1300,7 +1377,7 @@ def run(a):
     # what THIS box streams: a bare non-temporal read of the solver's own A (the whole of it up to 20 GB), outside every
     # timed region -- the boxes of one pool differ by several percent, so the line carries its own yardstick
     box_read = None
-    if not (a.bf16_direct or a.f16_direct) and inst.m * n_loc > 0:
+    if a.full and not (a.bf16_direct or a.f16_direct) and inst.m * n_loc > 0:
         import ctypes as C
         pb, pa = C.c_float(), C.c_float()
         nbytes = min(4 * inst.m * n_loc, 20_000_000_000) // 16 * 16
@@ -1311,9 +1388,9 @@ def run(a):
     barrier()
     # HIP events around the dominant kernel of the timed region.  An event pair costs the stream 3-5 us -- nothing in a 2.8 ms
     # iteration, 9 % of a 0.14 ms one (measured: LP 6 490 -> 7 085 iter/s without them) -- so a sample is timed: every launch
-    # up to 32 steps (the default line), about 32 launches spread over a longer region
+    # up to 32 steps (the default line), about 32 launches spread over a longer region.  --full only: roofline's figures
     prof_period = max(1, a.steps // 32)
-    lib.thip_prof_enable(0 if os.environ.get("THIP_BENCH_NO_PROF") else prof_period)
+    lib.thip_prof_enable(prof_period if (a.full and not os.environ.get("THIP_BENCH_NO_PROF")) else 0)
     t0 = time.perf_counter()
     r = fs.run(a.steps, poll_every=a.steps)
     barrier()
@@ -1330,6 +1407,8 @@ def run(a):
         elapsed = float(tt.item())
     assert r.state == _lib.ST_RUNNING and r.iters == a.warmup + a.steps + getattr(a, "warmup_extra", 0), (r.state, r.iters)
     assert math.isfinite(r.tau) and math.isfinite(r.cri[0]), "iterate blew up"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, loop_outputs(fs, r), rank, world)
 
     rccl_ranks = None
     if hook == "rccl":
@@ -1373,7 +1452,7 @@ def run(a):
         "frac_of_box_read": (achieved / box_read["best_GBps"]) if (box_read and nl.value) else None,
     }
     prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(prof) and a.a_storage in ("f32", "bf16", "f16"):
+    if a.full and os.path.exists(prof) and a.a_storage in ("f32", "bf16", "f16"):
         try:
             tr = json.load(open(prof))
             key = "%s_n%d_m%d_%s%s" % (a.workload, n, inst.m, fs.schedule_in_use(), "" if a.a_storage == "f32" else "_" + a.a_storage)
@@ -1389,7 +1468,7 @@ def run(a):
             pass
 
     roofline_eig = None
-    if a.workload == "sdp" and npsd.value:
+    if a.full and a.workload == "sdp" and npsd.value:
         roofline_eig = eig_record(a.k, psd_ms.value / npsd.value, npsd.value, 1e3 * elapsed / a.steps)
 
     out = {
@@ -1426,17 +1505,17 @@ def run(a):
                                      "2-pass schedule, all-reduce of A^T y per transposed product)")),
         "value_column_sharded": iters_per_s if cols else None,
         "value_row_sharded": iters_per_s if (hook is not None and not cols) else None,
-        "roofline": roofline,
+        "roofline": roofline if a.full else None,
         "roofline_eig": roofline_eig,
         # north_star: "same primal/dual objective as the f64 CPU reference within 1e-4 relative".  The f64 oracle runs the
         # full-size instance at ~0.24 iter/s (1e5 iterations = 5 days), so at this size the gate is (a) THIS run's answer
-        # re-evaluated in f64 (`this_run`, filled after the time_to_eps leg) and (b) stored evidence, by reference
+        # re-evaluated in f64 (`this_run`, filled after the time_to_eps leg) and (b) stored evidence, by reference (--full)
         "objective_gate": {"tolerance": 1e-4, "this_run": None, "stored_evidence": stored_objective_evidence(fs.schedule_in_use()),
                            "asserted_in_tests": "tests/test_gpu_solver.py::test_synth_socp_converges_to_oracle_objective[%s] (n = 500, "
                                                 "this schedule vs the f64 oracle's objective); at the full size: "
                                                 "tests/test_gpu_configs.py::test_c3_full_size_sweep_vs_oracle (iterates 0-2 of the "
                                                 "1000-cone instance, 0-99 of the 328-cone sub-instance vs the oracle)"
-                                                % fs.schedule_in_use()},
+                                                % fs.schedule_in_use()} if a.full else None,
         "sweep_faults": fs.sweep_faults(),
     }
     _PARTIAL["out"] = out          # (the legs below add to it in place)
@@ -1512,7 +1591,7 @@ def run(a):
         p2 = T.SolverParam()
         p2.eps_acc = a.to_eps
         p2.state_arith = a.state
-        budget = {"hit": False}
+        budget = {"hit": False, "s": leg_budget(a, a.to_eps_budget)}
 
         def run_to_end(fs):
             # in chunks, with a progress line on stderr: a run that hits an outer time limit still leaves its trail
@@ -1525,7 +1604,7 @@ def run(a):
                 if r.state != _lib.ST_RUNNING:
                     return r
                 # every rank sees the same elapsed-time decision (rank 0's clock)
-                over = time.perf_counter() - t0 > a.to_eps_budget
+                over = time.perf_counter() - t0 > budget["s"]
                 if use_dist:
                     tt = torch.tensor([1 if over else 0], dtype=torch.int32, device=dev_pg)
                     dist.broadcast(tt, src=0)
@@ -1559,7 +1638,7 @@ def run(a):
             barrier()
         rec = {"eps_acc": a.to_eps, "seconds": time.perf_counter() - t0, "iterations": r2.iters + 1,
                "state": r2.state, "cri": list(r2.cri), "a_storage": storage, "state_arith": a.state,
-               "budget_s": a.to_eps_budget, "budget_hit": budget["hit"],
+               "budget_s": budget["s"], "budget_hit": budget["hit"],
                "schedule": fs2.schedule_in_use(), "sweep_plan": fs2.sweep_plan(), "sweep_faults": fs2.sweep_faults(),
                "what": "wall time of the solve from the initial iterate (x = 0, tau = 1) to the reference's "
                        "stopping test at eps_acc (solver.rs:381-400), A resident in HBM, init (norms, "
@@ -1595,22 +1674,7 @@ def run(a):
         fs2.destroy()
         return rec, gate
 
-    if a.to_eps is not None:
-        out["time_to_eps"], out["objective_gate"]["this_run"] = to_eps_leg(a.a_storage)
-        if mixed_leg and out["time_to_eps"]["state"] == _lib.ST_OK:
-            # BASELINE's metric has two halves; the second one has a lever the f32 headline does not use: the same solve with
-            # the first phase streamed from an f16-stored copy of A (half the bytes per iteration), finished on the exact f32
-            # matrix to the SAME stopping test.  Reported beside the f32 leg, never instead of it.
-            try:
-                rec, gate = to_eps_leg("mixed")
-                rec["objective_gate_this_run"] = gate
-                rec["vs_f32_leg"] = {"seconds_ratio": rec["seconds"] / out["time_to_eps"]["seconds"],
-                                     "primal_obj_rel_diff": abs(rec["primal_obj"] - out["time_to_eps"]["primal_obj"])
-                                     / (1.0 + abs(out["time_to_eps"]["primal_obj"]))}
-                out["time_to_eps_mixed"] = rec
-            except Exception as e:          # the extra leg must never cost the line (single GPU: no peer is left waiting)
-                out["time_to_eps_mixed"] = {"error": repr(e)}
-
+    # (before the to-eps legs: their budget under --full then bounds the whole run)
     if rank == 0 and world == 1 and not a.no_cpu and a.workload == "socp":
         import oracle as O
         # a fixed sample (default: the first 328 cones, A_sub 13 GB of f64) so that the figure reproduces; shrunk only
@@ -1624,6 +1688,26 @@ def run(a):
         out["cpu_baseline"] = cpu_baseline(n, a.cones, 99, 0, min(cc, a.cones))
     elif rank == 0:
         out["cpu_baseline"] = None
+
+    if a.to_eps is not None:
+        out["time_to_eps"], gate = to_eps_leg(a.a_storage)
+        if out["objective_gate"] is not None:
+            out["objective_gate"]["this_run"] = gate
+        if mixed_leg and out["time_to_eps"]["state"] == _lib.ST_OK and leg_budget(a, a.to_eps_budget) <= 0:
+            out["time_to_eps_mixed"] = {"skipped": "--full-budget: no time left for this leg", "full_budget_s": a.full_budget}
+        elif mixed_leg and out["time_to_eps"]["state"] == _lib.ST_OK:
+            # BASELINE's metric has two halves; the second one has a lever the f32 headline does not use: the same solve with
+            # the first phase streamed from an f16-stored copy of A (half the bytes per iteration), finished on the exact f32
+            # matrix to the SAME stopping test.  Reported beside the f32 leg, never instead of it.
+            try:
+                rec, gate = to_eps_leg("mixed")
+                rec["objective_gate_this_run"] = gate
+                rec["vs_f32_leg"] = {"seconds_ratio": rec["seconds"] / out["time_to_eps"]["seconds"],
+                                     "primal_obj_rel_diff": abs(rec["primal_obj"] - out["time_to_eps"]["primal_obj"])
+                                     / (1.0 + abs(out["time_to_eps"]["primal_obj"]))}
+                out["time_to_eps_mixed"] = rec
+            except Exception as e:          # the extra leg must never cost the line (single GPU: no peer is left waiting)
+                out["time_to_eps_mixed"] = {"error": repr(e)}
 
     fs.destroy()
     inst.free()

@@ -176,7 +176,7 @@ def test_bench_gpus_8_control_path_at_the_real_shapes_without_a_gpu():
     at the REAL configs[2] shape (100 000 x 50 000 over 8 column blocks + the row-sharded extra leg), assert the plan against
     288 GB, bracket a timed region with barriers and a max over ranks, and rank 0 prints ONE line carrying the keys of a real
     one.  --dry-run replaces the HIP library (no GPU here), nothing else."""
-    r, lines = _bench_dry(["--gpus", "8", "--steps", "3", "--warmup", "1"])
+    r, lines = _bench_dry(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -201,14 +201,14 @@ def test_bench_gpus_8_control_path_at_the_real_shapes_without_a_gpu():
 def test_bench_gpus_8_configs4_budget_and_a_rank_that_cannot_sweep():
     """configs[4] (LP n = 200 000, m = 400 000) over 8 ranks: a 40 GB column shard + the row leg's 40 GB shard per rank, inside
     288 GB; and when ONE rank's probe says no (rank 5), every rank plans row shards and the carried schedule"""
-    r, lines = _bench_dry(["--gpus", "8", "--workload", "lp", "--size", "200000", "--steps", "2", "--warmup", "1"])
+    r, lines = _bench_dry(["--gpus", "8", "--workload", "lp", "--size", "200000", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(lines[0])
     plans = d["config"]["hbm_plan"]
     assert all(p["partition"] == "columns" and p["rows"] == 400_000 and p["cols"] == 25_000 for p in plans)
     assert all(p["A_bytes"] == 40_000_000_000 and p["row_leg_bytes"] == 40_000_000_000 for p in plans)      # 50 000 rows: no padded copy
     assert all(p["fits"] and 80e9 < p["total_bytes"] < 0.94 * 288e9 for p in plans)
-    r, lines = _bench_dry(["--gpus", "8", "--workload", "lp", "--size", "200000", "--steps", "2", "--warmup", "1"],
+    r, lines = _bench_dry(["--gpus", "8", "--workload", "lp", "--size", "200000", "--steps", "2", "--warmup", "1", "--full"],
                           env_extra={"THIP_DRY_PROBE_NO": "5"})
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(lines[0])
@@ -230,12 +230,51 @@ def test_bench_plan_that_does_not_fit_stops_every_rank_before_allocating():
 def test_bench_watchdog_prints_the_partial_line_when_a_rank_never_comes_back():
     """N > 1: a leg that hangs in a collective must not cost the line.  Rank 1 never reaches the barrier (test hook); after
     --watchdog seconds rank 0's timer thread -- the main thread sits inside the barrier's C call -- prints the line as far as it
-    got, marked partial, and the launcher takes every rank down: the run ends instead of waiting for the driver's kill"""
+    got, marked partial, and leaves; rank 1's own timer fires 20 s later and the launcher ends: the run ends instead of waiting
+    for the driver's kill.  --watchdog 15, not less: rank 0 must have reached the barrier (torch import, gloo setup, the plan)
+    before its timer fires, and on a loaded host that start-up alone has taken several seconds"""
     import time
     t0 = time.time()
-    r, lines = _bench_dry(["--gpus", "2", "--steps", "2", "--watchdog", "6"], env_extra={"THIP_DRY_HANG_RANK": "1"}, timeout=240)
+    r, lines = _bench_dry(["--gpus", "2", "--steps", "2", "--watchdog", "15"], env_extra={"THIP_DRY_HANG_RANK": "1"}, timeout=240)
     assert time.time() - t0 < 200
     assert len(lines) == 1, (lines, r.stderr[-2000:])
     d = json.loads(lines[0])
     assert d["dry_run"] is True and "watchdog" in d and d["n_gpus"] == 2
     assert "watchdog on rank 0" in r.stderr
+
+
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """a plain `bench.py --gpus N` times the headline alone: the row-sharded leg (its shard, its place in the HBM plan) comes
+    with --full only"""
+    r, lines = _bench_dry(["--gpus", "2", "--steps", "2", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["row_sharded"] is None and all(p["row_leg_bytes"] == 0 for p in d["config"]["hbm_plan"])
+    r, lines = _bench_dry(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["row_sharded"]["rows_per_gpu"] == 50_000 and all(p["row_leg_bytes"] > 0 for p in d["config"]["hbm_plan"])
+
+
+def test_bench_dump_outputs_float_arrays_and_a_fixed_sample_beyond_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in f32 / f64; past the byte cap each large one keeps the same seeded sample
+    of its entries, with their positions beside them, small ones stay whole, and the whole stays under the cap"""
+    import bench
+    x = np.arange(100_000, dtype=np.float32)
+    st = np.array([0.0, 5.0, 1.0], dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"iterate_x": x, "status": st})
+    assert np.array_equal(np.load(tmp_path / "a" / "iterate_x.npy"), x)
+    assert np.load(tmp_path / "a" / "status.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100_000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"iterate_x": x, "status": st})
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["iterate_x.npy", "iterate_x_index.npy", "status.npy"]
+    assert np.array_equal(np.load(tmp_path / "b" / "status.npy"), st)
+    assert 90_000 < sum(np.load(tmp_path / "b" / f).nbytes for f in files) <= 100_000
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    idx = np.load(tmp_path / "b" / "iterate_x_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(np.load(tmp_path / "b" / "iterate_x.npy"), x[idx.astype(np.int64)])
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "d"), {"bad": np.arange(3)})

@@ -116,7 +116,7 @@ def test_c5_column_shard_through_the_full_loop(T):
     lines = []
     for rep in range(2):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "lp", "--size", str(N5), "--emulate-world",
-                            str(WORLD5), "--emulate-latency", "30", "--steps", "50", "--warmup", "5"], capture_output=True, text=True,
+                            str(WORLD5), "--emulate-latency", "30", "--steps", "50", "--warmup", "5", "--full"], capture_output=True, text=True,
                            timeout=1200, cwd=root)
         assert r.returncode == 0, r.stderr[-3000:]
         out = [l for l in r.stdout.splitlines() if l.strip()]
@@ -454,7 +454,7 @@ def test_bench_lines_of_the_lp_and_sdp_workloads_carry_their_gates_and_the_eig_r
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
     def line(args):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu", "--steps", "20", "--warmup", "5"] + args,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu", "--steps", "20", "--warmup", "5", "--full"] + args,
                            capture_output=True, text=True, timeout=900, cwd=root)
         assert r.returncode == 0, r.stderr[-3000:]
         out = [l for l in r.stdout.splitlines() if l.strip()]

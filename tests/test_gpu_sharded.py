@@ -241,7 +241,7 @@ def test_bench_gpus_flag_spawns_the_ranks_itself():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--size", "2000", "--cones", "40", "--steps", "5", "--warmup", "1", "--no-cpu", "--to-eps", "1e-3"]
+    common = ["--size", "2000", "--cones", "40", "--steps", "5", "--warmup", "1", "--no-cpu", "--to-eps", "1e-3", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True,
                         text=True, timeout=900, env=env, cwd=root)

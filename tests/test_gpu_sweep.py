@@ -423,7 +423,7 @@ def test_bench_column_shard_path_at_world_1():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29583")
     base = [sys.executable, os.path.join(root, "bench.py"), "--size", "3000", "--cones", "60", "--steps", "5", "--warmup", "1",
-            "--no-cpu", "--to-eps", "1e-3"]
+            "--no-cpu", "--to-eps", "1e-3", "--full"]
     outs = []
     for extra in ([], ["--force-collective", "--shard", "cols"]):
         r = subprocess.run(base + extra, capture_output=True, text=True, timeout=900, env=env, cwd=root)
@@ -523,6 +523,39 @@ def test_bench_emulated_rank_of_a_column_sharded_run():
     assert d["n_gpus"] == 1 and c["emulated_world"] == 4 and c["schedule"] == "sweep" and c["passes_over_A_per_iter"] == 1
     assert c["cols_per_gpu"] == 750 and c["rows_per_gpu"] == 6000 and "column-sharded" in c["parallelism"]
     assert "time_to_eps" not in d or d["time_to_eps"] is None or True
+
+
+def test_bench_dump_outputs_writes_the_iterate_of_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR, dense and sparse, at sizes that take seconds: iterate_x (n + 2m + 1), iterate_y (n + m + 1)
+    and status (state, iterations, tau, kappa, criteria) of the run that was timed; the same arguments write the same values"""
+    import json
+    import os
+    import subprocess
+    import sys
+    from totsu_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cases = {"socp": ["--size", "1500", "--cones", "30"], "sparse-lp": ["--workload", "sparse-lp", "--n", "64"]}
+    for name, args in cases.items():
+        dumps = []
+        for rep in range(2):
+            d = str(tmp_path / ("%s%d" % (name, rep)))
+            r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "2", "--dump-outputs", d]
+                               + args, capture_output=True, text=True, timeout=900, cwd=root)
+            assert r.returncode == 0, r.stderr[-2000:]
+            lines = [l for l in r.stdout.splitlines() if l.strip()]
+            assert len(lines) == 1 and json.loads(lines[0])["steps"] == 7, lines
+            assert sorted(os.listdir(d)) == ["iterate_x.npy", "iterate_y.npy", "status.npy"], os.listdir(d)
+            dumps.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+        x, y, st = dumps[0]["iterate_x.npy"], dumps[0]["iterate_y.npy"], dumps[0]["status.npy"]
+        assert x.dtype == y.dtype == np.float32 and st.dtype == np.float64
+        n, m = (1500, 3000) if name == "socp" else (3 * 64 + 1, 4 * 64)
+        assert x.shape == (n + 2 * m + 1,) and y.shape == (n + m + 1,), (name, x.shape, y.shape)
+        assert st[0] == _lib.ST_RUNNING and st[1] == 9, st
+        assert np.isclose(st[2], x[-1], rtol=1e-6) and np.isclose(st[3], y[-1], rtol=1e-6), (st, x[-1], y[-1])
+        assert np.isfinite(x).all() and np.isfinite(y).all()
+        for f in ("iterate_x.npy", "iterate_y.npy"):
+            a_, b_ = dumps[0][f], dumps[1][f]
+            np.testing.assert_allclose(a_, b_, rtol=1e-4, atol=1e-6 * (1 + np.abs(a_).max()), err_msg=name + " " + f)
 
 
 def test_sweep_lp_with_equality_rows_and_qp_rotated_cone(T):

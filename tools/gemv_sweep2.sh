@@ -2,7 +2,7 @@
 # finer sweep: bash tools/gemv_sweep2.sh "<bench extra args>" "<nj list>" "<blocks list>" [steps]
 EXTRA=$1; NJS=$2; BLS=$3; STEPS=${4:-30}
 for nj in $NJS; do for blocks in $BLS; do
-  out=$(THIP_GEMV_NT=1 THIP_GEMV_NJ=$nj THIP_GEMV_BLOCKS=$blocks python bench.py --steps $STEPS --warmup 3 --no-cpu $EXTRA 2>/dev/null)
+  out=$(THIP_GEMV_NT=1 THIP_GEMV_NJ=$nj THIP_GEMV_BLOCKS=$blocks python bench.py --steps $STEPS --warmup 3 --full --no-cpu $EXTRA 2>/dev/null)
   python - "$nj" "$blocks" "$out" <<'PY'
 import json, sys
 nj, blocks, out = sys.argv[1:4]
