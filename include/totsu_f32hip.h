@@ -160,7 +160,9 @@ int thip_spmv_csr(size_t n_row, size_t n_col, size_t nnz, const int64_t *dev_row
  * a tile of full height whose every column holds all 4096 rows (a dense block of the matrix) is stored WITHOUT its index words -- 4 bytes
  * per entry on the device and per product (thip_sptile_layout reports how many).
  * thip_sptile_mv is `Operator::op / trans_op` (operator.rs:40-75) for such an operator: y = alpha A x + beta y,
- * transpose != 0: A^T; abs_mode != 0: |A| and x = 1 (absadd_rows / absadd_cols, operator.rs:82-154).  x, y on the device. */
+ * transpose != 0: A^T; abs_mode != 0: |A| and x = 1 (absadd_rows / absadd_cols, operator.rs:82-154).  x, y on the device.
+ * thip_sptile_mv on one handle must not run from two host threads at once (it uses a workspace the handle owns), while any
+ * number of solvers may share one handle (thip_solver_set_sptile: each brings its own workspace). */
 typedef struct thip_sptile thip_sptile;
 int thip_sptile_create(size_t n_row, size_t n_col, size_t nnz, const int64_t *host_colptr, const int32_t *host_rowidx,
                        const float *host_vals, thip_sptile **out);

@@ -180,12 +180,23 @@ static inline unsigned grid_for(size_t n, unsigned block, unsigned max_blocks)
 //   outN[r] = alphaN * (A xn)[r] + betaN * outN[r]      (betaN == 0: outN not read)
 //   outT[c] = alphaT * (A^T xt)[c] + betaT * outT[c]
 // abs_mode: use |A| (for absadd_*), x vectors ignored (taken as all-ones).
-// a_kind: THIP_A_F32 (mat = const float *), THIP_A_BF16 or THIP_A_F16 (mat = const uint16_t *, lda in elements;
-// F16 also needs inv_s, the per-column 1 / scale)
-int dual_gemv(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
+// The stored dense matrix as one value: column-major, `lda` in elements of `kind` -- THIP_A_F32 (mat = const float *), THIP_A_BF16 or
+// THIP_A_F16 (mat = const uint16_t *; F16 also needs inv_s, the per-column 1 / scale).  pad_zero: rows n_row .. lda - 1 are zeros
+// written by this library (its own padded / 16-bit copy), so a partial last row tile may be loaded whole.
+struct DenseA {
+    const void *mat = nullptr; size_t lda = 0; int kind = THIP_A_F32; const float *inv_s = nullptr; bool pad_zero = false;
+    bool is16() const { return kind != THIP_A_F32; }
+    size_t elem_bytes() const { return is16() ? 2 : 4; }
+    int vec_elems() const { return is16() ? 8 : 4; }                  // elements of a 16-byte load
+    // may the kernels read this matrix with 16-byte loads?  (THE definition: aligned base, every column starts aligned)
+    bool vec_ok() const { return ((uintptr_t)mat & 15u) == 0 && lda % vec_elems() == 0; }
+    int vec_width() const { return vec_ok() ? vec_elems() : 1; }      // elements per load the GEMV plans are made for
+};
+inline DenseA dense_f32(const float *mat, size_t lda) { return DenseA{ mat, lda, THIP_A_F32, nullptr, false }; }
+int dual_gemv(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
               const float *xn, float alphaN, float betaN, float *outN,
               const float *xt, float alphaT, float betaT, float *outT,
-              bool abs_mode, const int *stop_flag, int a_kind = 0, const float *inv_s = nullptr);
+              bool abs_mode, const int *stop_flag);
 int to_bf16(hipStream_t st, size_t n_row, size_t n_col, const float *src, uint16_t *dst, size_t ld16);
 // f16 with one power-of-two scale per column: inv_s[c] = 1 / s_c is written (n_col floats)
 int to_f16(hipStream_t st, size_t n_row, size_t n_col, const float *src, uint16_t *dst, size_t ld16, float *inv_s);
@@ -202,22 +213,19 @@ struct GroupDesc { const float *A; const float *xn; const float *xt; float *part
 int grouped_gemv(hipStream_t st, const GroupDesc *dev_tab, int n_desc, int max_tiles, int max_chunks, int mode);
 struct GemvHint { int nj; int target_blocks; };        // tiling override: row groups per lane, grid size
 const GemvHint *gemv_candidates(int *count);           // plans worth timing on a given matrix
-int dual_gemv_partials(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
+int dual_gemv_partials(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
                        const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
                        float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
-                       const GemvHint *hint = nullptr, int a_kind = 0, const float *inv_s = nullptr,
-                       bool pad_zero = false);     // pad_zero: rows n_row .. lda - 1 of mat are zeros (the library's own copy)
+                       const GemvHint *hint = nullptr);
 // the product over columns [col0, col1) as a launch of its own, partial sums left where a consumer of the whole product
-// expects them (thip_gemv.hip)
-int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
-                            const float *xn, const float *xt, bool do_n, bool do_t,
+// expects them (thip_gemv.hip; dual_gemv_partials is the range [0, n_col) with its own chunk rows: max_chunk_rows < 0)
+int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
+                            const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
                             float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
-                            const GemvHint *hint, int a_kind, const float *inv_s, bool pad_zero,
-                            size_t col0, size_t col1, int chunk_row0, int max_chunk_rows, int *chunks_used);
-int dual_gemv_chunk_rows(size_t n_row, size_t cols, bool vec_ok, int a_kind, const GemvHint *hint, int *tiles);
-int dual_gemv_cols_per_chunk(size_t n_row, size_t n_col, const void *mat, size_t lda, const GemvHint *hint, int a_kind,
-                             int *chunks);
-int dual_gemv_partials_geometry(size_t n_row, size_t n_col, const void *mat, size_t lda, bool do_n, bool do_t,
+                            const GemvHint *hint, size_t col0, size_t col1, int chunk_row0, int max_chunk_rows,
+                            int *chunks_used);
+int dual_gemv_chunk_rows(size_t n_row, size_t cols, const DenseA &A, const GemvHint *hint, int *tiles);
+int dual_gemv_partials_geometry(size_t n_row, size_t n_col, const DenseA &A, bool do_n, bool do_t,
                                 float *scratch_base, GemvPartials *out);
 size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col);
 // y[i] = alpha * sum_k part[k*stride + i] + beta * y[i]
@@ -262,8 +270,8 @@ struct SweepArgs {
 // how the groups' partial dots are published by default in this process: 0 plain stores (the publish-scope self-test of
 // thip_sweep.hip passed), 1 agent scope.  Runs the self-test on first use (allocates and synchronises: plan time only)
 int sweep_publish_default();
-int sweep_plan(size_t m, size_t n, size_t lda, const void *mat, SweepGeom *g, int elem = 0);
-int sweep_candidates(size_t m, size_t n, size_t lda, const void *mat, SweepGeom *out, int max_out, int elem = 0);
+int sweep_plan(size_t m, size_t n, const DenseA &A, SweepGeom *g);
+int sweep_candidates(size_t m, size_t n, const DenseA &A, SweepGeom *out, int max_out);
 int sweep_launch16(hipStream_t st, const SweepGeom &g, const SweepArgs &a);       // thip_sweep16.hip
 size_t sweep_gran_words(const SweepGeom &g);
 int sweep_census_dry_run(hipStream_t st, unsigned *census, unsigned seq);
@@ -276,9 +284,11 @@ int sptile_slices(const thip_sptile *M, bool tphase);
 size_t sptile_pad(const thip_sptile *M, bool tphase);
 size_t sptile_bytes_per_pass(const thip_sptile *M);
 void sptile_dims(const thip_sptile *M, size_t *m, size_t *n, size_t *nnz);
+// xmax: 2 x SPT_NMAX floats of the LAUNCHER's (zeroed once): the block maxima of the in-vectors of the product in flight
+constexpr int SPT_NMAX = 256;
 int sptile_product(hipStream_t st, const thip_sptile *M, bool tphase, const float *in0, const float *in1, float *part,
-                   int abs_mode, const int *stop, bool xmax_ready = false);
-int sptile_colupdate(hipStream_t st, const thip_sptile *M, const SweepArgs &a, const float *partT);
+                   float *xmax, int abs_mode, const int *stop, bool xmax_ready = false);
+int sptile_colupdate(hipStream_t st, const thip_sptile *M, const SweepArgs &a, const float *partT, float *xmax);
 
 // thip_oneshot.hip: the hook thip_solver_use_oneshot installs and the device address of its error word (NULL: not set up)
 thip_allreduce_fn oneshot_hook();

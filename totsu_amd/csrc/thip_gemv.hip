@@ -636,6 +636,15 @@ const GemvHint *gemv_candidates(int *count)
     return c;
 }
 
+// the partial last row tile runs unguarded when every vector it needs exists: m a multiple of the vector width, or the rows
+// m .. lda - 1 are the library's own zeros.  THIP_GEMV_CLAMP=0: the guarded form
+static void clamp_rows(Plan &p, size_t n_row, const DenseA &A)
+{
+    static const int clamp_on = getenv("THIP_GEMV_CLAMP") ? atoi(getenv("THIP_GEMV_CLAMP")) : 1;
+    const size_t m_up = round_up(n_row, (size_t)p.vw);
+    if (clamp_on && p.vw > 1 && (n_row % p.vw == 0 || (A.pad_zero && A.lda >= m_up))) p.m_load = (int)m_up;
+}
+
 size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col)
 {
     size_t best = 0;
@@ -651,74 +660,35 @@ size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col)
     return best + 64;
 }
 
-int dual_gemv_partials(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
-                       const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
-                       float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
-                       const GemvHint *hint, int a_kind, const float *inv_s, bool pad_zero)
-{
-    if (n_row == 0 || n_col == 0 || (!do_n && !do_t)) {
-        out->partN = out->partT = nullptr; out->nN = out->nT = 0; out->strideN = out->strideT = 0;
-        return 0;
-    }
-    if (n_row > 0x7fffffffull || n_col > 0x7fffffffull) return fail(THIP_E_INVALID, "matrix dimension > 2^31", __FILE__, __LINE__);
-    const bool bf16 = a_kind == THIP_A_BF16, f16 = a_kind == THIP_A_F16;
-    if (f16 && inv_s == nullptr) return fail(THIP_E_INVALID, "f16 storage needs the per-column scales", __FILE__, __LINE__);
-    const bool vec_ok = (((uintptr_t)mat & 15u) == 0) && (lda % ((bf16 || f16) ? 8 : 4) == 0);
-    Plan p = make_plan(n_row, n_col, vec_ok ? ((bf16 || f16) ? 8 : 4) : 1, hint);
-    {
-        // the partial last row tile runs unguarded when every vector it needs exists: m a multiple of the vector width,
-        // or the rows m .. lda - 1 are the library's own zeros.  THIP_GEMV_CLAMP=0: the guarded form
-        static const int clamp_on = getenv("THIP_GEMV_CLAMP") ? atoi(getenv("THIP_GEMV_CLAMP")) : 1;
-        const size_t m_up = round_up(n_row, (size_t)p.vw);
-        if (clamp_on && p.vw > 1 && (n_row % p.vw == 0 || (pad_zero && lda >= m_up))) p.m_load = (int)m_up;
-    }
-    const size_t needN = do_n ? (size_t)p.chunks * p.strideN : 0;
-    const size_t needT = do_t ? (size_t)p.tiles * p.strideT : 0;
-    if (needN + needT > scratch_floats) return fail(THIP_E_WORK, "gemv scratch too small", __FILE__, __LINE__);
-    float *partN = scratch_base;
-    float *partT = scratch_base + needN;
-    const int m = (int)n_row, n = (int)n_col;
-    if (bf16) launch_any(p, st, (const bf16raw *)mat, lda, m, n, xn, xt, do_n, do_t, abs_mode, partN, partT, stop_flag);
-    else if (f16) launch_any(p, st, (const f16elt *)mat, lda, m, n, xn, xt, do_n, do_t, abs_mode, partN, partT, stop_flag, inv_s);
-    else      launch_any(p, st, (const float *)mat, lda, m, n, xn, xt, do_n, do_t, abs_mode, partN, partT, stop_flag);
-    THIP_LAUNCH_CHECK();
-    out->partN = do_n ? partN : nullptr; out->nN = do_n ? p.chunks : 0; out->strideN = p.strideN;
-    out->partT = do_t ? partT : nullptr; out->nT = do_t ? p.tiles : 0;  out->strideT = p.strideT;
-    return 0;
-}
-
-// The product over columns [col0, col1) only, as one launch of its own: the tile height of the plan for (n_row x n_col)
-// under `hint`, its own column chunks starting at col0.  Partial sums go where a consumer of the WHOLE product expects
-// them: N partials into chunk rows chunk_row0 .. of partN (so that the launches over [0, c) and [c, n_col) fill
-// consecutive chunk rows and the consumer sums them all), T partials into columns col0 .. col1 of every tile row.
-// *chunks_used = chunk rows this launch filled.  `out` describes the layout (nN = chunk_row0 + *chunks_used).
-// col0 only needs the alignment of the vector loads (a multiple of 4 floats; 8 for 16-bit storage).
-int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
-                            const float *xn, const float *xt, bool do_n, bool do_t,
+// The product over columns [col0, col1) as one launch: the tile height of the plan for (n_row x n_col) under `hint`, its own
+// column chunks starting at col0.  Partial sums go where a consumer of the WHOLE product expects them: N partials into chunk
+// rows chunk_row0 .. of partN (so that the launches over [0, c) and [c, n_col) fill consecutive chunk rows and the consumer sums
+// them all), T partials into columns col0 .. col1 of every tile row.  max_chunk_rows = the chunk rows partN has room for (< 0:
+// this launch's own: the whole matrix in one launch); *chunks_used = chunk rows this launch filled.  `out` describes the layout
+// (nN = chunk_row0 + *chunks_used).  col0 only needs the alignment of the vector loads (a multiple of 4 floats; 8 for 16-bit storage).
+int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
+                            const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
                             float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
-                            const GemvHint *hint, int a_kind, const float *inv_s, bool pad_zero,
-                            size_t col0, size_t col1, int chunk_row0, int max_chunk_rows, int *chunks_used)
+                            const GemvHint *hint, size_t col0, size_t col1, int chunk_row0, int max_chunk_rows,
+                            int *chunks_used)
 {
     if (chunks_used) *chunks_used = 0;
-    if (n_row == 0 || n_col == 0 || (!do_n && !do_t) || col1 <= col0) {
-        out->partN = out->partT = nullptr; out->nN = out->nT = 0; out->strideN = out->strideT = 0;
-        return 0;
-    }
-    if (n_row > 0x7fffffffull || n_col > 0x7fffffffull || col1 > n_col) return fail(THIP_E_INVALID, "bad column range", __FILE__, __LINE__);
-    const bool bf16 = a_kind == THIP_A_BF16, f16 = a_kind == THIP_A_F16;
+    *out = GemvPartials{};
+    if (n_row == 0 || n_col == 0 || (!do_n && !do_t) || col1 <= col0) return 0;
+    if (n_row > 0x7fffffffull || n_col > 0x7fffffffull || col1 > n_col)
+        return fail(THIP_E_INVALID, "matrix dimension > 2^31, or bad column range", __FILE__, __LINE__);
+    const size_t lda = A.lda; const float *inv_s = A.inv_s;
+    const bool bf16 = A.kind == THIP_A_BF16, f16 = A.kind == THIP_A_F16;
     if (f16 && inv_s == nullptr) return fail(THIP_E_INVALID, "f16 storage needs the per-column scales", __FILE__, __LINE__);
-    const size_t esz = (bf16 || f16) ? 2 : 4;
-    const char *base = (const char *)mat + col0 * lda * esz;
-    const bool vec_ok = (((uintptr_t)mat & 15u) == 0) && (((uintptr_t)base & 15u) == 0) && (lda % ((bf16 || f16) ? 8 : 4) == 0);
+    DenseA R = A;                // the column range as a matrix of its own: its first column must be aligned too
+    R.mat = (const char *)A.mat + col0 * lda * A.elem_bytes();
+    const char *base = (const char *)R.mat;
     // tiling of the range's own shape (its columns decide the chunking); strides are those of the whole matrix
-    Plan p = make_plan(n_row, col1 - col0, vec_ok ? ((bf16 || f16) ? 8 : 4) : 1, hint);
+    Plan p = make_plan(n_row, col1 - col0, A.vec_ok() ? R.vec_width() : 1, hint);
     p.strideN = round_up(n_row, 4);
     p.strideT = round_up(n_col, 4);
-    {
-        static const int clamp_on = getenv("THIP_GEMV_CLAMP") ? atoi(getenv("THIP_GEMV_CLAMP")) : 1;
-        const size_t m_up = round_up(n_row, (size_t)p.vw);
-        if (clamp_on && p.vw > 1 && (n_row % p.vw == 0 || (pad_zero && lda >= m_up))) p.m_load = (int)m_up;
-    }
+    clamp_rows(p, n_row, A);
+    if (max_chunk_rows < 0) max_chunk_rows = chunk_row0 + p.chunks;
     if (chunk_row0 + p.chunks > max_chunk_rows) return fail(THIP_E_WORK, "gemv scratch: too many chunk rows", __FILE__, __LINE__);
     const size_t needN = do_n ? (size_t)max_chunk_rows * p.strideN : 0;
     const size_t needT = do_t ? (size_t)p.tiles * p.strideT : 0;
@@ -732,43 +702,40 @@ int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const vo
     float *pn = partN + (size_t)chunk_row0 * p.strideN;
     float *pt = partT + col0;
     const float *xnr = xn ? xn + col0 : nullptr;
-    if (bf16) launch_any(p, st, (const bf16raw *)base, lda, m, n, xnr, xt, do_n, do_t, false, pn, pt, stop_flag);
-    else if (f16) launch_any(p, st, (const f16elt *)base, lda, m, n, xnr, xt, do_n, do_t, false, pn, pt, stop_flag, inv_s + col0);
-    else      launch_any(p, st, (const float *)base, lda, m, n, xnr, xt, do_n, do_t, false, pn, pt, stop_flag);
+    if (bf16) launch_any(p, st, (const bf16raw *)base, lda, m, n, xnr, xt, do_n, do_t, abs_mode, pn, pt, stop_flag);
+    else if (f16) launch_any(p, st, (const f16elt *)base, lda, m, n, xnr, xt, do_n, do_t, abs_mode, pn, pt, stop_flag, inv_s + col0);
+    else      launch_any(p, st, (const float *)base, lda, m, n, xnr, xt, do_n, do_t, abs_mode, pn, pt, stop_flag);
     THIP_LAUNCH_CHECK();
     return 0;
 }
 
-// chunk rows a launch over `cols` columns of an n_row-row matrix will fill under `hint` (and its tile count)
-int dual_gemv_chunk_rows(size_t n_row, size_t cols, bool vec_ok, int a_kind, const GemvHint *hint, int *tiles)
+int dual_gemv_partials(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
+                       const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
+                       float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
+                       const GemvHint *hint)
 {
-    const bool h16 = a_kind == THIP_A_BF16 || a_kind == THIP_A_F16;
-    const Plan p = make_plan(n_row, cols, vec_ok ? (h16 ? 8 : 4) : 1, hint);
+    return dual_gemv_partials_cols(st, n_row, n_col, A, xn, xt, do_n, do_t, abs_mode, scratch_base, scratch_floats, out, stop_flag,
+                                   hint, 0, n_col, 0, -1, nullptr);
+}
+
+// chunk rows a launch over `cols` columns of an n_row-row matrix will fill under `hint` (and its tile count)
+int dual_gemv_chunk_rows(size_t n_row, size_t cols, const DenseA &A, const GemvHint *hint, int *tiles)
+{
+    const Plan p = make_plan(n_row, cols, A.vec_width(), hint);
     if (tiles) *tiles = p.tiles;
     return p.chunks;
 }
 
-// where dual_gemv_partials (f32, default plan) will leave its partial sums for this shape, without launching anything
-int dual_gemv_partials_geometry(size_t n_row, size_t n_col, const void *mat, size_t lda, bool do_n, bool do_t,
+// where dual_gemv_partials (default plan) will leave its partial sums for this shape, without launching anything
+int dual_gemv_partials_geometry(size_t n_row, size_t n_col, const DenseA &A, bool do_n, bool do_t,
                                 float *scratch_base, GemvPartials *out)
 {
-    const bool vec_ok = (((uintptr_t)mat & 15u) == 0) && (lda % 4 == 0);
-    const Plan p = make_plan(n_row, n_col, vec_ok ? 4 : 1, nullptr);
+    const Plan p = make_plan(n_row, n_col, A.vec_width(), nullptr);
     const size_t needN = do_n ? (size_t)p.chunks * p.strideN : 0;
     float *partN = scratch_base, *partT = scratch_base + needN;
     out->partN = do_n ? partN : nullptr; out->nN = do_n ? p.chunks : 0; out->strideN = p.strideN;
     out->partT = do_t ? partT : nullptr; out->nT = do_t ? p.tiles : 0;  out->strideT = p.strideT;
     return 0;
-}
-
-int dual_gemv_cols_per_chunk(size_t n_row, size_t n_col, const void *mat, size_t lda, const GemvHint *hint, int a_kind,
-                             int *chunks)
-{
-    const bool h16 = a_kind == THIP_A_BF16 || a_kind == THIP_A_F16;
-    const bool vec_ok = (((uintptr_t)mat & 15u) == 0) && (lda % (h16 ? 8 : 4) == 0);
-    const Plan p = make_plan(n_row, n_col, vec_ok ? (h16 ? 8 : 4) : 1, hint);
-    if (chunks) *chunks = p.chunks;
-    return p.cols_per_chunk;
 }
 
 int grouped_gemv(hipStream_t st, const GroupDesc *dev_tab, int n_desc, int max_tiles, int max_chunks, int mode)
@@ -811,24 +778,19 @@ int to_f16(hipStream_t st, size_t n_row, size_t n_col, const float *src, uint16_
     return 0;
 }
 
-int dual_gemv(hipStream_t st, size_t n_row, size_t n_col, const void *mat, size_t lda,
+int dual_gemv(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
               const float *xn, float alphaN, float betaN, float *outN,
               const float *xt, float alphaT, float betaT, float *outT,
-              bool abs_mode, const int *stop_flag, int a_kind, const float *inv_s)
+              bool abs_mode, const int *stop_flag)
 {
     const bool do_n = outN != nullptr, do_t = outT != nullptr;
     float *scr = nullptr;
     const size_t need = dual_gemv_scratch_floats(n_row, n_col);
     THIP_RC(scratch(need, &scr));
     GemvPartials gp;
-    THIP_RC(dual_gemv_partials(st, n_row, n_col, mat, lda, xn, xt, do_n, do_t, abs_mode, scr, need, &gp, stop_flag, nullptr, a_kind, inv_s));
-    if (do_n && n_row)
-        hipLaunchKernelGGL(finalize_k, dim3(grid_for(n_row, BLK, 2048)), dim3(BLK), 0, st, n_row, gp.partN, gp.nN,
-                           gp.strideN, alphaN, betaN, outN, stop_flag);
-    if (do_t && n_col)
-        hipLaunchKernelGGL(finalize_k, dim3(grid_for(n_col, BLK, 2048)), dim3(BLK), 0, st, n_col, gp.partT, gp.nT,
-                           gp.strideT, alphaT, betaT, outT, stop_flag);
-    THIP_LAUNCH_CHECK();
+    THIP_RC(dual_gemv_partials(st, n_row, n_col, A, xn, xt, do_n, do_t, abs_mode, scr, need, &gp, stop_flag));
+    if (do_n) THIP_RC(finalize_partials(st, n_row, gp.partN, gp.nN, gp.strideN, alphaN, betaN, outN, stop_flag));
+    if (do_t) THIP_RC(finalize_partials(st, n_col, gp.partT, gp.nT, gp.strideT, alphaT, betaT, outT, stop_flag));
     return 0;
 }
 
@@ -849,8 +811,8 @@ int thip_transform_ge(int transpose, size_t n_row, size_t n_col, float alpha, co
     THIP_RC(lazy_push(transpose, n_row, n_col, alpha, mat, x, beta, y, &deferred));
     if (deferred) return 0;
     if (transpose)
-        return dual_gemv(ctx().stream, n_row, n_col, mat, n_row, nullptr, 0.f, 0.f, nullptr, x, alpha, beta, y, false, nullptr);
-    return dual_gemv(ctx().stream, n_row, n_col, mat, n_row, x, alpha, beta, y, nullptr, 0.f, 0.f, nullptr, false, nullptr);
+        return dual_gemv(ctx().stream, n_row, n_col, dense_f32(mat, n_row), nullptr, 0.f, 0.f, nullptr, x, alpha, beta, y, false, nullptr);
+    return dual_gemv(ctx().stream, n_row, n_col, dense_f32(mat, n_row), x, alpha, beta, y, nullptr, 0.f, 0.f, nullptr, false, nullptr);
 }
 
 int thip_to_bf16(size_t n_row, size_t n_col, const float *mat, uint16_t *mat16, size_t ld16)
@@ -859,17 +821,22 @@ int thip_to_bf16(size_t n_row, size_t n_col, const float *mat, uint16_t *mat16, 
     return to_bf16(ctx().stream, n_row, n_col, mat, mat16, ld16);
 }
 
-int thip_transform_ge_bf16(int transpose, size_t n_row, size_t n_col, float alpha, const uint16_t *mat16, size_t ld16,
-                           const float *x, float beta, float *y)
+static int transform_ge16(int transpose, size_t n_row, size_t n_col, float alpha, const DenseA &A, const float *x, float beta, float *y)
 {
     THIP_NEED_INIT();
     const size_t ylen = transpose ? n_col : n_row;
     if (ylen == 0) return 0;
     if (n_row == 0 || n_col == 0) return thip_scale(ylen, beta, y);
-    if (ld16 < n_row) return fail(THIP_E_INVALID, "ld16 < n_row", __FILE__, __LINE__);
+    if (A.lda < n_row) return fail(THIP_E_INVALID, "ld16 < n_row", __FILE__, __LINE__);
     if (transpose)
-        return dual_gemv(ctx().stream, n_row, n_col, mat16, ld16, nullptr, 0.f, 0.f, nullptr, x, alpha, beta, y, false, nullptr, THIP_A_BF16);
-    return dual_gemv(ctx().stream, n_row, n_col, mat16, ld16, x, alpha, beta, y, nullptr, 0.f, 0.f, nullptr, false, nullptr, THIP_A_BF16);
+        return dual_gemv(ctx().stream, n_row, n_col, A, nullptr, 0.f, 0.f, nullptr, x, alpha, beta, y, false, nullptr);
+    return dual_gemv(ctx().stream, n_row, n_col, A, x, alpha, beta, y, nullptr, 0.f, 0.f, nullptr, false, nullptr);
+}
+
+int thip_transform_ge_bf16(int transpose, size_t n_row, size_t n_col, float alpha, const uint16_t *mat16, size_t ld16,
+                           const float *x, float beta, float *y)
+{
+    return transform_ge16(transpose, n_row, n_col, alpha, DenseA{ mat16, ld16, THIP_A_BF16, nullptr, false }, x, beta, y);
 }
 
 int thip_to_f16(size_t n_row, size_t n_col, const float *mat, uint16_t *mat16, size_t ld16, float *inv_scale)
@@ -882,28 +849,21 @@ int thip_to_f16(size_t n_row, size_t n_col, const float *mat, uint16_t *mat16, s
 int thip_transform_ge_f16(int transpose, size_t n_row, size_t n_col, float alpha, const uint16_t *mat16, size_t ld16,
                           const float *inv_scale, const float *x, float beta, float *y)
 {
-    THIP_NEED_INIT();
-    const size_t ylen = transpose ? n_col : n_row;
-    if (ylen == 0) return 0;
-    if (n_row == 0 || n_col == 0) return thip_scale(ylen, beta, y);
-    if (ld16 < n_row) return fail(THIP_E_INVALID, "ld16 < n_row", __FILE__, __LINE__);
-    if (transpose)
-        return dual_gemv(ctx().stream, n_row, n_col, mat16, ld16, nullptr, 0.f, 0.f, nullptr, x, alpha, beta, y, false, nullptr, THIP_A_F16, inv_scale);
-    return dual_gemv(ctx().stream, n_row, n_col, mat16, ld16, x, alpha, beta, y, nullptr, 0.f, 0.f, nullptr, false, nullptr, THIP_A_F16, inv_scale);
+    return transform_ge16(transpose, n_row, n_col, alpha, DenseA{ mat16, ld16, THIP_A_F16, inv_scale, false }, x, beta, y);
 }
 
 int thip_absadd_cols(size_t n_row, size_t n_col, const float *mat, float *tau)
 {
     THIP_NEED_INIT();
     if (n_row == 0 || n_col == 0) return 0;
-    return dual_gemv(ctx().stream, n_row, n_col, mat, n_row, nullptr, 0.f, 0.f, nullptr, nullptr, 1.0f, 1.0f, tau, true, nullptr);
+    return dual_gemv(ctx().stream, n_row, n_col, dense_f32(mat, n_row), nullptr, 0.f, 0.f, nullptr, nullptr, 1.0f, 1.0f, tau, true, nullptr);
 }
 
 int thip_absadd_rows(size_t n_row, size_t n_col, const float *mat, float *sigma)
 {
     THIP_NEED_INIT();
     if (n_row == 0 || n_col == 0) return 0;
-    return dual_gemv(ctx().stream, n_row, n_col, mat, n_row, nullptr, 1.0f, 1.0f, sigma, nullptr, 0.f, 0.f, nullptr, true, nullptr);
+    return dual_gemv(ctx().stream, n_row, n_col, dense_f32(mat, n_row), nullptr, 1.0f, 1.0f, sigma, nullptr, 0.f, 0.f, nullptr, true, nullptr);
 }
 
 int thip_transform_sp(size_t n, float alpha, const float *mat, const float *x, float beta, float *y)

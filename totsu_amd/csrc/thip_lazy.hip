@@ -522,7 +522,7 @@ int launch_plan(Plan *p)
     THIP_RC(grouped_gemv(st, dgd + p->nD + p->nN, p->nT, p->maxt[1], (p->maxc[1] + 3) / 4, 1));
     for (const BigMat &b : p->big) {
         GemvPartials gp;
-        THIP_RC(dual_gemv_partials(st, b.nr, b.nc, b.A, b.nr, b.xn, b.xt, b.xn != nullptr, b.xt != nullptr, false,
+        THIP_RC(dual_gemv_partials(st, b.nr, b.nc, dense_f32(b.A, b.nr), b.xn, b.xt, b.xn != nullptr, b.xt != nullptr, false,
                                    Q.part + b.scr_off, b.scr_floats, &gp, nullptr));
     }
     if (p->nDot) hipLaunchKernelGGL(dot_k, dim3(p->nDot), dim3(DBLK), 0, st, reinterpret_cast<const DotD *>(p->dev + p->off_dot));
@@ -747,7 +747,7 @@ int flush_products()
     std::vector<GemvPartials> biggp(p->big.size());
     for (size_t k = 0; k < p->big.size(); ++k) {
         const BigMat &b = p->big[k];
-        dual_gemv_partials_geometry(b.nr, b.nc, b.A, b.nr, b.xn != nullptr, b.xt != nullptr, dpart + b.scr_off, &biggp[k]);
+        dual_gemv_partials_geometry(b.nr, b.nc, dense_f32(b.A, b.nr), b.xn != nullptr, b.xt != nullptr, dpart + b.scr_off, &biggp[k]);
     }
 
     // ---- tables ----

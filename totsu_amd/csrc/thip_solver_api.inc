@@ -18,7 +18,7 @@ static int solver_create_impl(const thip_problem *prob, const thip_param *par, i
     thip_solver *s = new thip_solver();
     *out = s;                      // the caller releases it if anything below fails
     s->n = prob->n; s->m = prob->m;
-    s->A = prob->mat_a; s->b = prob->vec_b; s->c = prob->vec_c; s->b_rowabs = prob->vec_b_rowabs;
+    s->sa.f32 = prob->mat_a; s->sa.m = prob->m; s->b = prob->vec_b; s->c = prob->vec_c; s->b_rowabs = prob->vec_b_rowabs;
     s->par = *par; s->schedule = schedule;
     s->seg_type.assign(prob->host_seg_type, prob->host_seg_type + prob->n_seg);
     s->seg_len.assign(prob->host_seg_len, prob->host_seg_len + prob->n_seg);
@@ -141,9 +141,8 @@ int thip_solver_set_csr(thip_solver *s, size_t nnz, const int64_t *dev_rowptr, c
 {
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
     if (!dev_rowptr || !dev_t_rowptr) return fail(THIP_E_INVALID, "null CSR arrays", __FILE__, __LINE__);
-    s->sparse = true; s->nnz = nnz;
-    s->rp = dev_rowptr; s->ci = dev_colidx; s->sv = dev_vals;
-    s->trp = dev_t_rowptr; s->tci = dev_t_colidx; s->tsv = dev_t_vals;
+    if (s->op != A_TILED) s->op = A_CSR2;      // (a tiled copy, once given, is the operator)
+    s->csr = Csr2{ nnz, dev_rowptr, dev_t_rowptr, dev_colidx, dev_t_colidx, dev_vals, dev_t_vals };
     return 0;
 }
 
@@ -154,7 +153,7 @@ int thip_solver_set_sptile(thip_solver *s, thip_sptile *mat)
     size_t m = 0, n = 0, nnz = 0;
     sptile_dims(mat, &m, &n, &nnz);
     if (m != s->m || n != s->n) return fail(THIP_E_INVALID, "the sparse operator's shape is not the problem's m x n", __FILE__, __LINE__);
-    s->sparse = true; s->nnz = nnz; s->spt = mat;
+    s->op = A_TILED; s->spt = mat;
     return 0;
 }
 
@@ -207,7 +206,7 @@ int thip_solver_init(thip_solver *s)
     s->carried_stale = false;
     s->hst->state = THIP_ST_RUNNING;
     THIP_RC(ensure_gemv_scratch(s));
-    if (!s->is16()) THIP_RC(ensure_apad(s, true));      // a fresh solve re-reads the caller's A (it may have changed in place)
+    if (!s->sa.is16()) THIP_RC(ensure_apad(s, true));      // a fresh solve re-reads the caller's A (it may have changed in place)
     s->xx = s->xx_home; s->kx = s->kx_home; s->xbuf = 0;
     s->sw_first = true; s->sweep_state = 0; s->pn_par = 0; s->status_pending = false; s->step_par = 0; s->pm_par = 0;
     s->sweep_faults = 0; s->sweep_fault_word = 0; s->sweep_fault_iter = -1; s->snap_iter = -1;
@@ -227,22 +226,7 @@ int thip_solver_init(thip_solver *s)
 
     // |A| column sums (sharded partial -> all-reduce with the two scalars in the tail) and row sums
     float *colabs = s->g1, *rowabs = s->h1;
-    if (n && m && s->spt) {
-        THIP_RC(sptile_product(st, s->spt, false, s->c, nullptr, s->sw_partH, 1, nullptr));
-        THIP_RC(finalize_partials(st, m, s->sw_partH, sptile_slices(s->spt, false), 2 * sptile_pad(s->spt, false), 1.0f, 0.0f, rowabs, nullptr));
-        THIP_RC(sptile_product(st, s->spt, true, s->c, nullptr, s->sw_partT, 1, nullptr));
-        THIP_RC(finalize_partials(st, n, s->sw_partT, sptile_slices(s->spt, true), 2 * sptile_pad(s->spt, true), 1.0f, 0.0f, colabs, nullptr));
-    } else if (n && m && s->sparse) {
-        THIP_RC(thip_spmv_csr(m, n, s->nnz, s->rp, s->ci, s->sv, 1.0f, s->sv, 0.0f, rowabs, 1));
-        THIP_RC(thip_spmv_csr(n, m, s->nnz, s->trp, s->tci, s->tsv, 1.0f, s->tsv, 0.0f, colabs, 1));
-    } else if (n && m) {
-        // solver-owned scratch (several solvers may share the context, e.g. one per thread)
-        GemvPartials gp;
-        THIP_RC(dual_gemv_partials(st, m, n, s->amat(), s->alda(), nullptr, nullptr, true, true, true, s->gemv_scr,
-                                   s->gemv_scr_n, &gp, nullptr, nullptr, s->a_kind, s->ainv(), s->apadz()));
-        THIP_RC(finalize_partials(st, m, gp.partN, gp.nN, gp.strideN, 1.0f, 0.0f, rowabs, nullptr));
-        THIP_RC(finalize_partials(st, n, gp.partT, gp.nT, gp.strideT, 1.0f, 0.0f, colabs, nullptr));
-    }
+    THIP_RC(abs_sums(s, rowabs, colabs));
     if (s->col_shard) {
         // this rank holds a block of columns: b and the m-vectors are replicated, c is its block.  What the ranks have to
         // add up is the |A| row sums and sum c^2, sum |c| (the b sums and the column sums are complete as they are)
@@ -325,7 +309,7 @@ int thip_solver_run(thip_solver *s, int64_t max_steps, int64_t poll_every, thip_
         // (without a hook do_allreduce is a no-op: the "abort" would spin through dummy calls and report a time-out)
         if (s->allreduce == nullptr) return fail(THIP_E_INVALID, "a column-sharded solver needs an all-reduce (thip_solver_set_allreduce / _use_rccl / _use_oneshot)", __FILE__, __LINE__);
         if (s->schedule != THIP_SCHED_SWEEP) return fail(THIP_E_INVALID, "a column-sharded solver runs THIP_SCHED_SWEEP only", __FILE__, __LINE__);
-        if (s->sparse) return fail(THIP_E_INVALID, "column shards are for a dense A", __FILE__, __LINE__);
+        if (s->op != A_DENSE) return fail(THIP_E_INVALID, "column shards are for a dense A", __FILE__, __LINE__);
         if (s->hst->state != THIP_ST_RUNNING || max_steps == 0) return 0;      // nothing would run on any rank
         return col_shard_abort(s, max_steps, poll_every);
     }
@@ -443,15 +427,15 @@ static int set_a16_external(thip_solver *s, const uint16_t *mat16, size_t ld16, 
     THIP_NEED_INIT();
     if (!s || !mat16) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
     if (s->inited) return fail(THIP_E_INVALID, "a caller-built 16-bit matrix must precede thip_solver_init", __FILE__, __LINE__);
-    if (s->sparse) return fail(THIP_E_INVALID, "storage kinds apply to a dense A", __FILE__, __LINE__);
+    if (s->op != A_DENSE) return fail(THIP_E_INVALID, "storage kinds apply to a dense A", __FILE__, __LINE__);
     if (ld16 < s->m) return fail(THIP_E_INVALID, "ld16 < m", __FILE__, __LINE__);
     if (kind == THIP_A_F16 && !inv_scale) return fail(THIP_E_INVALID, "f16 storage needs the per-column scales", __FILE__, __LINE__);
-    if (s->A16_owned) { THIP_TRY(hipFree(s->A16)); s->A16_owned = false; }
-    if (s->inv_s_owned) { THIP_TRY(hipFree(s->inv_s)); s->inv_s_owned = false; }
-    s->A16 = const_cast<uint16_t *>(mat16);      // caller-owned, only ever read
-    s->inv_s = const_cast<float *>(inv_scale);
-    s->ld16 = ld16;
-    s->a_kind = s->a16_kind = kind;
+    StoredA &sa = s->sa;
+    THIP_TRY(sa.free16());
+    sa.a16 = const_cast<uint16_t *>(mat16);      // caller-owned, only ever read
+    sa.inv_s = const_cast<float *>(inv_scale);
+    sa.ld16 = ld16;
+    sa.kind = sa.kind16 = kind;
     return 0;
 }
 
@@ -471,35 +455,34 @@ int thip_solver_set_a_storage(thip_solver *s, int a_kind)
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
     if (a_kind != THIP_A_F32 && a_kind != THIP_A_BF16 && a_kind != THIP_A_F16)
         return fail(THIP_E_INVALID, "bad storage kind", __FILE__, __LINE__);
-    if (s->sparse) return fail(THIP_E_INVALID, "storage kinds apply to a dense A", __FILE__, __LINE__);
-    if (a_kind == THIP_A_F32 && !s->A && s->m && s->n) return fail(THIP_E_INVALID, "no f32 matrix was given", __FILE__, __LINE__);
-    if (a_kind != THIP_A_F32 && s->a16_kind != a_kind && s->m && s->n) {
+    if (s->op != A_DENSE) return fail(THIP_E_INVALID, "storage kinds apply to a dense A", __FILE__, __LINE__);
+    StoredA &sa = s->sa;
+    if (a_kind == THIP_A_F32 && !sa.f32 && s->m && s->n) return fail(THIP_E_INVALID, "no f32 matrix was given", __FILE__, __LINE__);
+    if (a_kind != THIP_A_F32 && sa.kind16 != a_kind && s->m && s->n) {
         // (re)build the library-owned 16-bit copy in the requested format
-        if (!s->A) return fail(THIP_E_INVALID, "no f32 matrix to convert", __FILE__, __LINE__);
-        if (s->A16 && !s->A16_owned) return fail(THIP_E_INVALID, "the 16-bit matrix is caller-built", __FILE__, __LINE__);
+        if (!sa.f32) return fail(THIP_E_INVALID, "no f32 matrix to convert", __FILE__, __LINE__);
+        if (sa.a16 && !sa.a16_owned) return fail(THIP_E_INVALID, "the 16-bit matrix is caller-built", __FILE__, __LINE__);
         hipStream_t st = ctx().stream;
-        if (!s->A16) {
-            s->ld16 = (s->m + 7) / 8 * 8;
-            THIP_TRY(hipMalloc((void **)&s->A16, s->ld16 * s->n * sizeof(uint16_t)));
-            s->A16_owned = true;
+        if (!sa.a16) {
+            sa.ld16 = (s->m + 7) / 8 * 8;
+            THIP_TRY(hipMalloc((void **)&sa.a16, sa.ld16 * s->n * sizeof(uint16_t)));
+            sa.a16_owned = true;
         }
         if (a_kind == THIP_A_F16) {
-            if (!s->inv_s) { THIP_TRY(hipMalloc((void **)&s->inv_s, s->n * sizeof(float))); s->inv_s_owned = true; }
-            THIP_RC(to_f16(st, s->m, s->n, s->A, s->A16, s->ld16, s->inv_s));
+            if (!sa.inv_s) { THIP_TRY(hipMalloc((void **)&sa.inv_s, s->n * sizeof(float))); sa.inv_s_owned = true; }
+            THIP_RC(to_f16(st, s->m, s->n, sa.f32, sa.a16, sa.ld16, sa.inv_s));
         } else {
-            THIP_RC(to_bf16(st, s->m, s->n, s->A, s->A16, s->ld16));
+            THIP_RC(to_bf16(st, s->m, s->n, sa.f32, sa.a16, sa.ld16));
         }
-        s->a16_kind = a_kind;
-        s->tuned16 = s->tuned16_sp = false;
+        sa.kind16 = a_kind;
+        stored_form_changed(s, PLANS_16);
     }
-    const bool changed = s->a_kind != a_kind;
-    s->a_kind = a_kind;
-    if (changed) s->sweep_state = 0;           // the one-pass schedule is planned per stored form (another kernel instance)
+    if (sa.kind != a_kind) {
+        sa.kind = a_kind;
+        stored_form_changed(s, KIND);      // (inside a solve: gP / hP rebuilt by the next thip_solver_run, after thip_solver_resume)
+    }
     if (s->inited && a_kind == THIP_A_F32) THIP_RC(ensure_apad(s, false));      // first f32 pass of this solve
-    if (s->inited) {
-        THIP_RC(autotune_gemv(s));      // a switch inside a running solve: tune the other kernel once
-        if (changed) s->carried_stale = true;      // rebuilt by the next thip_solver_run (after thip_solver_resume)
-    }
+    if (s->inited) THIP_RC(autotune_gemv(s));      // a switch inside a running solve: tune the other kernel once
     return 0;
 }
 
@@ -537,17 +520,8 @@ int thip_solver_resume(thip_solver *s)
 int thip_solver_passes(const thip_solver *s, int *host_passes, size_t *host_bytes_per_pass)
 {
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
-    if (s->spt) {
-        // every product is one pass over the stored entries (8 bytes each): two per stage
-        if (host_passes) *host_passes = (s->schedule == THIP_SCHED_REFERENCE || s->schedule == THIP_SCHED_FUSED) ? 6 : (sweep_active(s) ? 2 : 4);
-        if (host_bytes_per_pass) *host_bytes_per_pass = sptile_bytes_per_pass(s->spt);
-        return 0;
-    }
-    if (host_passes) *host_passes = s->schedule == THIP_SCHED_REFERENCE ? 6 : (s->schedule == THIP_SCHED_FUSED ? 3 : (sweep_active(s) ? 1 : 2));
-    // the algorithmic bytes of a pass (SURVEY.md 8d: 4 m n, or 2 m n for a 16-bit A); the padding rows of a library-owned
-    // copy (at most 15 per column) are zeros that the kernel never loads
-    if (host_bytes_per_pass) *host_bytes_per_pass = s->sparse ? 2 * s->nnz * (sizeof(float) + sizeof(int32_t))
-                                                              : s->m * s->n * (s->is16() ? 2 : sizeof(float));
+    int passes = 0; size_t bytes = 0;
+    traffic(s, host_passes ? host_passes : &passes, host_bytes_per_pass ? host_bytes_per_pass : &bytes);
     return 0;
 }
 
@@ -608,7 +582,7 @@ int thip_solver_set_gemv_autotune(thip_solver *s, int on)
 {
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
     s->autotune = on != 0;
-    if (!on) { s->tuned = s->tuned16 = s->tuned_sp = s->tuned16_sp = false; }        // back to the shape heuristic: the plan no longer depends on timings
+    if (!on) stored_form_changed(s, PLANS_F32 | PLANS_16);        // back to the shape heuristic: the plan no longer depends on timings
     return 0;
 }
 
@@ -654,10 +628,10 @@ int thip_test_spin_allreduce(thip_solver *s, int latency_us)
 int thip_solver_gemv_plan(const thip_solver *s, int *host_nj, int *host_blocks, float *host_ms)
 {
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
-    const GemvHint *h = s->ahint();
+    const GemvHint *h = s->hint_in_use();
     if (host_nj) *host_nj = h ? h->nj : 0;
     if (host_blocks) *host_blocks = h ? h->target_blocks : 0;
-    if (host_ms) *host_ms = s->split_plan ? (s->is16() ? s->tuned16_sp_ms : s->tuned_sp_ms) : (s->is16() ? s->tuned16_ms : s->tuned_ms);
+    if (host_ms) *host_ms = s->plan_in_use().ms;
     return 0;
 }
 
@@ -726,8 +700,8 @@ int thip_solver_destroy(thip_solver *s)
     hipFree(s->cls); hipFree(s->soc_beg); hipFree(s->soc_end); hipFree(s->rot_beg); hipFree(s->rot_end);
     for (auto &g : s->psd_groups) hipFree(g.dev_offs);
     hipFree(s->grp_beg); hipFree(s->grp_end); hipFree(s->psd_work); hipFree(s->arena); hipFree(s->part);
-    hipFree(s->gemv_scr); hipFree(s->dst); hipFree(s->Apad); if (s->A16_owned) hipFree(s->A16); if (s->inv_s_owned) hipFree(s->inv_s);
-    hipFree(s->sw_partT);
+    hipFree(s->gemv_scr); hipFree(s->dst); (void)s->sa.free_pad(); (void)s->sa.free16();
+    hipFree(s->sw_partT); hipFree(s->spt_xmax);
     hipFree(s->sw_partH); hipFree(s->sw_gran); hipFree(s->sw_census); hipFree(s->sw_part); hipFree(s->cs_buf);
     if (s->hst) hipHostFree(s->hst);
     if (s->hflags) hipHostFree(s->hflags);

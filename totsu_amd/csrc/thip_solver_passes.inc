@@ -2,56 +2,112 @@
 // the column-split pipeline of row-sharded runs, the GEMV plan autotune.
 namespace {
 
-// one stage's products as partial sums: N partials of A xn (m), T partials of A^T xt (n).  The fused and carried
-// schedules read A once (dual launch); the reference schedule issues the reference's two single GEMVs.
+bool sweep_active(const thip_solver *s);
+
+// ---- what depends on the operator kind, side by side: a stage's products, the preconditioner's abs sums, the traffic ----------
+// one product of a sparse operator as a finished vector (t: with A^T; abs_mode: |A| times ones).  Tiled copy: a pass over the
+// stored entries, then its slices added up; two-CSR form: a gather over the CSR of A or of A^T
+int spt_product(thip_solver *s, bool t, const float *in, int abs_mode, const int *stop, float *out)
+{
+    hipStream_t st = ctx().stream;
+    float *part = t ? s->sw_partT : s->sw_partH;
+    if (!abs_mode) prof_begin(st);
+    THIP_RC(sptile_product(st, s->spt, t, in, nullptr, part, s->spt_xmax, abs_mode, stop));
+    if (!abs_mode) prof_end(st);
+    return finalize_partials(st, t ? s->n : s->m, part, sptile_slices(s->spt, t), 2 * sptile_pad(s->spt, t), 1.0f, 0.0f, out, nullptr);
+}
+int csr_product(const thip_solver *s, bool t, const float *in, int abs_mode, float *out)
+{
+    const Csr2 &a = s->csr;
+    return t ? thip_spmv_csr(s->n, s->m, a.nnz, a.trp, a.tci, a.tsv, 1.0f, abs_mode ? a.tsv : in, 0.0f, out, abs_mode)
+             : thip_spmv_csr(s->m, s->n, a.nnz, a.rp, a.ci, a.sv, 1.0f, abs_mode ? a.sv : in, 0.0f, out, abs_mode);
+}
+
+// one stage's products: A xn (m) and A^T xt (n).  Dense: as partial sums -- the fused and carried schedules read A once (dual
+// launch), the reference schedule issues the reference's two single GEMVs.  Sparse: hN and gT as finished vectors; nN = nT = -1
+// tells post_k to take them as they are (the stop flag is honoured by the consumers: a stray product is harmless).
 int products(thip_solver *s, const float *xn, const float *xt, GemvPartials *gp, float *hN, float *gT)
 {
     hipStream_t st = ctx().stream;
     const int *stop = &s->dst->stop;
     gp->partN = gp->partT = nullptr; gp->nN = gp->nT = 0; gp->strideN = gp->strideT = 0;
     if (s->m == 0 || s->n == 0) return 0;     // zero-sized operator: products are 0 (matop.rs:83-85)
-    if (s->spt) {
-        // the tiled copy: each product is one pass over the stored entries, its slices added up into a finished vector
-        const size_t mp = sptile_pad(s->spt, false), np_ = sptile_pad(s->spt, true);
+    const DenseA A = s->sa.in_use();
+    const GemvHint *hint = s->hint_in_use();
+    switch (s->op) {
+    case A_TILED:
+        THIP_RC(spt_product(s, false, xn, 0, stop, hN));
+        THIP_RC(spt_product(s, true, xt, 0, stop, gT));
+        break;
+    case A_CSR2:
         prof_begin(st);
-        THIP_RC(sptile_product(st, s->spt, false, xn, nullptr, s->sw_partH, 0, stop));
+        THIP_RC(csr_product(s, false, xn, 0, hN));
+        THIP_RC(csr_product(s, true, xt, 0, gT));
         prof_end(st);
-        THIP_RC(finalize_partials(st, s->m, s->sw_partH, sptile_slices(s->spt, false), 2 * mp, 1.0f, 0.0f, hN, nullptr));
-        prof_begin(st);
-        THIP_RC(sptile_product(st, s->spt, true, xt, nullptr, s->sw_partT, 0, stop));
-        prof_end(st);
-        THIP_RC(finalize_partials(st, s->n, s->sw_partT, sptile_slices(s->spt, true), 2 * np_, 1.0f, 0.0f, gT, nullptr));
-        gp->nN = gp->nT = -1;
-        return 0;
+        break;
+    case A_DENSE:
+        if (s->schedule == THIP_SCHED_REFERENCE) {
+            GemvPartials a, b;
+            const size_t half = s->gemv_scr_n / 2;
+            prof_begin(st);
+            THIP_RC(dual_gemv_partials(st, s->m, s->n, A, nullptr, xt, false, true, false, s->gemv_scr, half, &a, stop, hint));
+            prof_end(st);
+            prof_begin(st);
+            THIP_RC(dual_gemv_partials(st, s->m, s->n, A, xn, nullptr, true, false, false, s->gemv_scr + half, half, &b, stop, hint));
+            prof_end(st);
+            gp->partT = a.partT; gp->nT = a.nT; gp->strideT = a.strideT;
+            gp->partN = b.partN; gp->nN = b.nN; gp->strideN = b.strideN;
+        } else {
+            prof_begin(st);
+            THIP_RC(dual_gemv_partials(st, s->m, s->n, A, xn, xt, true, true, false, s->gemv_scr, s->gemv_scr_n, gp, stop, hint));
+            prof_end(st);
+        }
     }
-    if (s->sparse) {
-        // hN = A xn and gT = A^T xt as finished vectors (gathers over the CSR of A and of A^T); nN = nT = -1 tells
-        // post_k to take them as they are.  The stop flag is honoured by the consumers (a stray product is harmless).
-        (void)stop;
-        prof_begin(st);
-        THIP_RC(thip_spmv_csr(s->m, s->n, s->nnz, s->rp, s->ci, s->sv, 1.0f, xn, 0.0f, hN, 0));
-        THIP_RC(thip_spmv_csr(s->n, s->m, s->nnz, s->trp, s->tci, s->tsv, 1.0f, xt, 0.0f, gT, 0));
-        prof_end(st);
-        gp->nN = gp->nT = -1;
-        return 0;
-    }
-    if (s->schedule == THIP_SCHED_REFERENCE) {
-        GemvPartials a, b;
-        const size_t half = s->gemv_scr_n / 2;
-        prof_begin(st);
-        THIP_RC(dual_gemv_partials(st, s->m, s->n, s->amat(), s->alda(), nullptr, xt, false, true, false, s->gemv_scr, half, &a, stop, s->ahint(), s->a_kind, s->ainv(), s->apadz()));
-        prof_end(st);
-        prof_begin(st);
-        THIP_RC(dual_gemv_partials(st, s->m, s->n, s->amat(), s->alda(), xn, nullptr, true, false, false, s->gemv_scr + half, half, &b, stop, s->ahint(), s->a_kind, s->ainv(), s->apadz()));
-        prof_end(st);
-        gp->partT = a.partT; gp->nT = a.nT; gp->strideT = a.strideT;
-        gp->partN = b.partN; gp->nN = b.nN; gp->strideN = b.strideN;
-    } else {
-        prof_begin(st);
-        THIP_RC(dual_gemv_partials(st, s->m, s->n, s->amat(), s->alda(), xn, xt, true, true, false, s->gemv_scr, s->gemv_scr_n, gp, stop, s->ahint(), s->a_kind, s->ainv(), s->apadz()));
-        prof_end(st);
+    if (s->op != A_DENSE) gp->nN = gp->nT = -1;
+    return 0;
+}
+
+// |A| row sums (m) and column sums (n) of the preconditioner (solver.rs:171-172), as finished vectors
+int abs_sums(thip_solver *s, float *rowabs, float *colabs)
+{
+    hipStream_t st = ctx().stream;
+    GemvPartials gp;
+    if (s->n == 0 || s->m == 0) return 0;
+    switch (s->op) {
+    case A_TILED:
+        THIP_RC(spt_product(s, false, s->c, 1, nullptr, rowabs));
+        return spt_product(s, true, s->c, 1, nullptr, colabs);
+    case A_CSR2:
+        THIP_RC(csr_product(s, false, nullptr, 1, rowabs));
+        return csr_product(s, true, nullptr, 1, colabs);
+    case A_DENSE:      // solver-owned scratch (several solvers may share the context, e.g. one per thread)
+        THIP_RC(dual_gemv_partials(st, s->m, s->n, s->sa.in_use(), nullptr, nullptr, true, true, true, s->gemv_scr, s->gemv_scr_n,
+                                   &gp, nullptr));
+        THIP_RC(finalize_partials(st, s->m, gp.partN, gp.nN, gp.strideN, 1.0f, 0.0f, rowabs, nullptr));
+        return finalize_partials(st, s->n, gp.partT, gp.nT, gp.strideT, 1.0f, 0.0f, colabs, nullptr);
     }
     return 0;
+}
+
+// passes over the operator per iteration and the algorithmic bytes of one
+void traffic(const thip_solver *s, int *passes, size_t *bytes)
+{
+    const bool ref = s->schedule == THIP_SCHED_REFERENCE;
+    const int stages = (ref || s->schedule == THIP_SCHED_FUSED) ? 3 : (sweep_active(s) ? 1 : 2);
+    // a stage reads a dense / two-CSR A once (the reference schedule: in its two single GEMVs); of the tiled copy every product is
+    // one pass over the stored entries (8 bytes each)
+    *passes = (ref || s->op == A_TILED) ? 2 * stages : stages;
+    switch (s->op) {
+    case A_TILED:
+        *bytes = sptile_bytes_per_pass(s->spt);
+        break;
+    case A_CSR2:
+        *bytes = 2 * s->csr.nnz * (sizeof(float) + sizeof(int32_t));
+        break;
+    case A_DENSE:      // SURVEY.md 8d: 4 m n, or 2 m n for a 16-bit A; the padding rows of a library-owned copy (at most 15 per
+                       // column) are zeros that the kernel never loads
+        *bytes = s->m * s->n * s->sa.in_use().elem_bytes();
+    }
 }
 
 int project_blocks(thip_solver *s)
@@ -206,17 +262,8 @@ int one_iteration(thip_solver *s)
 // rank's own tuned plan.  A multiple of 8 floats keeps every buffer offset 32-byte aligned.
 size_t split_column(const thip_solver *s)
 {
-    if (s->sparse || s->m == 0 || s->n < 16) return 0;
+    if (s->op != A_DENSE || s->m == 0 || s->n < 16) return 0;
     return (s->n / 2) & ~(size_t)7;
-}
-
-// chunk rows the two half-launches fill under the plan in use
-void split_rows(thip_solver *s)
-{
-    const bool h16 = s->is16();
-    const bool vec_ok = (((uintptr_t)s->amat() & 15u) == 0) && (s->alda() % (h16 ? 8 : 4) == 0);
-    s->rows1 = dual_gemv_chunk_rows(s->m, s->n1, vec_ok, s->a_kind, s->ahint(), nullptr);
-    s->rows2 = dual_gemv_chunk_rows(s->m, s->n - s->n1, vec_ok, s->a_kind, s->ahint(), nullptr);
 }
 
 bool split_active(const thip_solver *s)
@@ -225,19 +272,20 @@ bool split_active(const thip_solver *s)
 }
 
 int autotune_gemv(thip_solver *s);
-bool sweep_active(const thip_solver *s);
 
 // decides the form of the next run: column-split (its own tuned plan, its split column) or one launch per pass
 int prepare_split(thip_solver *s)
 {
-    s->split_plan = s->overlap >= 2 && s->allreduce != nullptr && !s->sparse && s->carried_like()
+    s->split_plan = s->overlap >= 2 && s->allreduce != nullptr && s->op == A_DENSE && s->carried_like()
                     && s->m > 0 && s->n > 0;
     s->n1 = 0;
     if (s->inited && !sweep_active(s)) THIP_RC(autotune_gemv(s));        // once per stored form and launch form (a no-op afterwards)
     if (!s->split_plan) return 0;
     s->n1 = split_column(s);
     if (s->n1 == 0 || s->n1 >= s->n) { s->split_plan = false; s->n1 = 0; return 0; }
-    split_rows(s);
+    // chunk rows the two half-launches fill under the plan in use
+    s->rows1 = dual_gemv_chunk_rows(s->m, s->n1, s->sa.in_use(), s->hint_in_use(), nullptr);
+    s->rows2 = dual_gemv_chunk_rows(s->m, s->n - s->n1, s->sa.in_use(), s->hint_in_use(), nullptr);
     return 0;
 }
 
@@ -280,9 +328,9 @@ int products_cols(thip_solver *s, const float *xn, const float *xt, GemvPartials
 {
     hipStream_t st = ctx().stream;
     prof_begin(st);
-    THIP_RC(dual_gemv_partials_cols(st, s->m, s->n, s->amat(), s->alda(), xn, xt, true, true, s->gemv_scr, s->gemv_scr_n, gp,
-                                    &s->dst->stop, s->ahint(), s->a_kind, s->ainv(), s->apadz(), half ? s->n1 : 0,
-                                    half ? s->n : s->n1, half ? s->rows1 : 0, s->rows1 + s->rows2, nullptr));
+    THIP_RC(dual_gemv_partials_cols(st, s->m, s->n, s->sa.in_use(), xn, xt, true, true, false, s->gemv_scr, s->gemv_scr_n, gp,
+                                    &s->dst->stop, s->hint_in_use(), half ? s->n1 : 0, half ? s->n : s->n1,
+                                    half ? s->rows1 : 0, s->rows1 + s->rows2, nullptr));
     prof_end(st);
     return 0;
 }
@@ -390,9 +438,11 @@ int autotune_gemv(thip_solver *s)
 {
     const char *env = getenv("THIP_GEMV_AUTOTUNE");
     if (s->autotune == 0 || (s->autotune < 0 && env && atoi(env) == 0) || getenv("THIP_GEMV_NJ") || getenv("THIP_GEMV_BLOCKS")) return 0;
-    if (s->sparse || s->m * s->n < (size_t)1 << 22) return 0;   // sparse, or tiny: nothing to tune
-    const bool b16 = s->is16(), sp = s->split_plan;
-    if (sp ? (b16 ? s->tuned16_sp : s->tuned_sp) : (b16 ? s->tuned16 : s->tuned)) return 0;
+    if (s->op != A_DENSE || s->m * s->n < (size_t)1 << 22) return 0;   // sparse, or tiny: nothing to tune
+    const bool sp = s->split_plan;
+    const DenseA A = s->sa.in_use();
+    GemvPlan &plan = s->plan[A.is16()][sp];
+    if (plan.tuned) return 0;
     hipStream_t st = ctx().stream;
     hipEvent_t e0, e1;
     THIP_TRY(hipEventCreate(&e0));
@@ -405,22 +455,15 @@ int autotune_gemv(thip_solver *s)
     // one pass in the form the iteration will use: one launch, or (split) two launches over the column halves of the
     // candidate's own chunking
     auto one_pass = [&](const GemvHint *h) -> int {
-        if (!sp)
-            return dual_gemv_partials(st, s->m, s->n, s->amat(), s->alda(), s->u, s->v, true, true, false, s->gemv_scr,
-                                      s->gemv_scr_n, &gp, nullptr, h, s->a_kind, s->ainv(), s->apadz());
-        const bool h16 = s->is16();
-        const bool vec_ok = (((uintptr_t)s->amat() & 15u) == 0) && (s->alda() % (h16 ? 8 : 4) == 0);
-        const size_t n1 = split_column(s);
+        const size_t n1 = sp ? split_column(s) : 0;
         if (n1 == 0 || n1 >= s->n)
-            return dual_gemv_partials(st, s->m, s->n, s->amat(), s->alda(), s->u, s->v, true, true, false, s->gemv_scr,
-                                      s->gemv_scr_n, &gp, nullptr, h, s->a_kind, s->ainv(), s->apadz());
-        const int r1 = dual_gemv_chunk_rows(s->m, n1, vec_ok, s->a_kind, h, nullptr);
-        const int r2 = dual_gemv_chunk_rows(s->m, s->n - n1, vec_ok, s->a_kind, h, nullptr);
-        THIP_RC(dual_gemv_partials_cols(st, s->m, s->n, s->amat(), s->alda(), s->u, s->v, true, true, s->gemv_scr, s->gemv_scr_n,
-                                        &gp, nullptr, h, s->a_kind, s->ainv(), s->apadz(), 0, n1, 0, r1 + r2, nullptr));
-        THIP_RC(dual_gemv_partials_cols(st, s->m, s->n, s->amat(), s->alda(), s->u, s->v, true, true, s->gemv_scr, s->gemv_scr_n,
-                                        &gp, nullptr, h, s->a_kind, s->ainv(), s->apadz(), n1, s->n, r1, r1 + r2, nullptr));
-        return 0;
+            return dual_gemv_partials(st, s->m, s->n, A, s->u, s->v, true, true, false, s->gemv_scr, s->gemv_scr_n, &gp, nullptr, h);
+        const int r1 = dual_gemv_chunk_rows(s->m, n1, A, h, nullptr);
+        const int r2 = dual_gemv_chunk_rows(s->m, s->n - n1, A, h, nullptr);
+        THIP_RC(dual_gemv_partials_cols(st, s->m, s->n, A, s->u, s->v, true, true, false, s->gemv_scr, s->gemv_scr_n, &gp, nullptr, h,
+                                        0, n1, 0, r1 + r2, nullptr));
+        return dual_gemv_partials_cols(st, s->m, s->n, A, s->u, s->v, true, true, false, s->gemv_scr, s->gemv_scr_n, &gp, nullptr, h,
+                                       n1, s->n, r1, r1 + r2, nullptr);
     };
     for (int w = 0; w < 3; ++w)         // clocks and caches settle before anything is timed
         THIP_RC(one_pass(nullptr));
@@ -442,13 +485,7 @@ int autotune_gemv(thip_solver *s)
         }
         if (ms < best) { best = ms; pick = c[i]; }
     }
-    if (sp) {
-        if (b16) { s->hint16_sp = pick; s->tuned16_sp = true; s->tuned16_sp_ms = best; }
-        else     { s->hint_sp = pick; s->tuned_sp = true; s->tuned_sp_ms = best; }
-    } else {
-        if (b16) { s->hint16 = pick; s->tuned16 = true; s->tuned16_ms = best; }
-        else     { s->hint = pick; s->tuned = true; s->tuned_ms = best; }
-    }
+    plan = GemvPlan{ pick, true, best };
     THIP_TRY(hipEventDestroy(e0));
     THIP_TRY(hipEventDestroy(e1));
     return 0;

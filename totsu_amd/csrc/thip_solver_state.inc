@@ -4,9 +4,42 @@
 // host side
 // ---------------------------------------------------------------------------------------------------
 
+// The operator the iteration applies, decided once by thip_solver_create / _set_csr / _set_sptile: a dense matrix (in one of its
+// stored forms: StoredA), the CSR of A and of A^T, or ONE tiled copy serving both products (thip_sptile.hip)
+enum OpKind { A_DENSE = 0, A_CSR2, A_TILED };
+struct Csr2 { size_t nnz; const int64_t *rp, *trp; const int32_t *ci, *tci; const float *sv, *tsv; };
+
+// The stored forms of a dense A and which one the iteration streams: the caller's f32 matrix (ld = m); a library-owned f32 copy
+// with the leading dimension padded to a multiple of 16 floats (m % 16 != 0, e.g. the k = 500 SDP: m = 125 250; a 12 500-row shard),
+// made by ensure_apad() when an f32 pass is about to run and the copy fits a third of the free HBM; ONE 16-bit copy at a time,
+// library-owned (ld16 = m rounded to 8) or caller-built: kind16 = bf16 or scaled f16, inv_s = the f16 column scales
+struct StoredA {
+    size_t m = 0; const float *f32 = nullptr;
+    float *pad = nullptr; size_t ldpad = 0;
+    uint16_t *a16 = nullptr; size_t ld16 = 0; bool a16_owned = false; int kind16 = 0;
+    float *inv_s = nullptr; bool inv_s_owned = false;
+    int kind = THIP_A_F32;        // the form in use: THIP_A_F32, or the 16-bit copy's kind
+    bool is16() const { return kind != THIP_A_F32; }
+    // (pad_zero: rows m .. lda - 1 of the matrix in use are zeros written by this library -- its padded f32 copy, or a 16-bit copy it made)
+    DenseA in_use() const
+    {
+        if (is16()) return DenseA{ a16, ld16, kind, kind == THIP_A_F16 ? inv_s : nullptr, a16_owned };
+        return pad ? DenseA{ pad, ldpad, THIP_A_F32, nullptr, true } : DenseA{ f32, m, THIP_A_F32, nullptr, false };
+    }
+    hipError_t free_pad() { float *p = pad; pad = nullptr; ldpad = 0; return hipFree(p); }
+    hipError_t free16()          // (a caller-built copy is only forgotten)
+    {
+        const hipError_t e0 = a16_owned ? hipFree(a16) : hipSuccess, e1 = inv_s_owned ? hipFree(inv_s) : hipSuccess;
+        a16 = nullptr; inv_s = nullptr; a16_owned = inv_s_owned = false;
+        return e0 != hipSuccess ? e0 : e1;
+    }
+};
+// a tuned tiling of the dual GEMV and the time of one pass under it
+struct GemvPlan { GemvHint hint{0, 0}; bool tuned = false; float ms = 0.0f; };
+
 struct thip_solver {
     size_t n = 0, m = 0;
-    const float *A = nullptr, *b = nullptr, *c = nullptr, *b_rowabs = nullptr;
+    const float *b = nullptr, *c = nullptr, *b_rowabs = nullptr;
     thip_param par{};
     int schedule = THIP_SCHED_FUSED;
 
@@ -33,14 +66,13 @@ struct thip_solver {
     unsigned gseq[4] = { 0, 0, 0, 0 };
     long long gate_ticks = 0;
 
-    // optional sparse A (CSR of A and of A^T)
-    bool sparse = false; size_t nnz = 0;
-    const int64_t *rp = nullptr, *trp = nullptr;
-    const int32_t *ci = nullptr, *tci = nullptr;
-    const float *sv = nullptr, *tsv = nullptr;
-    // ... or ONE tiled copy serving both products (thip_sptile.hip; thip_solver_set_sptile): the slices' shares of the N
-    // products go to sw_partH (the buffer the one-pass schedule's m-tail reads), those of the T products to sw_partT
-    thip_sptile *spt = nullptr; float *sw_partT = nullptr;
+    OpKind op = A_DENSE;
+    StoredA sa;
+    Csr2 csr{};
+    // the tiled copy (caller-held, possibly shared with other solvers) and this solver's launch state for it (spt_buffers): the
+    // slices' shares of the N products go to sw_partH (the buffer the one-pass schedule's m-tail reads), those of the T products
+    // to sw_partT; spt_xmax = the block maxima of the in-vectors of the product in flight (2 x SPT_NMAX floats)
+    thip_sptile *spt = nullptr; float *sw_partT = nullptr, *spt_xmax = nullptr;
 
     // cone structure
     std::vector<int32_t> seg_type;
@@ -68,34 +100,15 @@ struct thip_solver {
     float *part = nullptr;                           // block partials (4 * EG)
     float *dotc = nullptr;                           // local scalars: [0] c.u, [1] c.rx_x, [2..3] dd,cx
     float *gemv_scr = nullptr; size_t gemv_scr_n = 0;
-    GemvHint hint{0, 0}; bool tuned = false; float tuned_ms = 0.0f;
-    // storage of A streamed by the iteration: the caller's f32 matrix, or an owned bf16 copy (ld16 = m rounded to 8)
-    // (one 16-bit copy at a time: a16_kind says whether A16 holds bf16 or scaled f16; inv_s = the f16 column scales)
-    int a_kind = THIP_A_F32; uint16_t *A16 = nullptr; size_t ld16 = 0; bool A16_owned = false; int a16_kind = 0;
-    float *inv_s = nullptr; bool inv_s_owned = false;
-    GemvHint hint16{0, 0}; bool tuned16 = false; float tuned16_ms = 0.0f;
-    // the column-split form (overlap modes 2 / 3) has its own tuned plans: a half-launch has half the workgroups of the
-    // whole-matrix launch, so the best tiling differs (the 12 500 x 50 000 shard: ~1k tall tiles unsplit)
+    // The tuned plans of the dual GEMV, one per stored element width and launch form: [16-bit copy in use][column split].  The
+    // column-split form (overlap modes 2 / 3) has its own: a half-launch has half the workgroups of the whole-matrix launch, so
+    // the best tiling differs (the 12 500 x 50 000 shard: ~1k tall tiles unsplit)
+    GemvPlan plan[2][2];
     bool split_plan = false;      // the next run streams A as two column-half launches per pass
-    GemvHint hint_sp{0, 0}; bool tuned_sp = false; float tuned_sp_ms = 0.0f;
-    GemvHint hint16_sp{0, 0}; bool tuned16_sp = false; float tuned16_sp_ms = 0.0f;
-    // f32 with m % 16 != 0 (e.g. the k = 500 SDP: m = 125 250; a 12 500-row shard): a library-owned copy with the leading
-    // dimension padded to a multiple of 16 floats, made by ensure_apad() when an f32 pass is about to run and the copy
-    // fits a third of the free HBM
-    float *Apad = nullptr; size_t ldpad = 0;
     int lda_pad = -1;             // thip_solver_set_lda_pad: -1 = default (16 floats, or THIP_LDA_PAD), 0 = never copy
     int autotune = -1;            // thip_solver_set_gemv_autotune: -1 = default (on, or THIP_GEMV_AUTOTUNE), 0 / 1
-    bool is16() const { return a_kind != THIP_A_F32; }
-    const void *amat() const { return is16() ? (const void *)A16 : (Apad ? (const void *)Apad : (const void *)A); }
-    size_t alda() const { return is16() ? ld16 : (Apad ? ldpad : m); }
-    // rows m .. alda() - 1 of the matrix in use are zeros written by this library (its padded f32 copy, or a 16-bit copy it made)
-    bool apadz() const { return is16() ? A16_owned : Apad != nullptr; }
-    const float *ainv() const { return a_kind == THIP_A_F16 ? inv_s : nullptr; }
-    const GemvHint *ahint() const
-    {
-        if (split_plan) return is16() ? (tuned16_sp ? &hint16_sp : nullptr) : (tuned_sp ? &hint_sp : nullptr);
-        return is16() ? (tuned16 ? &hint16 : nullptr) : (tuned ? &hint : nullptr);
-    }
+    const GemvPlan &plan_in_use() const { return plan[sa.is16()][split_plan]; }
+    const GemvHint *hint_in_use() const { return plan_in_use().tuned ? &plan_in_use().hint : nullptr; }
     // THIP_SCHED_SWEEP (thip_sweep.hip): the second x_x buffer (x_x_{k+1} is formed while x_x_k is still the iterate), its
     // Kahan term, the groups' shares of the N products, the granule ring, the census words, block partials
     float *xx2 = nullptr, *kx2 = nullptr, *xx_home = nullptr, *kx_home = nullptr;
@@ -235,9 +248,22 @@ int allreduce_end(thip_solver *s)
 
 unsigned egrid(size_t n) { return grid_for(n, BLK, EG); }
 
+// EVERY change of the stored form of A goes through here; nothing else clears a plan's validity.  PLANS_F32: the padded f32 copy
+// was freed, re-pitched or freshly made (the f32 plans were timed on the other pitch); PLANS_16: the library's 16-bit copy was
+// (re)built in another format; both: the autotune was switched off (back to the shape heuristic); KIND: the form in use changed --
+// the one-pass schedule is planned per stored form (another kernel instance), and inside a solve gP / hP of the carried
+// schedules still hold products with the old matrix (rebuild_carried, by the next thip_solver_run)
+enum { PLANS_F32 = 1, PLANS_16 = 2, KIND = 4 };
+void stored_form_changed(thip_solver *s, unsigned what)
+{
+    if (what & PLANS_F32) s->plan[0][0].tuned = s->plan[0][1].tuned = false;
+    if (what & PLANS_16) s->plan[1][0].tuned = s->plan[1][1].tuned = false;
+    if (what & KIND) { s->sweep_state = 0; s->carried_stale = s->carried_stale || s->inited; }
+}
+
 int ensure_gemv_scratch(thip_solver *s)
 {
-    if (s->gemv_scr || s->sparse || s->m == 0 || s->n == 0) return 0;
+    if (s->gemv_scr || s->op != A_DENSE || s->m == 0 || s->n == 0) return 0;
     s->gemv_scr_n = 2 * dual_gemv_scratch_floats(s->m, s->n);
     THIP_TRY(hipMalloc((void **)&s->gemv_scr, s->gemv_scr_n * sizeof(float)));
     return 0;

@@ -9,8 +9,8 @@ namespace {
 // placement census came out as 8 x 32 in a dry run.  Examined once per (re)initialisation.
 int sweep_pass(thip_solver *s, int first, int np_m = 0, bool timing = false);
 
-// the partial-sum buffers of a solver on the tiled sparse copy (zeroed once: a block without entries is never written) and the
-// words the sweep schedule's host side reads (error word, block partials)
+// the launch state of a solver on the tiled sparse copy -- the partial-sum buffers (zeroed once: a block without entries is never
+// written), the block maxima of the in-vectors -- and the words the sweep schedule's host side reads (error word, block partials)
 int spt_buffers(thip_solver *s)
 {
     hipStream_t st = ctx().stream;
@@ -19,8 +19,10 @@ int spt_buffers(thip_solver *s)
         if (s->sw_partH) { THIP_TRY(hipFree(s->sw_partH)); s->sw_partH = nullptr; }
         THIP_TRY(hipMalloc((void **)&s->sw_partH, fh * sizeof(float)));
         THIP_TRY(hipMalloc((void **)&s->sw_partT, ft * sizeof(float)));
+        THIP_TRY(hipMalloc((void **)&s->spt_xmax, 2 * SPT_NMAX * sizeof(float)));
         THIP_TRY(hipMemsetAsync(s->sw_partH, 0, fh * sizeof(float), st));
         THIP_TRY(hipMemsetAsync(s->sw_partT, 0, ft * sizeof(float), st));
+        THIP_TRY(hipMemsetAsync(s->spt_xmax, 0, 2 * SPT_NMAX * sizeof(float), st));
     }
     if (!s->sw_census) {
         THIP_TRY(hipMalloc((void **)&s->sw_census, 64 * sizeof(unsigned)));
@@ -33,7 +35,7 @@ int spt_buffers(thip_solver *s)
 
 int sweep_prepare(thip_solver *s)
 {
-    if (s->spt) {
+    if (s->op == A_TILED) {
         // the tiled sparse copy: no persistent kernel, no placement census, no geometry to time -- the one-pass recurrence
         // in three launches (sweep_pass) whenever it was asked for on one GPU
         THIP_RC(spt_buffers(s));
@@ -50,7 +52,7 @@ int sweep_prepare(thip_solver *s)
     }
     if (s->schedule != THIP_SCHED_SWEEP) return 0;
     if ((s->allreduce != nullptr) != s->col_shard) return 0;      // row shards run the carried schedule; column shards need the hook
-    if (s->sparse || s->m == 0 || s->n == 0) return 0;      // not now (may change)
+    if (s->op != A_DENSE || s->m == 0 || s->n == 0) return 0;      // not now (may change)
     if (s->sweep_state != 0) return 0;
     s->sweep_state = -1;
     // a (re-)plan restarts the schedule from the consistent iterate: the timing sweeps below rewrite the groups' shares and
@@ -58,12 +60,12 @@ int sweep_prepare(thip_solver *s)
     s->sw_first = true;
     static const int env_off = getenv("THIP_SWEEP_OFF") ? atoi(getenv("THIP_SWEEP_OFF")) : 0;
     if (env_off) return 0;
-    size_t m_eff = s->m;
-    const int elem = s->a_kind;                   // THIP_A_F32, or the 16-bit form the iteration streams now
-    const size_t esize = elem ? 2 : 4;
-    // a library-owned padded copy has zero rows behind row m, and every m-vector of the arena has zeros behind entry m
-    if (!elem && m_eff % 4 != 0 && s->Apad != nullptr && s->ldpad >= (m_eff + 3) / 4 * 4) m_eff = (m_eff + 3) / 4 * 4;
-    if (elem && m_eff % 8 != 0 && s->A16_owned && s->ld16 >= (m_eff + 7) / 8 * 8) m_eff = (m_eff + 7) / 8 * 8;
+    const DenseA A = s->sa.in_use();              // f32, or the 16-bit form the iteration streams now
+    const int elem = A.kind;
+    const size_t esize = A.elem_bytes(), epv = A.vec_elems();
+    // a library-owned copy has zero rows behind row m, and every m-vector of the arena has zeros behind entry m
+    const size_t m_up = (s->m + epv - 1) / epv * epv;
+    const size_t m_eff = (A.pad_zero && A.lda >= m_up) ? m_up : s->m;
     if (!s->col_shard && s->m * s->n * esize < s->sweep_min_bytes) return 0;
     // how the partial dots are published in this process: decided HERE, at plan time (the self-test allocates 64 MB and
     // synchronises; left to the first sweep_pass it ran in the middle of the first batch when the autotune is off)
@@ -71,8 +73,8 @@ int sweep_prepare(thip_solver *s)
     // the geometries the kernel offers for this matrix (group size, columns per panel); THIP_SWEEP_CLASS pins one
     SweepGeom cand[6];
     int nc = 0;
-    if (getenv("THIP_SWEEP_CLASS")) { if (sweep_plan(m_eff, s->n, s->alda(), s->amat(), &cand[0], elem) == 0) nc = 1; }
-    else nc = sweep_candidates(m_eff, s->n, s->alda(), s->amat(), cand, 6, elem);
+    if (getenv("THIP_SWEEP_CLASS")) { if (sweep_plan(m_eff, s->n, A, &cand[0]) == 0) nc = 1; }
+    else nc = sweep_candidates(m_eff, s->n, A, cand, 6);
     if (nc == 0) return 0;
     hipStream_t st = ctx().stream;
     if (!s->sw_census) {
@@ -160,7 +162,8 @@ int sweep_prepare(thip_solver *s)
             double carried_ms = 2.0 * (double)s->m * (double)s->n * esize / 6.2e12 * 1e3 + 0.03;
             if ((double)s->sw_plan_ms > 0.75 * carried_ms) {
                 THIP_RC(autotune_gemv(s));
-                const float pass_ms = elem ? (s->tuned16 ? s->tuned16_ms : 0.0f) : (s->tuned ? s->tuned_ms : 0.0f);
+                const GemvPlan &one = s->plan[elem != 0][0];       // (the one-launch form: no collective on this path)
+                const float pass_ms = one.tuned ? one.ms : 0.0f;
                 if (pass_ms > 0.0f) carried_ms = 2.0 * (double)pass_ms + 0.03;
             }
             if ((double)s->sw_plan_ms > carried_ms) return 0;
@@ -183,12 +186,12 @@ int sweep_prepare(thip_solver *s)
 
 bool sweep_active(const thip_solver *s)
 {
-    if (s->spt) return s->schedule == THIP_SCHED_SWEEP && s->sweep_state == 1 && s->allreduce == nullptr && !s->col_shard;
-    if (!(s->schedule == THIP_SCHED_SWEEP && s->sweep_state == 1 && (s->allreduce != nullptr) == s->col_shard && !s->sparse
-          && s->sgeom.elem == s->a_kind)) return false;       // (planned for the stored form of A in use now)
+    if (s->schedule != THIP_SCHED_SWEEP || s->sweep_state != 1) return false;
+    if (s->op == A_TILED) return s->allreduce == nullptr && !s->col_shard;
+    const DenseA A = s->sa.in_use();
+    if (s->op != A_DENSE || (s->allreduce != nullptr) != s->col_shard || s->sgeom.elem != A.kind) return false;       // (planned for the stored form of A in use now)
     // planned on the padded copy (m not a multiple of the rows per slot): only while that copy is the matrix in use
-    if ((size_t)s->sgeom.m_eff == s->m) return true;
-    return s->is16() ? (s->A16_owned && s->ld16 >= (size_t)s->sgeom.m_eff) : (s->Apad != nullptr && s->ldpad >= (size_t)s->sgeom.m_eff);
+    return (size_t)s->sgeom.m_eff == s->m || (A.pad_zero && A.lda >= (size_t)s->sgeom.m_eff);
 }
 
 int sweep_pass(thip_solver *s, int first, int np_m, bool timing)
@@ -196,8 +199,9 @@ int sweep_pass(thip_solver *s, int first, int np_m, bool timing)
     hipStream_t st = ctx().stream;
     const SweepGeom &g = s->sgeom;
     SweepArgs a;
-    a.A = reinterpret_cast<const float *>(s->amat()); a.lda = s->alda(); a.m = g.m_eff; a.n = (int)s->n;
-    a.inv_s = s->ainv();
+    const DenseA A = s->sa.in_use();
+    a.A = reinterpret_cast<const float *>(A.mat); a.lda = A.lda; a.m = g.m_eff; a.n = (int)s->n;
+    a.inv_s = A.inv_s;
     a.G = g.G; a.rows_per_member = g.rows_per_member; a.cols_per_group = g.cols_per_group;
     a.v = s->v; a.xy = s->xy; a.c = s->c; a.Su = s->Su; a.Tx = s->Tx;
     a.u = s->u; a.ku = s->comp() ? s->ku : nullptr;
@@ -237,14 +241,14 @@ int sweep_pass(thip_solver *s, int first, int np_m, bool timing)
     a.fault = 0;
     if (!first && s->fault_kind == 2 && s->fault_after >= 0 && s->fault_after-- == 0) { a.fault = 1; s->fault_kind = 0; }
     if (!first && s->fault_kind == 7 && (s->fault_after < 0 || s->fault_after-- <= 0)) { a.fault = 1; s->fault_after = -1; }      // every sweep from then on
-    if (s->spt) {
+    if (s->op == A_TILED) {
         // A^T [v x_y] -> per column: u_k[j], x_x_{k+1}[j], kappa, the sums over n -> A [u_k x_x_{k+1}] as the slices' shares
         prof_begin(st);
-        THIP_RC(sptile_product(st, s->spt, true, a.v, a.xy, s->sw_partT, 0, a.stop));
+        THIP_RC(sptile_product(st, s->spt, true, a.v, a.xy, s->sw_partT, s->spt_xmax, 0, a.stop));
         prof_end(st);
-        THIP_RC(sptile_colupdate(st, s->spt, a, s->sw_partT));
+        THIP_RC(sptile_colupdate(st, s->spt, a, s->sw_partT, s->spt_xmax));
         prof_begin(st);
-        THIP_RC(sptile_product(st, s->spt, false, a.u, a.xx_out, s->sw_partH, 0, a.stop, true));      // (sp_col_k left the block maxima)
+        THIP_RC(sptile_product(st, s->spt, false, a.u, a.xx_out, s->sw_partH, s->spt_xmax, 0, a.stop, true));      // (sp_col_k left the block maxima)
         prof_end(st);
         return 0;
     }
@@ -261,9 +265,6 @@ void sweep_swap(thip_solver *s)
     s->kx = b0 ? s->kx2 : s->kx_home;
     s->xbuf ^= 1;
 }
-
-// the x_x buffer that is NOT the iterate: x_x_{k+1} after a sweep
-float *sweep_next(thip_solver *s) { return s->xbuf == 0 ? s->xx2 : s->xx_home; }
 
 // last: the host looks at the status block after this iteration (end of a polling batch / of the run)
 int one_iteration_sweep(thip_solver *s, bool last)
@@ -324,7 +325,7 @@ int one_iteration_sweep(thip_solver *s, bool last)
     if (foldable && (merge || cone_merge)) s->pm_par ^= 1;
     float *const pm = pm_cur();
     // (a sparse operator with at most four slices per row block: the one-thread-per-row form of the two sw_xm_k launches)
-    const bool flat_rows = s->spt != nullptr && !cols && s->sgeom.ngroups <= 4;
+    const bool flat_rows = s->op == A_TILED && !cols && s->sgeom.ngroups <= 4;
     const unsigned xm_threads = (flat_rows && s->m > (size_t)EG * 1024) ? 1024u : (unsigned)BLK;
     if (merge) {
         hipLaunchKernelGGL((flat_rows ? sw_xm_k<true, true> : sw_xm_k<true, false>), dim3(gx), dim3(xm_threads), 0, st, m, cols ? 1 : s->sgeom.ngroups, s->sgeom.mpad,
@@ -369,31 +370,33 @@ int one_iteration_sweep(thip_solver *s, bool last)
 // thip_solver_set_lda_pad.
 int ensure_apad(thip_solver *s, bool refresh)
 {
-    if (s->sparse || !s->A || s->m == 0 || s->n == 0) return 0;
+    StoredA &sa = s->sa;
+    if (s->op != A_DENSE || !sa.f32 || s->m == 0 || s->n == 0) return 0;
     hipStream_t st = ctx().stream;
     const size_t m = s->m, n = s->n;
     size_t padto = 16;
     if (s->lda_pad >= 0) padto = (size_t)s->lda_pad;
     else if (getenv("THIP_LDA_PAD")) padto = (size_t)atoi(getenv("THIP_LDA_PAD"));
-    if (padto == 0 || m % padto == 0) {
-        if (s->Apad) { THIP_TRY(hipStreamSynchronize(st)); THIP_TRY(hipFree(s->Apad)); s->Apad = nullptr; s->ldpad = 0; s->tuned = s->tuned_sp = false; }
-        return 0;
+    const size_t ld = (padto == 0 || m % padto == 0) ? 0 : (m + padto - 1) / padto * padto;      // 0: no copy wanted
+    if (sa.pad && sa.ldpad != ld) {      // freed, or re-pitched below
+        THIP_TRY(hipStreamSynchronize(st));
+        THIP_TRY(sa.free_pad());
+        stored_form_changed(s, PLANS_F32);
     }
-    const size_t ld = (m + padto - 1) / padto * padto;
-    if (s->Apad && s->ldpad != ld) { THIP_TRY(hipStreamSynchronize(st)); THIP_TRY(hipFree(s->Apad)); s->Apad = nullptr; s->tuned = s->tuned_sp = false; }
+    if (ld == 0) return 0;
     bool fresh = false;
-    if (!s->Apad) {
+    if (!sa.pad) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
         if (ld * n * sizeof(float) >= free_b / 3) return 0;
-        s->ldpad = ld;
-        THIP_TRY(hipMalloc((void **)&s->Apad, ld * n * sizeof(float)));
-        THIP_TRY(hipMemsetAsync(s->Apad, 0, ld * n * sizeof(float), st));
+        THIP_TRY(hipMalloc((void **)&sa.pad, ld * n * sizeof(float)));
+        sa.ldpad = ld;
+        THIP_TRY(hipMemsetAsync(sa.pad, 0, ld * n * sizeof(float), st));
         fresh = true;
-        s->tuned = s->tuned_sp = false;             // the plans were timed on the other pitch
+        stored_form_changed(s, PLANS_F32);             // the plans were timed on the other pitch
     }
     if (fresh || refresh)
-        THIP_TRY(hipMemcpy2DAsync(s->Apad, ld * sizeof(float), s->A, m * sizeof(float), m * sizeof(float), n,
+        THIP_TRY(hipMemcpy2DAsync(sa.pad, ld * sizeof(float), sa.f32, m * sizeof(float), m * sizeof(float), n,
                                   hipMemcpyDeviceToDevice, st));
     return 0;
 }

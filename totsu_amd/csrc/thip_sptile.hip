@@ -88,7 +88,7 @@ struct SptArgs {
 };
 
 constexpr int SPT_FIX_BITS = 50;        // bits of a fixed-point partial sum below the sign (see spt_add)
-constexpr int SPT_NMAX = 256;           // block maxima per in-vector
+// (SPT_NMAX, thip_common.h: block maxima per in-vector)
 
 // block maxima of |x0|, |x1| (x1 may be NULL): part[b], part[SPT_NMAX + b]; every block of the grid writes its slot
 // (256 or 1024 threads: at most SPT_NMAX blocks, so a long vector -- a stencil's 9 M -- needs the wider block to keep the loads in flight)
@@ -573,12 +573,12 @@ struct thip_sptile {
     size_t mpad = 0, npad = 0;
     f32x4 *vals = nullptr; i32x4 *idx = nullptr; SptTile *tiles = nullptr; int *order = nullptr;
     SptItem *itemsN = nullptr, *itemsT = nullptr;
-    // partial sums of the trait-level products (thip_sptile_mv), made on first use
-    float *partN = nullptr, *partT = nullptr;
-    // fixed-point accumulation: |value| < 2^(a_exp + 1); at most 2^headN / 2^headT entries in a row / column; block maxima of the
-    // in-vectors of the launch in flight (2 x SPT_NMAX floats)
+    // fixed-point accumulation: |value| < 2^(a_exp + 1); at most 2^headN / 2^headT entries in a row / column
     int a_exp = 0, headN = 1, headT = 1;
-    float *xmax = nullptr;
+    // launch state of the HANDLE-LEVEL entry points only (thip_sptile_mv, thip_test_sptile_time: one host thread at a time per
+    // handle): the slices' partial sums, made on first use, and the block maxima of the in-vectors (2 x SPT_NMAX floats).  A solver
+    // brings its own (spt_buffers), so the products below never write through the matrix and any number of solvers may share it
+    struct MvWork { float *partN = nullptr, *partT = nullptr, *xmax = nullptr; } mv;
     int64_t max_visit = 0;      // entries of the largest tile
     int ndense = 0;             // tiles stored without indices
     size_t nidx = 0;            // entries that carry an index
@@ -595,10 +595,10 @@ void sptile_dims(const thip_sptile *M, size_t *m, size_t *n, size_t *nnz) { *m =
 // part[slice][2][pad] <- the slices' shares of A [in0 in1] (tphase: of A^T [in0 in1]); in1 == NULL: one right-hand side (the
 // second half of every slice is then left alone); abs_mode: |A| times ones.  `part` must have been zeroed once after its
 // allocation: a (block, slice) without entries is never written.
-// xmax_ready: the kernel that produced in0 / in1 left their block maxima in M->xmax (all SPT_NMAX slots of each: sp_col_k does, for
-// the N product of the one-pass loop) -- no sp_absmax_k launch.
+// xmax: the launcher's block maxima (2 x SPT_NMAX floats); xmax_ready: the kernel that produced in0 / in1 left them there (all
+// SPT_NMAX slots of each: sp_col_k does, for the N product of the one-pass loop) -- no sp_absmax_k launch.
 int sptile_product(hipStream_t st, const thip_sptile *M, bool tphase, const float *in0, const float *in1, float *part,
-                   int abs_mode, const int *stop, bool xmax_ready)
+                   float *xmax, int abs_mode, const int *stop, bool xmax_ready)
 {
     const int items = tphase ? M->nT : M->nN;
     if (items == 0) return 0;
@@ -608,12 +608,12 @@ int sptile_product(hipStream_t st, const thip_sptile *M, bool tphase, const floa
     a.in0 = in0; a.in1 = in1; a.in_len = (int)(tphase ? M->m : M->n);
     a.part = part; a.opad = tphase ? M->npad : M->mpad;
     a.abs_mode = abs_mode; a.stop = stop ? stop : ctx().never_stop;
-    a.xmax = M->xmax; a.a_exp = M->a_exp; a.head_bits = tphase ? M->headT : M->headN; a.nmax = 1;
+    a.xmax = xmax; a.a_exp = M->a_exp; a.head_bits = tphase ? M->headT : M->headN; a.nmax = 1;
     if (!abs_mode && xmax_ready) a.nmax = SPT_NMAX;
     else if (!abs_mode) {
         const int len = a.in_len;
         a.nmax = (int)std::min<size_t>(SPT_NMAX, std::max<size_t>(1, ((size_t)len + 1023) / 1024));
-        hipLaunchKernelGGL(sp_absmax_k, dim3(a.nmax), dim3(len > SPT_NMAX * 1024 ? 1024 : 256), 0, st, in0, in1, len, M->xmax);
+        hipLaunchKernelGGL(sp_absmax_k, dim3(a.nmax), dim3(len > SPT_NMAX * 1024 ? 1024 : 256), 0, st, in0, in1, len, xmax);
     }
     constexpr size_t lds_full = (size_t)SPT_TB * (2 * sizeof(unsigned long long) + sizeof(float2));
     constexpr size_t lds_lite = (size_t)SPT_TB * (2 * sizeof(unsigned long long));
@@ -646,10 +646,10 @@ int sptile_product(hipStream_t st, const thip_sptile *M, bool tphase, const floa
     return 0;
 }
 
-int sptile_colupdate(hipStream_t st, const thip_sptile *M, const SweepArgs &a, const float *partT)
+int sptile_colupdate(hipStream_t st, const thip_sptile *M, const SweepArgs &a, const float *partT, float *xmax)
 {
     SpColArgs ca;
-    ca.a = a; ca.partT = partT; ca.nsl = M->slT; ca.npad = M->npad; ca.xmax = M->xmax;
+    ca.a = a; ca.partT = partT; ca.nsl = M->slT; ca.npad = M->npad; ca.xmax = xmax;
     static_assert(SPT_NMAX == 256, "sp_col_k's grid fills every slot of the block maxima");
     hipLaunchKernelGGL(sp_col_k, dim3(256), dim3(M->n > (size_t)256 * 1024 ? 1024 : 256), 0, st, ca);
     THIP_LAUNCH_CHECK();
@@ -893,8 +893,8 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
     THIP_RC(upload(order, &M->order));
     THIP_RC(upload(itN, &M->itemsN));
     THIP_RC(upload(itT, &M->itemsT));
-    THIP_TRY(hipMalloc((void **)&M->xmax, 2 * SPT_NMAX * sizeof(float)));
-    THIP_TRY(hipMemset(M->xmax, 0, 2 * SPT_NMAX * sizeof(float)));
+    THIP_TRY(hipMalloc((void **)&M->mv.xmax, 2 * SPT_NMAX * sizeof(float)));
+    THIP_TRY(hipMemset(M->mv.xmax, 0, 2 * SPT_NMAX * sizeof(float)));
     return 0;
 }
 
@@ -920,7 +920,7 @@ int thip_sptile_destroy(thip_sptile *M)
     if (!M) return 0;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     for (void *p : { (void *)M->vals, (void *)M->idx, (void *)M->tiles, (void *)M->order, (void *)M->itemsN, (void *)M->itemsT,
-                     (void *)M->partN, (void *)M->partT, (void *)M->xmax })
+                     (void *)M->mv.partN, (void *)M->mv.partT, (void *)M->mv.xmax })
         if (p) (void)hipFree(p);
     delete M;
     return 0;
@@ -960,13 +960,13 @@ int thip_sptile_mv(thip_sptile *M, int transpose, float alpha, const float *x, f
     const bool t = transpose != 0;
     const size_t len = t ? M->n : M->m;
     if (len == 0) return 0;
-    float *&part = t ? M->partT : M->partN;
+    float *&part = t ? M->mv.partT : M->mv.partN;
     if (!part) {
         const size_t fl = sptile_part_floats(M, t);
         THIP_TRY(hipMalloc((void **)&part, fl * sizeof(float)));
         THIP_TRY(hipMemsetAsync(part, 0, fl * sizeof(float), st));
     }
-    THIP_RC(sptile_product(st, M, t, abs_mode ? (const float *)M->vals : x, nullptr, part, abs_mode, nullptr));
+    THIP_RC(sptile_product(st, M, t, abs_mode ? (const float *)M->vals : x, nullptr, part, M->mv.xmax, abs_mode, nullptr));
     return finalize_partials(st, len, part, sptile_slices(M, t), 2 * sptile_pad(M, t), alpha, beta, y, nullptr);
 }
 
@@ -990,7 +990,7 @@ int thip_test_sptile_time(thip_sptile *M, int reps, float *host_ms)
         float best = 1e30f, tot = 0.0f;
         for (int r = 0; r <= reps; ++r) {
             THIP_TRY(hipEventRecord(e0, st));
-            THIP_RC(sptile_product(st, M, ph == 0, ones, ones + nv, ph == 0 ? pt : pn, 0, nullptr));
+            THIP_RC(sptile_product(st, M, ph == 0, ones, ones + nv, ph == 0 ? pt : pn, M->mv.xmax, 0, nullptr));
             THIP_TRY(hipEventRecord(e1, st));
             THIP_TRY(hipEventSynchronize(e1));
             float ms = 0.0f;

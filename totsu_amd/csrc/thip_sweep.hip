@@ -74,10 +74,11 @@ int sweep_class()
 
 // One candidate geometry: W columns per panel (1 or 2: the two families of kernel instances), the smallest group size
 // the family's row capacity allows times gmul.  0 when the kernel can take the matrix that way.
-static int sweep_plan_one(size_t m, size_t n, size_t lda, const void *mat, int W, int gmul, SweepGeom *g, int force_G = 0, int elem = 0)
+static int sweep_plan_one(size_t m, size_t n, const DenseA &A, int W, int gmul, SweepGeom *g, int force_G = 0)
 {
-    const size_t epv = elem ? 8 : 4;                 // rows per 16-byte slot
-    if (m == 0 || n == 0 || m % epv != 0 || lda % epv != 0 || ((uintptr_t)mat & 15u) != 0) return 1;
+    const int elem = A.kind;
+    const size_t epv = A.vec_elems();                // rows per 16-byte slot
+    if (m == 0 || n == 0 || m % epv != 0 || !A.vec_ok()) return 1;
     if (n > ((size_t)1 << 30) || n < (size_t)40 * W) return 1;
     if (ctx().num_cu != 256) return 1;
     const size_t slot_rows = (size_t)SW_CT * epv;
@@ -119,35 +120,35 @@ static int sweep_plan_one(size_t m, size_t n, size_t lda, const void *mat, int W
 // workgroups per column the rows allow (8 at BASELINE configs[2]); THIP_SWEEP_CLASS = 0 / 1 force the others.
 // 16-bit storage: two columns per panel first (a 16-bit column is half the bytes: the interval of a one-column panel is
 // too short for the service wave's chain)
-int sweep_plan(size_t m, size_t n, size_t lda, const void *mat, SweepGeom *g, int elem)
+int sweep_plan(size_t m, size_t n, const DenseA &A, SweepGeom *g)
 {
-    if (elem) {
+    if (A.is16()) {
         // THIP_SWEEP16_GEOM = "W:gmul" pins the 16-bit geometry (experiments; with THIP_SWEEP_CLASS set so that the solver does not
         // time the candidates)
         if (const char *e = getenv("THIP_SWEEP16_GEOM")) {
             int w = 1, gm = 1;
-            if (sscanf(e, "%d:%d", &w, &gm) == 2 && sweep_plan_one(m, n, lda, mat, w, gm, g, 0, elem) == 0) return 0;
+            if (sscanf(e, "%d:%d", &w, &gm) == 2 && sweep_plan_one(m, n, A, w, gm, g) == 0) return 0;
         }
-        if (sweep_plan_one(m, n, lda, mat, 2, 1, g, 0, elem) == 0) return 0;
-        return sweep_plan_one(m, n, lda, mat, 1, 1, g, 0, elem);
+        if (sweep_plan_one(m, n, A, 2, 1, g) == 0) return 0;
+        return sweep_plan_one(m, n, A, 1, 1, g);
     }
     const int cls = sweep_class();
-    if (cls == 0 && sweep_plan_one(m, n, lda, mat, 2, 1, g) == 0) return 0;
-    if (cls == 1 && sweep_plan_one(m, n, lda, mat, 1, 2, g) == 0) return 0;
-    return sweep_plan_one(m, n, lda, mat, 1, 1, g);
+    if (cls == 0 && sweep_plan_one(m, n, A, 2, 1, g) == 0) return 0;
+    if (cls == 1 && sweep_plan_one(m, n, A, 1, 2, g) == 0) return 0;
+    return sweep_plan_one(m, n, A, 1, 1, g);
 }
 
 // the geometries worth timing on a given matrix (thip_solver.hip times them on the actual matrix, like the GEMV plans)
-int sweep_candidates(size_t m, size_t n, size_t lda, const void *mat, SweepGeom *out, int max_out, int elem)
+int sweep_candidates(size_t m, size_t n, const DenseA &A, SweepGeom *out, int max_out)
 {
     static const int cand32[6][2] = { { 1, 1 }, { 1, 2 }, { 1, 4 }, { 2, 1 }, { 2, 2 }, { 1, 8 } };
     // (16-bit: one column per panel first since the interval's sums are DPP adds -- before, two columns were the safer default)
     static const int cand16[6][2] = { { 1, 1 }, { 4, 1 }, { 2, 1 }, { 2, 2 }, { 4, 2 }, { 1, 2 } };
-    const int (*cand)[2] = elem ? cand16 : cand32;
+    const int (*cand)[2] = A.is16() ? cand16 : cand32;
     int k = 0;
     for (int c = 0; c < 6 && k < max_out; ++c) {
         SweepGeom g;
-        if (sweep_plan_one(m, n, lda, mat, cand[c][0], cand[c][1], &g, 0, elem) != 0) continue;
+        if (sweep_plan_one(m, n, A, cand[c][0], cand[c][1], &g) != 0) continue;
         bool dup = false;
         for (int j = 0; j < k; ++j) dup = dup || (out[j].G == g.G && out[j].w == g.w && out[j].nslot == g.nslot);
         if (!dup) out[k++] = g;
@@ -219,9 +220,10 @@ static int run_test_sweep(const thip_sweep_test *t, int spin_max, float *host_ms
     // 16-bit: `variant` = columns per panel (1, 2 or 4; else the planner's preference)
     // (f32: variant 12 = two columns per panel)
     const int w16 = t->elem ? ((t->variant == 1 || t->variant == 2 || t->variant == 4) ? t->variant : 0) : (t->variant == 12 ? 2 : 0);
-    if (w16 ? sweep_plan_one(t->m, t->n, t->lda, t->mat_a, w16, 1, &g, t->force_members, t->elem) != 0
-        : (t->force_members > 0 ? sweep_plan_one(t->m, t->n, t->lda, t->mat_a, t->elem ? 2 : 1, 1, &g, t->force_members, t->elem)
-                                : sweep_plan(t->m, t->n, t->lda, t->mat_a, &g, t->elem)) != 0)
+    const DenseA A{ t->mat_a, t->lda, t->elem, t->inv_s, false };
+    if (w16 ? sweep_plan_one(t->m, t->n, A, w16, 1, &g, t->force_members) != 0
+        : (t->force_members > 0 ? sweep_plan_one(t->m, t->n, A, t->elem ? 2 : 1, 1, &g, t->force_members)
+                                : sweep_plan(t->m, t->n, A, &g)) != 0)
         return fail(THIP_E_INVALID, "the one-pass kernel cannot take this shape", __FILE__, __LINE__);
     hipStream_t st = ctx().stream;
     unsigned long long *gran = nullptr;
@@ -460,7 +462,8 @@ extern "C" int thip_sweep_probe(size_t m, size_t n_local, size_t lda, int elem, 
     SweepGeom g;
     const size_t epv = elem ? 8 : 4;              // rows per 16-byte vector: the library's own copy pads rows and pitch to it
     // (the matrix itself is not needed: any 16-byte aligned address stands for it)
-    if (sweep_plan((m + epv - 1) / epv * epv, n_local, (lda + epv - 1) / epv * epv, reinterpret_cast<const void *>((uintptr_t)4096), &g, elem) != 0) return 0;
+    const DenseA A{ reinterpret_cast<const void *>((uintptr_t)4096), (lda + epv - 1) / epv * epv, elem, nullptr, false };
+    if (sweep_plan((m + epv - 1) / epv * epv, n_local, A, &g) != 0) return 0;
     unsigned *census = nullptr;
     THIP_TRY(hipMalloc((void **)&census, 16 * sizeof(unsigned)));
     hipStream_t st = ctx().stream;
