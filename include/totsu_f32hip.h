@@ -161,6 +161,17 @@ int thip_spmv_csr(size_t n_row, size_t n_col, size_t nnz, const int64_t *dev_row
  * per entry on the device and per product (thip_sptile_layout reports how many).
  * thip_sptile_mv is `Operator::op / trans_op` (operator.rs:40-75) for such an operator: y = alpha A x + beta y,
  * transpose != 0: A^T; abs_mode != 0: |A| and x = 1 (absadd_rows / absadd_cols, operator.rs:82-154).  x, y on the device.
+ * ACCURACY.  Every out element i (a row of A x, a column of A^T x) accumulates in fixed point with a scale OF ITS OWN, taken from
+ * amax_i, the largest stored |a| of that row / column, and from max|x|.  With head_bits = ceil(log2(longest row (A x) or column
+ * (A^T x))) + 1 and G = 50 - 2 head_bits,
+ *         |out_i - (A x)_i|  <=  1e-5 (|A||x|)_i  +  2^-G  amax_i  max|x|        (amax_i no smaller than 2^-127)
+ * -- the first term is the f32 rounding of the products and of the partial sums kept in registers, the second the fixed-point
+ * rounding: at most 2^(head_bits - 1) adds of half a unit 2^-(50 - head_bits) 2^e_i 2^ex, 2^e_i <= 2 amax_i, 2^ex <= 2 max|x|.
+ * A row or column that is small as a whole keeps its bits (its amax_i is small with it); an entry of x far below max|x| -- 2^-(G - 17)
+ * of it and less -- contributes with the absolute resolution that max|x| sets.  abs_mode: x = 1, so the bound is relative to amax_i
+ * alone and a non-empty row or column never sums to 0.  A non-finite entry of x answers NaN in every element of y.
+ * thip_sptile_create returns THIP_E_INVALID for a stored value that is not finite (an integer accumulator cannot carry it) and
+ * for n_col > 0 without column pointers (also when nnz == 0: the n_col + 1 pointers are always read).
  * thip_sptile_mv on one handle must not run from two host threads at once (it uses a workspace the handle owns), while any
  * number of solvers may share one handle (thip_solver_set_sptile: each brings its own workspace). */
 typedef struct thip_sptile thip_sptile;

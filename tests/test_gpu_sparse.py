@@ -148,15 +148,17 @@ def test_fused_loop_sparse_socp_iterates_vs_oracle(T, schedule, two_copies):
     fs.destroy()
 
 
-def _iterates_vs_oracle(T, A, b, c, seg_t, seg_l, iters, tols, schedule="sweep"):
-    """iterates of the fused loop on the tiled sparse copy of A against the f64 oracle on the dense-ified A"""
+def _iterates_vs_oracle(T, A, b, c, seg_t, seg_l, iters, tols, schedule="sweep", sparse_two_copies=False, report=None):
+    """iterates of the fused loop on the tiled sparse copy of A (sparse_two_copies: on the two CSR copies) against the f64 oracle on
+    the dense-ified A; report: a label under which every measured error is printed before it is asserted.  Returns the solver's
+    preconditioner vectors and the oracle's."""
     m, n = A.shape
     Ad = np.asfortranarray(A.toarray().astype(np.float32)).ravel(order="F")
     ro = O.solve_matop_cones(O.param(max_iter=iters[-1] + 2, eps_acc=1e-300), c, Ad, b, seg_t, seg_l, snap_iters=list(iters),
                              trace_cap=64)
     p = T.SolverParam()
     p.eps_acc = 0.0
-    fs = T.FusedSolver(n, m, A, b, c, seg_t, seg_l, p, schedule)
+    fs = T.FusedSolver(n, m, A, b, c, seg_t, seg_l, p, schedule, sparse_two_copies=sparse_two_copies)
     assert fs.schedule_in_use() == schedule
     N = n + 2 * m + 1
     done = 0
@@ -165,9 +167,14 @@ def _iterates_vs_oracle(T, A, b, c, seg_t, seg_l, iters, tols, schedule="sweep")
         done = it + 1
         x, y = fs.iterate()
         rx, ry = ro.snaps[q][:N], ro.snaps[q][N:]
+        if report:
+            print("%s: iterate %d x %.2e y %.2e (tolerance %.1e)" % (report, it, np.abs(x - rx).max() / max(np.abs(rx).max(), 1e-6),
+                                                                     np.abs(y - ry).max() / max(np.abs(ry).max(), 1e-6), tol))
         assert np.abs(x - rx).max() <= tol * max(np.abs(rx).max(), 1e-6), (it, np.abs(x - rx).max(), np.abs(rx).max())
         assert np.abs(y - ry).max() <= tol * max(np.abs(ry).max(), 1e-6), (it, np.abs(y - ry).max(), np.abs(ry).max())
+    pre = fs.precond()
     fs.destroy()
+    return pre, ro.precond
 
 
 @pytest.mark.parametrize("schedule", ["sweep", "carried"])

@@ -82,9 +82,10 @@ struct SptArgs {
     float *part; size_t opad;           // [slice][2][opad]
     int abs_mode; const int *stop;
     int stage_min;                      // entries of a tile visit from which the in-vector's block is staged in LDS
-    // fixed-point accumulation (see sp_tile_k): block maxima of |in0| / |in1| left by sp_absmax_k (nmax each, in1's behind in0's),
-    // the exponent bound of the stored values and the bits of headroom for the longest row (N) / column (T)
-    const float *xmax; int nmax; int a_exp; int head_bits;
+    // fixed-point accumulation (see spt_scale): block maxima of |in0| / |in1| left by sp_absmax_k (nmax each, in1's behind in0's),
+    // the exponent codes of the out elements -- rows (N) / columns (T), one byte each, per block of 4096 in spt_slot order -- and
+    // the bits of headroom for the longest row (N) / column (T)
+    const float *xmax; int nmax; const unsigned char *oexp; int head_bits;
 };
 
 constexpr int SPT_FIX_BITS = 50;        // bits of a fixed-point partial sum below the sign (see spt_add)
@@ -110,35 +111,45 @@ __global__ __launch_bounds__(1024) void sp_absmax_k(const float *__restrict__ x0
 
 // The accumulators are 64-bit FIXED-POINT words and the LDS adds INTEGER adds (round 6, second half).  tools/lds_atomic_probe.hip:
 // ds_add_f32 runs at 0.33 lane-adds per clock per CU on this part, ds_add_u32 at 7.4, ds_add_u64 at 5.4-6.7 (profiles/
-// r06_lds_atomic_rates.txt) -- the float form was what bounded every scattered pattern (0.64 TB/s of entries).  A product p = a x is
-// added as (int64)(p * 2^k): with |a| < 2^(a_exp + 1) (the matrix's, known at build time), |x| <= xmax (sp_absmax_k, one small launch
-// in front of the product) and at most 2^head_bits terms per out element (the longest row / column), k = 50 - head_bits - (bound of
-// the product's exponent) keeps every partial sum below 2^50 (so that a term converts with one f64 fma, spt_add); the resolution is 2^-(48 - head_bits) of the largest possible
-// product -- finer than an f32 accumulator's.  And integer adds are associative: whatever order the waves reach an accumulator
-// in, the sum is the same -- the products are BITWISE REPRODUCIBLE again (the register sums of the dense path and the wave sums
-// of the T product have a fixed order by construction).
-__device__ __forceinline__ double spt_scale(const float *xm, int nmax, int a_exp, int head_bits, float *sh, double *inv)
+// r06_lds_atomic_rates.txt) -- the float form was what bounded every scattered pattern (0.64 TB/s of entries).  And integer adds are
+// associative: whatever order the waves reach an accumulator in, the sum is the same -- the products are BITWISE REPRODUCIBLE (the
+// register sums of the dense path and the wave sums of the T product have a fixed order by construction).
+//
+// The scale is ONE PER OUT ELEMENT.  Out element i (a row of the N product, a column of the T product) has its own exponent e_i, fixed
+// at build time from the largest stored |a| of that row / column: amax_i < 2^e_i (one byte per row and per column: e_i + 127, e_i
+// clamped to >= -126).  With |x| <= xmax < 2^ex (sp_absmax_k, one small launch in front of the product; abs mode: x = 1, ex = 1)
+// and at most 2^(head_bits - 1) terms per out element (the longest row / column), a product p = a x is added to accumulator i as
+// round(p 2^k_i), k_i = 50 - head_bits - ex - e_i: every term and every partial sum stays below 2^50 (so that a term converts
+// with one f64 fma, spt_add).  Each add rounds by at most half a unit, so the fixed-point part of the error of out element i is
+//      <= 2^(head_bits - 2) 2^-k_i  <=  2^-(50 - 2 head_bits) amax_i max|x|           (2^e_i <= 2 amax_i, 2^ex <= 2 max|x|)
+// -- relative to THAT ROW'S (column's) largest possible product, not to the matrix's: a row that is small as a whole keeps its
+// bits (a single scale from the matrix's largest |a| lost them: rows 10^-6 of a matrix with rows 10^6 came out 40 % wrong, 183
+// abs-mode row sums exactly 0 -- NOTEBOOK.md, round 7).  What remains is the window in the IN-VECTOR's range: an entry of x far below max|x|
+// contributes with an absolute resolution set by max|x| (include/totsu_f32hip.h states the bound beside thip_sptile_mv).
+// An f32 accumulator is finer only where (|A||x|)_i < 2^-(26 - 2 head_bits) amax_i max|x|.
+constexpr int SPT_EXP_BIAS = 1023 + 127;    // the f64 exponent field of 2^(k - e) for a code e + 127 is (SPT_EXP_BIAS + k) - code
+// the biased base exponent of a product: out element i adds with the scale whose f64 exponent field is (result) - code_i
+__device__ __forceinline__ int spt_scale(const float *xm, int nmax, int head_bits, float *sh, bool *bad)
 {
     // every workgroup forms the same maximum from the same block maxima
     float m = 0.0f;
     for (int i = threadIdx.x; i < nmax; i += blockDim.x) m = fmaxf(m, xm[i]);
     m = -block_min(-m, sh);
     int ex = 0;
-    if (!(m < __builtin_inff())) { *inv = __builtin_nan(""); return 1.0; }    // an infinite / NaN entry in the in-vector: the product is NaN
-    if (m > 0.0f) (void)frexpf(m, &ex);                                   // m < 2^ex
-    const int k = SPT_FIX_BITS - head_bits - (a_exp + 1 + ex);
-    *inv = ldexp(1.0, -k);
-    return ldexp(1.0, k);
+    *bad = !(m < __builtin_inff());                                       // an infinite / NaN entry in the in-vector: the product is NaN
+    if (!*bad && m > 0.0f) (void)frexpf(m, &ex);                          // m < 2^ex
+    return SPT_EXP_BIAS + SPT_FIX_BITS - head_bits - ex;
 }
 // The conversion is ONE f64 fma: |p S| < 2^51, so p S + 1.5 2^52 lies in [2^52, 2^53) and the low bits of its mantissa are
 // round(p S) in two's complement -- the word to add is the difference of the bit patterns.  (long long)((double)p * S) -- f64 -> i64
 // has no instruction: a dozen f64 operations -- made the scattered patterns VALU-bound: PMC on the random 1 % matrix, VALUBusy 73 %
 // (T product) / 65 % with 33 % LDS bank conflicts (N), profiles/r06_sparse_patterns_pmc_counters.txt; an integer-only form (frexp,
 // 24-bit mantissa, 64-bit shift) measured slower still.  The price: 50 instead of 62 bits below the sign.
-__device__ __forceinline__ void spt_add(unsigned long long *acc, float p, double S)
+// `hi` is the high word of the scale S (a power of two: its low word is 0): (base - code) << 20.
+__device__ __forceinline__ void spt_add(unsigned long long *acc, float p, int hi)
 {
     constexpr double M = 6755399441055744.0;        // 1.5 * 2^52
-    const double d = fma((double)p, S, M);
+    const double d = fma((double)p, __hiloint2double(hi, 0), M);
     atomicAdd(acc, (unsigned long long)(__double_as_longlong(d) - __double_as_longlong(M)));
 }
 
@@ -177,18 +188,27 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
     const SptItem it = a.items[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool two = a.in1 != nullptr;
-    for (int i = tid; i < SPT_TB; i += SPT_THREADS) { lo0[i] = 0ull; lo1[i] = 0ull; }
-    double inv0 = 1.0, inv1 = 1.0;
-    const double S0 = a.abs_mode ? ldexp(1.0, SPT_FIX_BITS - a.head_bits - (a.a_exp + 2)) : spt_scale(a.xmax, a.nmax, a.a_exp, a.head_bits, shm, &inv0);
-    const double S1 = (two && !a.abs_mode) ? spt_scale(a.xmax + SPT_NMAX, a.nmax, a.a_exp, a.head_bits, shm, &inv1) : 1.0;
-    if (a.abs_mode) inv0 = ldexp(1.0, -(SPT_FIX_BITS - a.head_bits - (a.a_exp + 2)));
+    // The code of an out element RIDES IN ITS FIRST ACCUMULATOR, above the sum: the word starts as code << 56, and a sum stays inside
+    // (-2^50, 2^50), so at any moment code = the word's high half rounded to a multiple of 2^24 -- one ds_read_b32 beside the LDS traffic
+    // a lane already has, no table in LDS (96 KB / 64 KB as before) and no dependent global gather (a byte gather from the L1 per add
+    // cost the random 1 % matrix 35 % / 31 % of its T / N rate and the stencil 21 % / 13 %: NOTEBOOK 11.3)
+    {
+        const unsigned char *const oex = a.oexp + (size_t)it.out_block * SPT_TB;    // (whole blocks, in slot order: every slot is readable)
+        for (int i = tid; i < SPT_TB; i += SPT_THREADS) { lo0[i] = (unsigned long long)oex[i] << 56; lo1[i] = 0ull; }
+    }
+    // S0 / S1: the high words of the two products' scales for an out element of code 0; an element's own is S - (code << 20)
+    bool bad0 = false, bad1 = false;
+    const int S0 = (a.abs_mode ? SPT_EXP_BIAS + SPT_FIX_BITS - a.head_bits - 1 : spt_scale(a.xmax, a.nmax, a.head_bits, shm, &bad0)) << 20;
+    const int S1 = ((two && !a.abs_mode) ? spt_scale(a.xmax + SPT_NMAX, a.nmax, a.head_bits, shm, &bad1) : SPT_EXP_BIAS) << 20;
+    const unsigned *const lo0_hi = reinterpret_cast<const unsigned *>(lo0) + 1;
+    auto code = [&](const int slot) { return (int)((lo0_hi[2 * slot] + (1u << 23)) >> 24) << 20; };
     // N product: in a dense column block no LDS add is needed at all: a column of a full tile is 1024 quads -- one step of this
     // loop, or half of one -- so a lane meets the SAME four rows in every step.  The lane keeps the sums of "its" rows in registers for as long
     // as the rows of its next quad are the ones it holds, and pays the LDS adds only when they change (every step, for a
     // scattered pattern: the old cost plus a compare).
-    int hold[2][4] = { { -1, -1, -1, -1 }, { -1, -1, -1, -1 } };
+    int hold[2][4] = { { -1, -1, -1, -1 }, { -1, -1, -1, -1 } }, hcode[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
     float h0[2][4] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } }, h1[2][4] = { { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
-    __syncthreads();                    // the accumulators are zero before any wave adds to them
+    __syncthreads();                    // the accumulators are set before any wave adds to them
     // one quad of the stream (slot u of the lane's two in flight): four entries `av` with their index words `iv`, the in-vector's
     // block from LDS (staged) or straight from L2 (in0b / in1b); `tag` tells the visits of one wave apart (the flat walk of LITE)
     auto process = [&](const int u, const f32x4 av, const i32x4 iv, const bool ok, const bool staged, const float *in0b, const float *in1b,
@@ -213,9 +233,10 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
                     const float s0 = (p0[0] + p0[1]) + (p0[2] + p0[3]), s1 = (p1[0] + p1[1]) + (p1[2] + p1[3]);
                     const int tg = tag << 12;           // (a slot is 12 bits)
                     const int first = __builtin_amdgcn_readfirstlane(oi[0] | tg);
+                    const int c3 = code(oi[3]);         // (asked for here: the in-vector's reads are in flight beside it)
                     if (__all(ok && same && (oi[0] | tg) == first)) {
                         const float w0 = wave_sum_dpp(s0), w1 = two ? wave_sum_dpp(s1) : 0.0f;
-                        if (lane == 0) { spt_add(&lo0[first & 0xfff], w0, S0); if (two) spt_add(&lo1[first & 0xfff], w1, S1); }
+                        if (lane == 0) { spt_add(&lo0[first & 0xfff], w0, S0 - c3); if (two) spt_add(&lo1[first & 0xfff], w1, S1 - c3); }
                     } else {
                         // several columns in the wave: a segmented sum over the lanes (keys ascend with the lane: the stream is
                         // column-sorted), one LDS add per column and wave instead of one per entry.  A lane whose quad straddles
@@ -230,21 +251,22 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     if (oi[e] == oi[3]) { a0 += p0[e]; a1 += p1[e]; }
-                                    else { spt_add(&lo0[oi[e]], p0[e], S0); if (two) spt_add(&lo1[oi[e]], p1[e], S1); }
+                                    else { const int ce = code(oi[e]); spt_add(&lo0[oi[e]], p0[e], S0 - ce); if (two) spt_add(&lo1[oi[e]], p1[e], S1 - ce); }
                                 }
                             }
                         }
                         seg_scan_dpp(key, a0, a1);
                         const int kn = __builtin_amdgcn_update_dpp(-2, key, 0x130, 0xf, 0xf, false);     // the next lane's key (wave shift left)
-                        if (kn != key && key != 0x7fffffff) { spt_add(&lo0[key & 0xfff], a0, S0); if (two) spt_add(&lo1[key & 0xfff], a1, S1); }
+                        if (kn != key && key != 0x7fffffff) { spt_add(&lo0[key & 0xfff], a0, S0 - c3); if (two) spt_add(&lo1[key & 0xfff], a1, S1 - c3); }
                     }
                 } else if (ok) {
                     const bool keep = oi[0] == hold[u][0] && oi[1] == hold[u][1] && oi[2] == hold[u][2] && oi[3] == hold[u][3];
                     if (!keep) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            if (hold[u][e] >= 0) { spt_add(&lo0[hold[u][e]], h0[u][e], S0); if (two) spt_add(&lo1[hold[u][e]], h1[u][e], S1); }
-                            hold[u][e] = oi[e]; h0[u][e] = 0.0f; h1[u][e] = 0.0f;
+                            if (hold[u][e] >= 0) { spt_add(&lo0[hold[u][e]], h0[u][e], S0 - hcode[u][e]); if (two) spt_add(&lo1[hold[u][e]], h1[u][e], S1 - hcode[u][e]); }
+                            // (the code of a row is fetched when the lane takes the row up, and used when it lets go of it)
+                            hold[u][e] = oi[e]; hcode[u][e] = code(oi[e]); h0[u][e] = 0.0f; h1[u][e] = 0.0f;
                         }
                     }
 #pragma unroll
@@ -295,7 +317,7 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
         auto flush = [&]() {
             if (cur < 0) return;
             const float t0 = wave_sum_dpp(s0), t1 = two ? wave_sum_dpp(s1) : 0.0f;
-            if (lane == 0) { spt_add(&lo0[spt_slot(cur)], t0, S0); if (two) spt_add(&lo1[spt_slot(cur)], t1, S1); }
+            if (lane == 0) { const int cc = code(spt_slot(cur)); spt_add(&lo0[spt_slot(cur)], t0, S0 - cc); if (two) spt_add(&lo1[spt_slot(cur)], t1, S1 - cc); }
             s0 = 0.0f; s1 = 0.0f;
         };
         for (long long cb = w0; cb < w1; cb += 4) {
@@ -349,7 +371,7 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
             if (q0 + t < q1) {
                 const int row = (int)(((q0 + t - tq0) & 1023) << 2);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { spt_add(&lo0[spt_slot(row + e)], r0[e], S0); if (two) spt_add(&lo1[spt_slot(row + e)], r1[e], S1); }
+                for (int e = 0; e < 4; ++e) { const int ce = code(spt_slot(row + e)); spt_add(&lo0[spt_slot(row + e)], r0[e], S0 - ce); if (two) spt_add(&lo1[spt_slot(row + e)], r1[e], S1 - ce); }
             }
         }
     };
@@ -451,15 +473,23 @@ __global__ __launch_bounds__(LITE ? SPT_THREADS_LITE : SPT_THREADS) void sp_tile
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (hold[u][e] >= 0) { spt_add(&lo0[hold[u][e]], h0[u][e], S0); if (two) spt_add(&lo1[hold[u][e]], h1[u][e], S1); }
+                if (hold[u][e] >= 0) { spt_add(&lo0[hold[u][e]], h0[u][e], S0 - hcode[u][e]); if (two) spt_add(&lo1[hold[u][e]], h1[u][e], S1 - hcode[u][e]); }
     }
     __syncthreads();
     const size_t r0 = (size_t)it.out_block * SPT_TB;
     float *o0 = a.part + (size_t)it.slice * 2 * a.opad + r0, *o1 = o0 + a.opad;
     for (int i = tid; i < SPT_TB; i += SPT_THREADS)
         if (r0 + i < a.opad) {
-            o0[i] = (float)((double)(long long)lo0[spt_slot(i)] * inv0);
-            if (two) o1[i] = (float)((double)(long long)lo1[spt_slot(i)] * inv1);
+            // the sum without the code above it; 1 / S of this element: the exponent field 2046 - (that of S)
+            const unsigned long long w0 = lo0[spt_slot(i)];
+            const unsigned cb = ((unsigned)(w0 >> 32) + (1u << 23)) >> 24;
+            const int ce = (int)cb << 20;
+            const double inv0 = bad0 ? __builtin_nan("") : __hiloint2double((2046 << 20) - (S0 - ce), 0);
+            o0[i] = (float)((double)(long long)(w0 - ((unsigned long long)cb << 56)) * inv0);
+            if (two) {
+                const double inv1 = bad1 ? __builtin_nan("") : __hiloint2double((2046 << 20) - (S1 - ce), 0);
+                o1[i] = (float)((double)(long long)lo1[spt_slot(i)] * inv1);
+            }
         }
 }
 
@@ -573,8 +603,10 @@ struct thip_sptile {
     size_t mpad = 0, npad = 0;
     f32x4 *vals = nullptr; i32x4 *idx = nullptr; SptTile *tiles = nullptr; int *order = nullptr;
     SptItem *itemsN = nullptr, *itemsT = nullptr;
-    // fixed-point accumulation: |value| < 2^(a_exp + 1); at most 2^headN / 2^headT entries in a row / column
-    int a_exp = 0, headN = 1, headT = 1;
+    // fixed-point accumulation (spt_scale): at most 2^(headN - 1) / 2^(headT - 1) entries in a row / column; the exponent codes of
+    // the rows and of the columns, nrb / ncw whole blocks of 4096 bytes, each block in spt_slot order
+    int headN = 1, headT = 1;
+    unsigned char *rexp = nullptr, *cexp = nullptr;
     // launch state of the HANDLE-LEVEL entry points only (thip_sptile_mv, thip_test_sptile_time: one host thread at a time per
     // handle): the slices' partial sums, made on first use, and the block maxima of the in-vectors (2 x SPT_NMAX floats).  A solver
     // brings its own (spt_buffers), so the products below never write through the matrix and any number of solvers may share it
@@ -608,7 +640,7 @@ int sptile_product(hipStream_t st, const thip_sptile *M, bool tphase, const floa
     a.in0 = in0; a.in1 = in1; a.in_len = (int)(tphase ? M->m : M->n);
     a.part = part; a.opad = tphase ? M->npad : M->mpad;
     a.abs_mode = abs_mode; a.stop = stop ? stop : ctx().never_stop;
-    a.xmax = xmax; a.a_exp = M->a_exp; a.head_bits = tphase ? M->headT : M->headN; a.nmax = 1;
+    a.xmax = xmax; a.oexp = tphase ? M->cexp : M->rexp; a.head_bits = tphase ? M->headT : M->headN; a.nmax = 1;
     if (!abs_mode && xmax_ready) a.nmax = SPT_NMAX;
     else if (!abs_mode) {
         const int len = a.in_len;
@@ -678,15 +710,15 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
     if (m >= ((size_t)1 << 31) || n >= ((size_t)1 << 31) || nrb * ncw > ((size_t)1 << 27))
         return fail(THIP_E_INVALID, "sparse operator too large for the tile directory", __FILE__, __LINE__);
     M->nrb = (int)nrb; M->ncw = (int)ncw;
-    if (nnz && (!colptr || !rowidx || !vals)) return fail(THIP_E_INVALID, "null CSC arrays", __FILE__, __LINE__);
-    if (n && colptr && (colptr[0] != 0 || (size_t)colptr[n] != nnz)) return fail(THIP_E_INVALID, "column pointers do not span nnz", __FILE__, __LINE__);
+    if ((n && !colptr) || (nnz && (!rowidx || !vals))) return fail(THIP_E_INVALID, "null CSC arrays", __FILE__, __LINE__);
+    if (n && (colptr[0] != 0 || (size_t)colptr[n] != nnz)) return fail(THIP_E_INVALID, "column pointers do not span nnz", __FILE__, __LINE__);
     // entries per (row block, column block)
     std::vector<int64_t> cnt(nrb * ncw ? nrb * ncw : 1, 0);
     std::vector<int32_t> rowlen(m ? m : 1, 0);
     std::vector<char> unsorted(ncw ? ncw : 1, 0);   // a column block with a column whose rows do not ascend: no dense tiles there
     static const bool allow_dense = !(getenv("THIP_SPT_DENSE") && atoi(getenv("THIP_SPT_DENSE")) == 0);
     int64_t max_col = 0;
-    float amax = 0.0f;
+    std::vector<float> rowmax(m ? m : 1, 0.0f), colmax(n ? n : 1, 0.0f);        // largest |a| of every row / column
     for (size_t j = 0; j < n; ++j) {
         if (colptr[j + 1] < colptr[j]) return fail(THIP_E_INVALID, "column pointers decrease", __FILE__, __LINE__);
         int64_t *crow = cnt.data() + j / SPT_TB;
@@ -699,15 +731,21 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
             prev = r;
             ++crow[(size_t)(r / SPT_TB) * ncw];
             ++rowlen[r];
+            // (the integer accumulators cannot carry an infinity or a NaN: it would come out as a finite number)
             const float av = std::fabs(vals[k]);
-            if (av > amax && av < std::numeric_limits<float>::infinity()) amax = av;
+            if (!(av < std::numeric_limits<float>::infinity())) return fail(THIP_E_INVALID, "non-finite stored value", __FILE__, __LINE__);
+            rowmax[r] = std::max(rowmax[r], av);
+            colmax[j] = std::max(colmax[j], av);
         }
     }
+    // the fixed-point accumulators' bounds: row / column i holds |value| < 2^e_i (code e_i + 127 in 1 .. 255; an empty one, or one of
+    // subnormals only, gets the smallest), at most 2^(head - 1) terms per out element
+    std::vector<unsigned char> rcode(nrb * SPT_TB ? nrb * SPT_TB : 1, 1), ccode(ncw * SPT_TB ? ncw * SPT_TB : 1, 1);
     {
-        // the fixed-point accumulators' bounds: |value| < 2^(a_exp + 1), at most 2^head terms per out element (+ 1 bit of slack)
-        int ex = 0;
-        if (amax > 0.0f) (void)std::frexp(amax, &ex);           // amax < 2^ex
-        M->a_exp = ex - 1;
+        auto slot = [](size_t i) { return (i / SPT_TB) * SPT_TB + (((i & 3) << 10) | ((i % SPT_TB) >> 2)); };      // (spt_slot)
+        auto code_of = [](float mx) { int ex = -126; if (mx > 0.0f) (void)std::frexp(mx, &ex); return (unsigned char)(std::max(ex, -126) + 127); };
+        for (size_t r = 0; r < m; ++r) rcode[slot(r)] = code_of(rowmax[r]);
+        for (size_t j = 0; j < n; ++j) ccode[slot(j)] = code_of(colmax[j]);
         const int64_t max_row = m ? *std::max_element(rowlen.begin(), rowlen.end()) : 0;
         auto bits = [](int64_t c) { int b = 0; while (((int64_t)1 << b) < c) ++b; return b + 1; };
         M->headN = bits(std::max<int64_t>(max_row, 1)); M->headT = bits(std::max<int64_t>(max_col, 1));
@@ -893,6 +931,8 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
     THIP_RC(upload(order, &M->order));
     THIP_RC(upload(itN, &M->itemsN));
     THIP_RC(upload(itT, &M->itemsT));
+    THIP_RC(upload(rcode, &M->rexp));
+    THIP_RC(upload(ccode, &M->cexp));
     THIP_TRY(hipMalloc((void **)&M->mv.xmax, 2 * SPT_NMAX * sizeof(float)));
     THIP_TRY(hipMemset(M->mv.xmax, 0, 2 * SPT_NMAX * sizeof(float)));
     return 0;
@@ -919,7 +959,7 @@ int thip_sptile_destroy(thip_sptile *M)
 {
     if (!M) return 0;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
-    for (void *p : { (void *)M->vals, (void *)M->idx, (void *)M->tiles, (void *)M->order, (void *)M->itemsN, (void *)M->itemsT,
+    for (void *p : { (void *)M->vals, (void *)M->idx, (void *)M->tiles, (void *)M->order, (void *)M->itemsN, (void *)M->itemsT, (void *)M->rexp, (void *)M->cexp,
                      (void *)M->mv.partN, (void *)M->mv.partT, (void *)M->mv.xmax })
         if (p) (void)hipFree(p);
     delete M;
@@ -937,7 +977,7 @@ int thip_sptile_info(const thip_sptile *M, size_t *host_nnz_stored, int *host_ti
     if (host_slices_n) *host_slices_n = M->slN;
     if (host_slices_t) *host_slices_t = M->slT;
     if (host_bytes) *host_bytes = M->nnz_pad * 4 + M->nidx * 4 + (size_t)M->ntiles * (sizeof(SptTile) + sizeof(int))
-                                  + (size_t)(M->nN + M->nT) * sizeof(SptItem);
+                                  + (size_t)(M->nN + M->nT) * sizeof(SptItem) + ((size_t)M->nrb + (size_t)M->ncw) * SPT_TB;
     return 0;
 }
 

@@ -58,7 +58,8 @@ class SpTile:
     def __init__(self, mat):
         _lib.ensure_init()
         m = mat.tocsc()
-        m.sort_indices()
+        if not m.has_sorted_indices:
+            m = m.sorted_indices()      # (a copy: tocsc() of a CSC matrix is the caller's own object)
         self.shape = m.shape
         self.nnz = int(m.nnz)
         colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
