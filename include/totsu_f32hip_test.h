@@ -37,6 +37,13 @@ int thip_test_spin_allreduce(thip_solver *s, int latency_us);
  * (the default where the m-tail is one of the merged forms: it is launched only when the host is about to look). */
 int thip_test_sweep_fault(thip_solver *s, int kind, int64_t after_sweeps, int spin_max);
 
+/* TEST HOOK (SYNC): the Kahan terms of the current iterate (thip_param.state_arith; zeros under THIP_STATE_PLAIN), n floats for
+ * x_x and u, m floats for x_y, x_s and v, any pointer may be NULL -- so that a test can check a compensated update bit for bit
+ * from the outside -- and the form of the m-tail the last one-pass step launched: 0 none yet, 1 merged (element-wise cones), 2 a
+ * wave per cone, 3 three launches; + 4 where the row kernels ran one thread per row (a tiled sparse A with few slices). */
+int thip_test_solver_kahan(thip_solver *s, float *host_kx, float *host_ky, float *host_ks, float *host_ku, float *host_kv,
+                           int *host_mtail_form);
+
 /* test entry point of the one-pass kernel (thip_sweep.hip): one sweep over the m x n matrix A (device, column-major),
  *   gT = A^T v ; g3 = A^T xy ; u <- u + Su o (-(gP - 2 g3) - c rtau) unless `first` ; gP <- g3 ;
  *   xx_out = xx_in + Tx o (gT + c kappa) ; hN = A u ; h3 = A xx_out            (Kahan terms ku / kx_* may be NULL)

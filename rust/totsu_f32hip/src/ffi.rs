@@ -202,6 +202,8 @@ extern "C" {
     pub fn thip_test_eig_force(engine: c_int) -> c_int;
     pub fn thip_test_spin_allreduce(s: *mut thip_solver, latency_us: c_int) -> c_int;
     pub fn thip_test_sweep(t: *const thip_sweep_test, host_ms: *mut f32, host_info: *mut c_int) -> c_int;
+    pub fn thip_test_solver_kahan(s: *mut thip_solver, host_kx: *mut f32, host_ky: *mut f32, host_ks: *mut f32, host_ku: *mut f32,
+                                  host_kv: *mut f32, host_mtail_form: *mut c_int) -> c_int;
     pub fn thip_test_sweep_fault(s: *mut thip_solver, kind: c_int, after_sweeps: i64, spin_max: c_int) -> c_int;
     pub fn thip_test_gemm_sym(n: c_int, ld: c_int, alpha: f32, a: *const f32, b: *const f32, beta: f32, d: *const f32,
                               gamma: f32, c: *mut f32) -> c_int;

@@ -464,3 +464,12 @@ def test_sweep_kernel_on_a_16_bit_matrix_vs_numpy(T, kind, m, n, members, w):
         for b in list(bufs.values()) + list(outs.values()):
             b.free()
     mat.free()
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+@pytest.mark.parametrize("m,n,members,w", [(248, 120, 0, 1), (4096, 3000, 0, 2), (12_504, 1000, 0, 4), (28_672, 5200, 4, 2)])
+def test_sweep_kernel_compensated_update_on_a_16_bit_matrix_is_fast2sum_bit_for_bit(T, kind, m, n, members, w):
+    """the compensated update of sweep_k<..., ELEM = bf16 / f16> (the solver passes Kahan terms there too): bitwise against numpy's
+    f32 Fast2Sum on data whose products are exact (test_gpu_sweep._exact_sweep_case), one, two and four columns per panel"""
+    from test_gpu_sweep import _exact_sweep_case
+    _exact_sweep_case(T, m, n, 1 if kind == "bf16" else 2, w, members)

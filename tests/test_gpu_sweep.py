@@ -74,10 +74,8 @@ def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0):
     scale = [((c64 + g3) ** 2).sum(), np.abs(c64) @ np.abs(xx64), np.abs(c64) @ np.abs(u_ref), np.abs(c64) @ (np.abs(xx64) + 2 * np.abs(x_ref))]
     for q in range(4):
         assert abs(sums[q] - want[q]) <= 2e-5 * scale[q], (m, n, first, comp, q, sums[q], want[q])
-    if comp:
-        # the Kahan term carries what the f32 sum dropped: (x + inc) - stored = -k (to f32 round-off of k itself)
-        kxo = outs["kx_out"].to_host().astype(np.float64)
-        assert np.abs((got["x"].astype(np.float64) - kxo) - x_ref).max() <= 1e-6 * np.abs(x_ref).max()
+    # (the Kahan terms themselves: test_sweep_kernel_compensated_update_is_fast2sum_bit_for_bit -- here the f32 dots behind x_ref
+    # err by more than a term is large)
     for b in list(bufs.values()) + list(outs.values()):
         b.free()
     return info[1], info[2], info[3]
@@ -104,6 +102,91 @@ def test_sweep_kernel_two_columns_per_panel(T, m, n, members):
 
 def test_sweep_kernel_padded_leading_dimension(T):
     _sweep_case(2000, 5000, 0, 1, seed=5, lda=2048)
+
+
+def _exact_sweep_case(T, m, n, elem=0, variant=0, members=0, seed=0):
+    """sweep_k's update of x_x / u and of their Kahan terms, BIT FOR BIT, on data whose dot products are exact in f32 in any
+    order of summation: A from {-1, -0.5, 0, 0.5, 1} (exact in bf16 and f16; the f16 column scales are powers of two), v, x_y,
+    gP, c integers in [-4, 4] (every partial sum a multiple of 0.5 below 2^19), Su, Tx powers of two, kappa = -3/8,
+    rtau = 13/16.  Then g3, gT and both increments Su o (-(gP - 2 g3) - c rtau), Tx o (gT + c kappa) are exactly representable --
+    an fma the compiler contracts them into rounds nothing -- and what is left to round is the compensated add itself:
+        y = f32(inc - k) ; x_out = f32(x + y) ; k_out = f32(f32(x_out - x) - y)
+    on u, x_x = 1e3 x N(0, 1) with terms k of up to an ulp of their entry.  A term with the other sign, one that is not read, one
+    that is not written, or a sum the compiler re-associated differs in the last bits.  Without the terms: x_out = f32(x + inc).
+    Returns (members per group, groups, slots per thread)."""
+    from totsu_amd import _lib
+    D = T.DeviceBuffer
+    rng = np.random.default_rng(seed + m + 7 * n + 1000 * elem + variant)
+    At = (rng.integers(-2, 3, (n, m), dtype=np.int8) * np.float32(0.5)).astype(np.float32)   # row j = column j of the m x n matrix
+    kind = {0: None, 1: "bf16", 2: "f16"}[elem]
+    mat = D.from_host(At.ravel()) if elem == 0 else T.Bf16Matrix.from_f32(At.ravel(), m, n, kind)
+    ints = lambda k: rng.integers(-4, 5, k).astype(np.float32)
+    pow2 = lambda k: np.ldexp(np.float32(1.0), rng.integers(-10, -5, k)).astype(np.float32)
+    v, xy, gp, c, su, tx = ints(m), ints(m), ints(n), ints(n), pow2(n), pow2(n)
+    u, xx = ((1e3 * rng.standard_normal(n)).astype(np.float32) for _ in range(2))
+    ku, kx = ((np.spacing(np.abs(a)) * rng.uniform(-1, 1, n)).astype(np.float32) for a in (u, xx))
+    kappa, rtau = np.float32(-0.375), np.float32(0.8125)
+    assert 8 * m < 2 ** 24                               # |partial sum| <= 4 m, a multiple of 0.5: exact in f32 in any order
+    gT, g3 = At @ v, At @ xy
+    inc_u, inc_x = su * (-(gp - 2 * g3) - c * rtau), tx * (gT + c * kappa)
+    f8 = lambda a: a.astype(np.float64)
+    for a, a64 in ((inc_u, f8(su) * (-(f8(gp) - 2 * f8(g3)) - f8(c) * 0.8125)), (inc_x, f8(tx) * (f8(gT) + f8(c) * -0.375))):
+        assert a.dtype == np.float32 and np.array_equal(f8(a), a64)                       # the increments are exact in f32
+
+    def fast2sum(x, inc, k):
+        y = inc - k
+        t = x + y
+        return t, (t - x) - y
+    fixed = {k: D.from_host(a) for k, a in dict(v=v, xy=xy, c=c, su=su, tx=tx, xx=xx, kx=kx).items()}
+    geom = None
+    for first, comp in ((0, 1), (0, 0), (1, 1)):
+        io = {k: D.from_host(a) for k, a in dict(u=u, ku=ku, gp=gp).items()}
+        outs = {k: D(sz, zero=True) for k, sz in dict(xx_out=n, kx_out=n, hn=m + 8, h3=m + 8).items()}
+        t = _lib.SweepTest()
+        t.m, t.n, t.lda = m, n, (m if elem == 0 else mat.ld16)
+        t.mat_a, t.v, t.xy, t.c, t.su, t.tx = (mat.ptr, fixed["v"].ptr, fixed["xy"].ptr, fixed["c"].ptr, fixed["su"].ptr, fixed["tx"].ptr)
+        t.u, t.ku = io["u"].ptr, (io["ku"].ptr if comp else None)
+        t.xx_in, t.kx_in = fixed["xx"].ptr, (fixed["kx"].ptr if comp else None)
+        t.xx_out, t.kx_out = outs["xx_out"].ptr, (outs["kx_out"].ptr if comp else None)
+        t.gp, t.hn, t.h3 = io["gp"].ptr, outs["hn"].ptr, outs["h3"].ptr
+        t.kappa, t.rtau, t.first, t.reps = float(kappa), float(rtau), first, 1
+        t.variant, t.force_members, t.elem = variant, members, elem
+        t.inv_s = mat.inv_ptr if elem == 2 else None
+        ms, info = (C.c_float * 2)(), (C.c_int * 8)()
+        _lib.lib.thip_test_sweep(C.byref(t), ms, info)
+        assert info[0] == 0, list(info)
+        geom = (info[1], info[2], info[4])
+        tag = (m, n, elem, variant, members, first, comp, geom)
+        got_u, got_ku, got_x, got_kx = io["u"].to_host(), io["ku"].to_host(), outs["xx_out"].to_host(), outs["kx_out"].to_host()
+        assert np.array_equal(io["gp"].to_host(), g3), tag
+        want_x, want_kx = fast2sum(xx, inc_x, kx) if comp else (xx + inc_x, np.zeros(n, np.float32))
+        assert np.array_equal(got_x, want_x), (tag, "x_x", int((got_x != want_x).sum()))
+        assert np.array_equal(got_kx, want_kx), (tag, "kx", int((got_kx != want_kx).sum()))
+        if first:
+            want_u, want_ku = u, ku                      # from a consistent iterate the sweep leaves u alone
+        else:
+            want_u, want_ku = fast2sum(u, inc_u, ku) if comp else (u + inc_u, ku)
+        assert np.array_equal(got_u, want_u), (tag, "u", int((got_u != want_u).sum()))
+        assert np.array_equal(got_ku, want_ku), (tag, "ku", int((got_ku != want_ku).sum()))
+        if comp and not first:
+            # the data does exercise the terms: the plain sum differs from the compensated one in many entries, and the new terms
+            # are not zero
+            assert (want_x != xx + inc_x).mean() > 0.1 and (want_u != u + inc_u).mean() > 0.1
+            assert (want_kx != 0).mean() > 0.5 and (want_ku != 0).mean() > 0.5
+        for b in list(io.values()) + list(outs.values()):
+            b.free()
+    for b in fixed.values():
+        b.free()
+    mat.free()
+    return geom
+
+
+@pytest.mark.parametrize("variant", [0, 12])
+@pytest.mark.parametrize("m,n", [(240, 120), (4096, 3000), (20_000, 1000), (100_000, 300)])
+def test_sweep_kernel_compensated_update_is_fast2sum_bit_for_bit(T, m, n, variant):
+    """f32 A, one and two columns per panel, 4 .. 32 workgroups per column, one and two slots per thread (_exact_sweep_case)"""
+    G, groups, _ = _exact_sweep_case(T, m, n, 0, variant)
+    assert G * groups == 256
 
 
 def _check_sweep_iterates(T, dense, iters, tols):

@@ -571,6 +571,21 @@ int thip_test_sweep_fault(thip_solver *s, int kind, int64_t after_sweeps, int sp
     return 0;
 }
 
+int thip_test_solver_kahan(thip_solver *s, float *host_kx, float *host_ky, float *host_ks, float *host_ku, float *host_kv, int *host_mtail_form)
+{
+    THIP_NEED_INIT();
+    if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
+    const size_t n = s->n, m = s->m;
+    THIP_RC(poll(s, nullptr));
+    if (host_kx) THIP_RC(thip_d2h(host_kx, s->kx, n));
+    if (host_ky) THIP_RC(thip_d2h(host_ky, s->ky, m));
+    if (host_ks) THIP_RC(thip_d2h(host_ks, s->ks, m));
+    if (host_ku) THIP_RC(thip_d2h(host_ku, s->ku, n));
+    if (host_kv) THIP_RC(thip_d2h(host_kv, s->kv, m));
+    if (host_mtail_form) *host_mtail_form = s->mtail_form;
+    return 0;
+}
+
 int thip_solver_set_sweep_publish(thip_solver *s, int agent_scope)
 {
     if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);

@@ -131,6 +131,8 @@ struct thip_solver {
     bool status_pending = false;  // the last enqueued iteration's termination test has not been evaluated yet (the next m-kernel's head does)
     int step_par = 0;             // parity of the tau / iter copies the next m-kernel reads
     int pm_par = 0;               // which of the two buffers of sums over m (sw_part + (4 + 4 par) EG) holds the latest
+    int mtail_form = 0;           // the m-tail the last one-pass step launched (thip_test_solver_kahan): 0 none yet, 1 merged (sw_xm_k<MERGE>),
+                                  // 2 a wave per cone (sw_cone_k), 3 three launches (sw_xm_k + block cones + sw_vm_k); + 4: one thread per row (FLAT)
     bool no_merge = false;        // thip_test_sweep_fault(kind 3): the two m-kernels of a step as two launches also without block cones
     int pn_par = 0;               // which of the two buffers of sums over n (sw_part + par * 2 EG) the LAST sweep wrote
     int pub_agent = -1;           // thip_solver_set_sweep_publish: 0 plain stores, 1 agent scope, -1 what the process's self-test said

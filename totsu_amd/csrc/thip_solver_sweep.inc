@@ -327,6 +327,7 @@ int one_iteration_sweep(thip_solver *s, bool last)
     // (a sparse operator with at most four slices per row block: the one-thread-per-row form of the two sw_xm_k launches)
     const bool flat_rows = s->op == A_TILED && !cols && s->sgeom.ngroups <= 4;
     const unsigned xm_threads = (flat_rows && s->m > (size_t)EG * 1024) ? 1024u : (unsigned)BLK;
+    s->mtail_form = (merge ? 1 : (cone_merge ? 2 : 3)) + ((flat_rows && !cone_merge) ? 4 : 0);
     if (merge) {
         hipLaunchKernelGGL((flat_rows ? sw_xm_k<true, true> : sw_xm_k<true, false>), dim3(gx), dim3(xm_threads), 0, st, m, cols ? 1 : s->sgeom.ngroups, s->sgeom.mpad,
                            cols ? s->cs_buf : s->sw_partH, s->h3, s->b, s->v, s->Ty, s->Ts, s->cls, s->xy, s->xs, s->rxy, s->rxs,

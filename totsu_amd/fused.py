@@ -323,6 +323,17 @@ class FusedSolver:
         after_sweeps-th regular sweep from now withholds its partial dots; spin_max shortens the polling bound"""
         lib.thip_test_sweep_fault(self.h, int(kind), int(after_sweeps), int(spin_max))
 
+    def kahan_terms(self):
+        """TEST HOOK (thip_test_solver_kahan): the Kahan terms of the current iterate as a dict of host arrays (x_x, x_y, x_s, u, v),
+        and the form of the m-tail the last one-pass step launched (0 none, 1 merged, 2 a wave per cone, 3 three launches; + 4: one
+        thread per row)"""
+        k = {"xx": np.empty(self.n, np.float32), "xy": np.empty(self.m, np.float32), "xs": np.empty(self.m, np.float32),
+             "u": np.empty(self.n, np.float32), "v": np.empty(self.m, np.float32)}
+        form = C.c_int()
+        lib.thip_test_solver_kahan(self.h, k["xx"].ctypes.data, k["xy"].ctypes.data, k["xs"].ctypes.data, k["u"].ctypes.data,
+                                   k["v"].ctypes.data, C.byref(form))
+        return k, form.value
+
     def set_sweep_publish(self, agent_scope):
         lib.thip_solver_set_sweep_publish(self.h, 1 if agent_scope else 0)
 
