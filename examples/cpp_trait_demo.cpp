@@ -58,7 +58,14 @@ int main()
         s.par.eps_acc = 1e-5f;
         const SolverError e = s.solve(op_c, op_a, op_b, cone, work.slice());
         const std::vector<float> w = work.to_host();
-        const bool ok = e == SolverError::Ok && std::fabs(w[0] - 2.f) <= 1e-3f && std::fabs(w[1] - 2.f) <= 1e-3f;
+        // the same operator from the DENSE column-major matrix on the device (what a MatBuild holds), zeros dropped, built on the
+        // device (SparseOp::from_dense over thip_sptile_from_dense): the same stored object, so the same product bit for bit
+        DeviceVec da(std::vector<float>{ 4, -1, -1, -1, 4, -1 }), ya(3), yd(3);
+        const SparseOp op_d = SparseOp::from_dense(3, 2, da.slice().p, 3);
+        op_a.op(1.0f, dc.slice(), 0.0f, ya.slice());
+        op_d.op(1.0f, dc.slice(), 0.0f, yd.slice());
+        const bool same = ya.to_host() == yd.to_host();
+        const bool ok = same && e == SolverError::Ok && std::fabs(w[0] - 2.f) <= 1e-3f && std::fabs(w[1] - 2.f) <= 1e-3f;
         printf("%-10s status %d after %lld iterations: x = [%.5f, %.5f]  %s\n", "sparse-lp", (int)e, (long long)s.iters, w[0], w[1], ok ? "OK" : "MISMATCH");
         bad += ok ? 0 : 1;
     }

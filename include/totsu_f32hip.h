@@ -187,6 +187,38 @@ int thip_sptile_info(const thip_sptile *mat, size_t *host_nnz_stored, int *host_
  * entries that carry an index (8 bytes per entry), and the bytes of entries ONE product streams */
 int thip_sptile_layout(const thip_sptile *mat, int *host_dense_tiles, size_t *host_indexed_entries, size_t *host_bytes_per_product);
 
+/* The SAME object built on the device from DENSE column-major panels -- what every Prob* builder and MatBuild produce: a dense,
+ * mostly-zero array -- in two passes over the panels: count every column once, plan, fill every column once, finish.  The result is
+ * the object thip_sptile_create builds from the CSC form of the same matrix with its zeros dropped: same directory, items, exponent
+ * codes, indices and values, bit for bit, whatever the panel widths, the panel order or ld.
+ *  - dev_panel: columns [c0, c0 + ncols) on the DEVICE, column-major, leading dimension ld >= n_row.  Rows n_row .. ld - 1 of a
+ *    panel are never read as data.  Panels may come in any order and any widths from 1 to n_col (no alignment with 4096), and the
+ *    two passes may split the columns differently; each pass covers every column exactly once.  A panel may live in one staging
+ *    buffer that the caller refills between calls (the calls are ordered on the library's stream).
+ *  - an entry is stored iff (bits & 0x7fffffff) != 0: +0.0 and -0.0 are dropped, subnormals are kept, in every denormal mode.
+ *  - THIP_E_INVALID, with nothing launched: a column counted or filled twice; a panel outside [0, n_col); ld < n_row; plan with
+ *    columns missing; fill before plan; finish with columns unfilled; a null panel with ncols > 0 and n_row > 0.
+ *  - a non-finite value sets a device flag in the count pass and plan returns THIP_E_INVALID (the rule of thip_sptile_create).
+ *  - a panel whose non-zero pattern differs between the passes never makes the fill write outside that column's counted segment:
+ *    every write is bounded by the counted length, a device flag is raised and finish returns THIP_E_INVALID.
+ *  - plan reports what thip_sptile_info / _layout will report of the finished object (any pointer may be NULL), so that a caller
+ *    can decide before pass 2; it allocates the store.
+ *  - finish hands the object over (thip_sptile_destroy frees it); the builder is destroyed separately, at any stage.
+ * DEVICE MEMORY during a build: the final store; the count table, one int32 per (column, block of 4096 rows) = n_col x
+ * ceil(n_row / 4096) words, 1 / 4096 of the dense bytes; a length and a maximum per row and a maximum per column; the tile
+ * directory.  Nothing proportional to n_row x n_col: with the panels streamed through a staging buffer the dense matrix never
+ * exists on the device. */
+typedef struct thip_sptile_builder thip_sptile_builder;
+int thip_sptile_builder_create(size_t n_row, size_t n_col, thip_sptile_builder **out);
+int thip_sptile_builder_count(thip_sptile_builder *b, size_t c0, size_t ncols, const float *dev_panel, size_t ld);
+int thip_sptile_builder_plan(thip_sptile_builder *b, size_t *host_nnz, int *host_dense_tiles, size_t *host_indexed_entries,
+                             size_t *host_bytes_per_product);
+int thip_sptile_builder_fill(thip_sptile_builder *b, size_t c0, size_t ncols, const float *dev_panel, size_t ld);
+int thip_sptile_builder_finish(thip_sptile_builder *b, thip_sptile **out);
+int thip_sptile_builder_destroy(thip_sptile_builder *b);
+/* the whole matrix is on the device: count, plan, fill, finish */
+int thip_sptile_from_dense(size_t n_row, size_t n_col, const float *dev_mat, size_t ld, thip_sptile **out);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants used by the fused path (no host round trip).  They replace host loops
  * in totsu_core that a generic backend cannot intercept ("hard parts").

@@ -98,6 +98,10 @@ struct SparseOp : Operator {
     {
         chk(thip_sptile_create(r, c, vals.size(), colptr.data(), rowidx.data(), vals.data(), &mat));
     }
+    // from a dense column-major matrix on the DEVICE (leading dimension ld >= r), zeros dropped: the same object, built on the device
+    struct FromDense {};
+    SparseOp(FromDense, size_t r, size_t c, const float *dev_mat, size_t ld) : nr(r), nc(c) { chk(thip_sptile_from_dense(r, c, dev_mat, ld, &mat)); }
+    static SparseOp from_dense(size_t r, size_t c, const float *dev_mat, size_t ld) { return SparseOp(FromDense{}, r, c, dev_mat, ld); }
     SparseOp(const SparseOp &) = delete;
     SparseOp &operator=(const SparseOp &) = delete;
     ~SparseOp() override { thip_sptile_destroy(mat); }

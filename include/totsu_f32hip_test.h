@@ -97,6 +97,10 @@ int thip_test_chain_probe(int mode, int ld, int reps, float *host_us);
  * (vectors of ones, two right-hand sides as in the one-pass recurrence); host_ms[0] / [1] = best milliseconds per launch of the
  * T / N product, host_ms[2] / [3] their averages */
 int thip_test_sptile_time(thip_sptile *mat, int reps, float *host_ms);
+/* TEST HOOK (SYNC): downloads two tiled sparse objects and compares every part, in this order: 1 dimensions and nnz; 2 nnz_pad, nidx,
+ * ndense, max_visit; 3 headN and headT; 4 slN, slT and the item counts; 5 tiles; 6 order; 7 itemsN and itemsT; 8 rexp and cexp;
+ * 9 idx; 10 vals, bit for bit.  *host_first_difference = 0 when the objects are equal, else the number of the first differing part. */
+int thip_test_sptile_equal(const thip_sptile *a, const thip_sptile *b, int *host_first_difference);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ pub struct thip_sweep_test {
 
 pub enum thip_solver {}
 pub enum thip_sptile {}
+pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
 
 pub const THIP_CONE_ZERO: i32 = 0;
@@ -136,6 +137,17 @@ extern "C" {
                             host_slices_t: *mut c_int, host_bytes: *mut usize) -> c_int;
     pub fn thip_sptile_layout(mat: *const thip_sptile, host_dense_tiles: *mut c_int, host_indexed_entries: *mut usize,
                               host_bytes_per_product: *mut usize) -> c_int;
+    pub fn thip_sptile_builder_create(n_row: usize, n_col: usize, out: *mut *mut thip_sptile_builder) -> c_int;
+    pub fn thip_sptile_builder_count(b: *mut thip_sptile_builder, c0: usize, ncols: usize, dev_panel: *const f32,
+                                     ld: usize) -> c_int;
+    pub fn thip_sptile_builder_plan(b: *mut thip_sptile_builder, host_nnz: *mut usize, host_dense_tiles: *mut c_int,
+                                    host_indexed_entries: *mut usize, host_bytes_per_product: *mut usize) -> c_int;
+    pub fn thip_sptile_builder_fill(b: *mut thip_sptile_builder, c0: usize, ncols: usize, dev_panel: *const f32,
+                                    ld: usize) -> c_int;
+    pub fn thip_sptile_builder_finish(b: *mut thip_sptile_builder, out: *mut *mut thip_sptile) -> c_int;
+    pub fn thip_sptile_builder_destroy(b: *mut thip_sptile_builder) -> c_int;
+    pub fn thip_sptile_from_dense(n_row: usize, n_col: usize, dev_mat: *const f32, ld: usize,
+                                  out: *mut *mut thip_sptile) -> c_int;
     pub fn thip_to_bf16(n_row: usize, n_col: usize, mat: *const f32, mat16: *mut u16, ld16: usize) -> c_int;
     pub fn thip_transform_ge_bf16(transpose: c_int, n_row: usize, n_col: usize, alpha: f32, mat16: *const u16,
                                   ld16: usize, x: *const f32, beta: f32, y: *mut f32) -> c_int;
@@ -211,6 +223,7 @@ extern "C" {
                                 y: *const f32, beta: f32, d: *const f32, gamma: f32, c: *mut f32) -> c_int;
     pub fn thip_test_chain_probe(mode: c_int, ld: c_int, reps: c_int, host_us: *mut f32) -> c_int;
     pub fn thip_test_sptile_time(mat: *mut thip_sptile, reps: c_int, host_ms: *mut f32) -> c_int;
+    pub fn thip_test_sptile_equal(a: *const thip_sptile, b: *const thip_sptile, host_first_difference: *mut c_int) -> c_int;
     pub fn thip_test_gemm_dual(kernel: c_int, n: c_int, ld: c_int, nb: c_int, a: *const f32, b0: *const f32, b1: *const f32,
                                coef: *const f32, o0: *mut f32, o1: *mut f32) -> c_int;
 }

@@ -96,6 +96,13 @@ PROTOTYPES = {
     "thip_sptile_info": (_i, [_vp, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                               C.POINTER(_sz)]),
     "thip_sptile_layout": (_i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
+    "thip_sptile_builder_create": (_i, [_sz, _sz, C.POINTER(_vp)]),
+    "thip_sptile_builder_count": (_i, [_vp, _sz, _sz, _vp, _sz]),
+    "thip_sptile_builder_plan": (_i, [_vp, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
+    "thip_sptile_builder_fill": (_i, [_vp, _sz, _sz, _vp, _sz]),
+    "thip_sptile_builder_finish": (_i, [_vp, C.POINTER(_vp)]),
+    "thip_sptile_builder_destroy": (_i, [_vp]),
+    "thip_sptile_from_dense": (_i, [_sz, _sz, _vp, _sz, C.POINTER(_vp)]),
     "thip_map_eig_worklen": (_sz, [_sz]),
     "thip_map_eig": (_i, [_sz, _vp, _i, _f, _f, _vp, _sz, _i]),
     "thip_eig_decompose": (_i, [_sz, _vp, _i, _f, _f, _vp, _sz, fp]),
@@ -167,6 +174,7 @@ PROTOTYPES = {
     "thip_test_gemm_chain": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _f, _vp, _f, _vp]),
     "thip_test_chain_probe": (_i, [_i, _i, _i, C.POINTER(_f)]),
     "thip_test_sptile_time": (_i, [_vp, _i, C.POINTER(_f)]),
+    "thip_test_sptile_equal": (_i, [_vp, _vp, C.POINTER(_i)]),
     "thip_test_gemm_dual": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "thip_solver_gemv_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
     "thip_prof_enable": (_i, [_i]),

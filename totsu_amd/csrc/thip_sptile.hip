@@ -702,57 +702,60 @@ int upload(const std::vector<T> &h, T **d)
     return 0;
 }
 
-int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *vals)
+// What a count over the entries leaves for the planners.  Two routes fill it: build() below from the caller's CSC arrays on the host, and
+// the builder of thip_sptile_build.inc from dense column panels on the device.  Everything after the count -- the tile directory, the
+// exponent codes, the items -- is planned by the SAME functions from these figures alone, so the two routes cannot drift.
+struct SptCounts {
+    std::vector<int64_t> cnt;           // entries per (row block, column block)
+    std::vector<char> unsorted;         // a column block with a column whose rows do not ascend: no dense tiles there
+    std::vector<float> rowmax, colmax;  // largest |a| of every row / column
+    int64_t max_row = 0, max_col = 0;   // entries of the longest row / column
+};
+// the planned store, on the host: the tile directory (tile_of: tile of a (row block, column block), -1: empty), the T product's
+// tile order, the exponent codes, the items
+struct SptPlan {
+    std::vector<SptTile> tiles;
+    std::vector<int> tile_of, order;
+    std::vector<unsigned char> rcode, ccode;
+    std::vector<SptItem> itN, itT;
+};
+
+int plan_dims(thip_sptile *M, size_t m, size_t n)
 {
-    M->m = m; M->n = n; M->nnz = nnz;
+    M->m = m; M->n = n;
     M->mpad = (m + 63) / 64 * 64; M->npad = (n + 63) / 64 * 64;
     const size_t nrb = (m + SPT_TB - 1) / SPT_TB, ncw = (n + SPT_TB - 1) / SPT_TB;
     if (m >= ((size_t)1 << 31) || n >= ((size_t)1 << 31) || nrb * ncw > ((size_t)1 << 27))
         return fail(THIP_E_INVALID, "sparse operator too large for the tile directory", __FILE__, __LINE__);
     M->nrb = (int)nrb; M->ncw = (int)ncw;
-    if ((n && !colptr) || (nnz && (!rowidx || !vals))) return fail(THIP_E_INVALID, "null CSC arrays", __FILE__, __LINE__);
-    if (n && (colptr[0] != 0 || (size_t)colptr[n] != nnz)) return fail(THIP_E_INVALID, "column pointers do not span nnz", __FILE__, __LINE__);
-    // entries per (row block, column block)
-    std::vector<int64_t> cnt(nrb * ncw ? nrb * ncw : 1, 0);
-    std::vector<int32_t> rowlen(m ? m : 1, 0);
-    std::vector<char> unsorted(ncw ? ncw : 1, 0);   // a column block with a column whose rows do not ascend: no dense tiles there
+    return 0;
+}
+
+// the tile directory from the counts: dense-tile detection, e0 / i0, padding to quads, head bits, exponent codes, the T order
+int plan_directory(thip_sptile *M, const SptCounts &C, SptPlan &P)
+{
+    const size_t m = M->m, n = M->n, nrb = (size_t)M->nrb, ncw = (size_t)M->ncw;
+    const std::vector<int64_t> &cnt = C.cnt;
+    const std::vector<char> &unsorted = C.unsorted;
     static const bool allow_dense = !(getenv("THIP_SPT_DENSE") && atoi(getenv("THIP_SPT_DENSE")) == 0);
-    int64_t max_col = 0;
-    std::vector<float> rowmax(m ? m : 1, 0.0f), colmax(n ? n : 1, 0.0f);        // largest |a| of every row / column
-    for (size_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) return fail(THIP_E_INVALID, "column pointers decrease", __FILE__, __LINE__);
-        int64_t *crow = cnt.data() + j / SPT_TB;
-        max_col = std::max<int64_t>(max_col, colptr[j + 1] - colptr[j]);
-        int32_t prev = -1;
-        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-            const int32_t r = rowidx[k];
-            if (r < 0 || (size_t)r >= m) return fail(THIP_E_INVALID, "row index out of range", __FILE__, __LINE__);
-            if (r <= prev) unsorted[j / SPT_TB] = 1;
-            prev = r;
-            ++crow[(size_t)(r / SPT_TB) * ncw];
-            ++rowlen[r];
-            // (the integer accumulators cannot carry an infinity or a NaN: it would come out as a finite number)
-            const float av = std::fabs(vals[k]);
-            if (!(av < std::numeric_limits<float>::infinity())) return fail(THIP_E_INVALID, "non-finite stored value", __FILE__, __LINE__);
-            rowmax[r] = std::max(rowmax[r], av);
-            colmax[j] = std::max(colmax[j], av);
-        }
-    }
     // the fixed-point accumulators' bounds: row / column i holds |value| < 2^e_i (code e_i + 127 in 1 .. 255; an empty one, or one of
     // subnormals only, gets the smallest), at most 2^(head - 1) terms per out element
-    std::vector<unsigned char> rcode(nrb * SPT_TB ? nrb * SPT_TB : 1, 1), ccode(ncw * SPT_TB ? ncw * SPT_TB : 1, 1);
+    std::vector<unsigned char> &rcode = P.rcode, &ccode = P.ccode;
+    rcode.assign(nrb * SPT_TB ? nrb * SPT_TB : 1, 1); ccode.assign(ncw * SPT_TB ? ncw * SPT_TB : 1, 1);
     {
         auto slot = [](size_t i) { return (i / SPT_TB) * SPT_TB + (((i & 3) << 10) | ((i % SPT_TB) >> 2)); };      // (spt_slot)
         auto code_of = [](float mx) { int ex = -126; if (mx > 0.0f) (void)std::frexp(mx, &ex); return (unsigned char)(std::max(ex, -126) + 127); };
-        for (size_t r = 0; r < m; ++r) rcode[slot(r)] = code_of(rowmax[r]);
-        for (size_t j = 0; j < n; ++j) ccode[slot(j)] = code_of(colmax[j]);
-        const int64_t max_row = m ? *std::max_element(rowlen.begin(), rowlen.end()) : 0;
+        for (size_t r = 0; r < m; ++r) rcode[slot(r)] = code_of(C.rowmax[r]);
+        for (size_t j = 0; j < n; ++j) ccode[slot(j)] = code_of(C.colmax[j]);
+        const int64_t max_row = C.max_row, max_col = C.max_col;
         auto bits = [](int64_t c) { int b = 0; while (((int64_t)1 << b) < c) ++b; return b + 1; };
         M->headN = bits(std::max<int64_t>(max_row, 1)); M->headT = bits(std::max<int64_t>(max_col, 1));
     }
-    std::vector<SptTile> tiles;
-    std::vector<int64_t> cur(cnt.size(), -1);       // write cursor of a tile; -1: empty
-    std::vector<int> tile_of(cnt.size(), -1);
+    std::vector<SptTile> &tiles = P.tiles;
+    std::vector<int> &tile_of = P.tile_of;
+    tiles.clear();
+    tile_of.assign(cnt.size(), -1);
+    M->ndense = 0; M->max_visit = 0;
     int64_t e = 0, ie = 0;
     for (size_t rb = 0; rb < nrb; ++rb)
         for (size_t cw = 0; cw < ncw; ++cw) {
@@ -766,7 +769,6 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
             if (t.dense) ++M->ndense; else ie += t.cnt;
             if ((c + 3) / 4 * 4 > 0x7fffffff) return fail(THIP_E_INVALID, "a tile holds more than 2^31 entries", __FILE__, __LINE__);
             tile_of[rb * ncw + cw] = (int)tiles.size();
-            cur[rb * ncw + cw] = e;
             tiles.push_back(t);
             e += t.cnt;
         }
@@ -774,31 +776,22 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
     for (const SptTile &t_ : tiles) M->max_visit = std::max<int64_t>(M->max_visit, t_.cnt);
     M->nnz_pad = (size_t)e;
     M->nidx = (size_t)ie;
-    std::vector<float> hv(M->nnz_pad ? M->nnz_pad : 4, 0.0f);
-    std::vector<int32_t> hi(M->nidx ? M->nidx : 4, 0);
-    for (size_t j = 0; j < n; ++j) {
-        const size_t cw = j / SPT_TB;
-        const uint32_t lc = (uint32_t)(j % SPT_TB) << 16;
-        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-            const size_t r = (size_t)rowidx[k];
-            const size_t ti = (r / SPT_TB) * ncw + cw;
-            int64_t &c = cur[ti];
-            const SptTile &t = tiles[tile_of[ti]];
-            hv[c] = vals[k];
-            if (!t.dense) hi[t.i0 + (c - t.e0)] = (int32_t)((uint32_t)(r % SPT_TB) | lc);
-            ++c;
-        }
-    }
-    for (const SptTile &t : tiles) {
-        const int64_t real_end = cur[(size_t)t.rb * ncw + t.cw];
-        for (int64_t k = real_end; k < t.e0 + t.cnt; ++k) { hv[k] = 0.0f; hi[t.i0 + (k - t.e0)] = hi[t.i0 + (real_end - 1 - t.e0)]; }
-    }
     // the tiles of a column block, for the T product
-    std::vector<int> order;
+    std::vector<int> &order = P.order;
+    order.clear();
     order.reserve(tiles.size());
     for (size_t cw = 0; cw < ncw; ++cw)
         for (size_t rb = 0; rb < nrb; ++rb)
             if (tile_of[rb * ncw + cw] >= 0) order.push_back(tile_of[rb * ncw + cw]);
+    return 0;
+}
+
+// the items of the two products from the directory (it depends on the tiles' padded counts alone)
+void plan_items(thip_sptile *M, SptPlan &P)
+{
+    const size_t m = M->m, n = M->n;
+    const std::vector<SptTile> &tiles = P.tiles;
+    const std::vector<int> &order = P.order;
     // items: a block's entries are cut into S equal slices of about `per_item` entries, at least 32 768, at most nnz / (16 dim)
     // (<= 256) slices per block.  One workgroup is resident per CU and the workgroups are handed out in launch order, so a product
     // takes as long as the busiest CU: per_item is the candidate whose items, list-scheduled on 256 CUs at (entries + a fill and a
@@ -849,7 +842,8 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
         p0 = p1;
     }
     const int64_t per_itemN = pick_per_item(lensN, capN), per_itemT = pick_per_item(lensT, capT);
-    std::vector<SptItem> itN, itT;
+    std::vector<SptItem> &itN = P.itN, &itT = P.itT;
+    itN.clear(); itT.clear();
     M->slN = 1; M->slT = 1;
     {
         size_t t0 = 0;
@@ -923,19 +917,86 @@ int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr,
         }
     }
     M->nN = (int)itN.size(); M->nT = (int)itT.size();
+}
+
+// the planned directory, items and codes to the device (the entries themselves are the route's own business)
+int upload_plan(thip_sptile *M, const SptPlan &P)
+{
+    THIP_RC(upload(P.tiles, &M->tiles));
+    THIP_RC(upload(P.order, &M->order));
+    THIP_RC(upload(P.itN, &M->itemsN));
+    THIP_RC(upload(P.itT, &M->itemsT));
+    THIP_RC(upload(P.rcode, &M->rexp));
+    THIP_RC(upload(P.ccode, &M->cexp));
+    THIP_TRY(hipMalloc((void **)&M->mv.xmax, 2 * SPT_NMAX * sizeof(float)));
+    THIP_TRY(hipMemset(M->mv.xmax, 0, 2 * SPT_NMAX * sizeof(float)));
+    return 0;
+}
+
+// the host route: count, plan the directory, fill, plan the items -- from the caller's CSC arrays
+int build(thip_sptile *M, size_t m, size_t n, size_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *vals)
+{
+    THIP_RC(plan_dims(M, m, n));
+    M->nnz = nnz;
+    const size_t nrb = (size_t)M->nrb, ncw = (size_t)M->ncw;
+    if ((n && !colptr) || (nnz && (!rowidx || !vals))) return fail(THIP_E_INVALID, "null CSC arrays", __FILE__, __LINE__);
+    if (n && (colptr[0] != 0 || (size_t)colptr[n] != nnz)) return fail(THIP_E_INVALID, "column pointers do not span nnz", __FILE__, __LINE__);
+    SptCounts C;
+    C.cnt.assign(nrb * ncw ? nrb * ncw : 1, 0);
+    C.unsorted.assign(ncw ? ncw : 1, 0);
+    C.rowmax.assign(m ? m : 1, 0.0f); C.colmax.assign(n ? n : 1, 0.0f);
+    std::vector<int32_t> rowlen(m ? m : 1, 0);
+    for (size_t j = 0; j < n; ++j) {
+        if (colptr[j + 1] < colptr[j]) return fail(THIP_E_INVALID, "column pointers decrease", __FILE__, __LINE__);
+        int64_t *crow = C.cnt.data() + j / SPT_TB;
+        C.max_col = std::max<int64_t>(C.max_col, colptr[j + 1] - colptr[j]);
+        int32_t prev = -1;
+        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
+            const int32_t r = rowidx[k];
+            if (r < 0 || (size_t)r >= m) return fail(THIP_E_INVALID, "row index out of range", __FILE__, __LINE__);
+            if (r <= prev) C.unsorted[j / SPT_TB] = 1;
+            prev = r;
+            ++crow[(size_t)(r / SPT_TB) * ncw];
+            ++rowlen[r];
+            // (the integer accumulators cannot carry an infinity or a NaN: it would come out as a finite number)
+            const float av = std::fabs(vals[k]);
+            if (!(av < std::numeric_limits<float>::infinity())) return fail(THIP_E_INVALID, "non-finite stored value", __FILE__, __LINE__);
+            C.rowmax[r] = std::max(C.rowmax[r], av);
+            C.colmax[j] = std::max(C.colmax[j], av);
+        }
+    }
+    C.max_row = m ? *std::max_element(rowlen.begin(), rowlen.end()) : 0;
+    SptPlan P;
+    THIP_RC(plan_directory(M, C, P));
+    const std::vector<SptTile> &tiles = P.tiles;
+    const std::vector<int> &tile_of = P.tile_of;
+    std::vector<int64_t> cur(C.cnt.size(), -1);     // write cursor of a tile; -1: empty
+    for (const SptTile &t : tiles) cur[(size_t)t.rb * ncw + t.cw] = t.e0;
+    std::vector<float> hv(M->nnz_pad ? M->nnz_pad : 4, 0.0f);
+    std::vector<int32_t> hi(M->nidx ? M->nidx : 4, 0);
+    for (size_t j = 0; j < n; ++j) {
+        const size_t cw = j / SPT_TB;
+        const uint32_t lc = (uint32_t)(j % SPT_TB) << 16;
+        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
+            const size_t r = (size_t)rowidx[k];
+            const size_t ti = (r / SPT_TB) * ncw + cw;
+            int64_t &c = cur[ti];
+            const SptTile &t = tiles[tile_of[ti]];
+            hv[c] = vals[k];
+            if (!t.dense) hi[t.i0 + (c - t.e0)] = (int32_t)((uint32_t)(r % SPT_TB) | lc);
+            ++c;
+        }
+    }
+    for (const SptTile &t : tiles) {
+        const int64_t real_end = cur[(size_t)t.rb * ncw + t.cw];
+        for (int64_t k = real_end; k < t.e0 + t.cnt; ++k) { hv[k] = 0.0f; hi[t.i0 + (k - t.e0)] = hi[t.i0 + (real_end - 1 - t.e0)]; }
+    }
+    plan_items(M, P);
     THIP_TRY(hipMalloc((void **)&M->vals, hv.size() * sizeof(float)));
     THIP_TRY(hipMalloc((void **)&M->idx, hi.size() * sizeof(int32_t)));
     THIP_TRY(hipMemcpy(M->vals, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice));
     THIP_TRY(hipMemcpy(M->idx, hi.data(), hi.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    THIP_RC(upload(tiles, &M->tiles));
-    THIP_RC(upload(order, &M->order));
-    THIP_RC(upload(itN, &M->itemsN));
-    THIP_RC(upload(itT, &M->itemsT));
-    THIP_RC(upload(rcode, &M->rexp));
-    THIP_RC(upload(ccode, &M->cexp));
-    THIP_TRY(hipMalloc((void **)&M->mv.xmax, 2 * SPT_NMAX * sizeof(float)));
-    THIP_TRY(hipMemset(M->mv.xmax, 0, 2 * SPT_NMAX * sizeof(float)));
-    return 0;
+    return upload_plan(M, P);
 }
 
 }  // namespace
@@ -1046,3 +1107,5 @@ int thip_test_sptile_time(thip_sptile *M, int reps, float *host_ms)
 }
 
 }  // extern "C"
+
+#include "thip_sptile_build.inc"

@@ -121,22 +121,46 @@ class FusedResult:
 class FusedSolver:
     def __init__(self, n, m, mat_a, vec_b, vec_c, seg_type, seg_len, param=None, schedule="fused",
                  vec_b_rowabs=None, allreduce=None, a_storage="f32", overlap=None, gemv_autotune=None, lda_pad=None,
-                 sweep_min_bytes=None, col_shard=False, sparse_two_copies=False):
+                 sweep_min_bytes=None, col_shard=False, sparse_two_copies=False, a_layout="dense"):
         """mat_a / vec_b / vec_c / vec_b_rowabs: DeviceBuffer or host arrays (uploaded).
         a_storage: "f32" (the matrix as given), "bf16" or "f16" (a rounded 16-bit copy streamed at half the bytes; f16
         is column-scaled and rounds 8x finer; see set_a_storage / include/totsu_f32hip.h).
         allreduce: None (single GPU), "rccl" (native communicator set up with comm_init), or a Python callable
-        (ctx, dev_ptr, count, stream) -> 0."""
+        (ctx, dev_ptr, count, stream) -> 0.
+        a_layout: how a DENSE mat_a (host array or DeviceBuffer, column-major) is held.  "dense" (default): as given.  "tiled":
+        its tiled sparse copy with the zeros dropped, built on the device (SpTile.from_dense; from a host array no dense device
+        copy is made), owned by the solver.  "auto": the count pass and the plan, then sparse.choose_layout decides."""
+        from .sparse import SpTile, choose_layout
+        assert a_layout in ("dense", "tiled", "auto"), a_layout
+        if a_layout != "dense":
+            # (what the sparse path refuses as well; checked before any library call)
+            assert a_storage == "f32" and not isinstance(mat_a, Bf16Matrix), "a_layout: 16-bit storage holds A dense"
+            assert not col_shard, "a_layout: column shards hold A dense"
+            assert not isinstance(mat_a, SpTile) and not hasattr(mat_a, "tocsr"), "a_layout: mat_a is sparse already"
         _lib.ensure_init()
         self.n, self.m = int(n), int(m)
         self._owned = []
         self._csr = None
         self._spt = None
         self._spt_owned = False
-        from .sparse import SpTile
-        if isinstance(mat_a, SpTile):                     # a tiled sparse operator built by the caller (kept by the caller)
+        self.a_layout = "dense"
+        if a_layout != "dense":
+            b = SpTile.Builder(self.m, self.n)
+            run, release = SpTile._dense_feed(mat_a, self.m, self.n)
+            try:
+                run(b.count)
+                plan = b.plan()
+                if a_layout == "tiled" or choose_layout(self.m, self.n, plan["bytes_per_product"]) == "tiled":
+                    run(b.fill)
+                    mat_a = b.finish()
+            finally:
+                b.destroy()
+                release()
+        if isinstance(mat_a, SpTile):                     # a tiled sparse operator: the caller's (kept by the caller), or a_layout's
             assert mat_a.shape == (self.m, self.n)
             self._spt = mat_a
+            self._spt_owned = a_layout != "dense"
+            self.a_layout = "tiled"
             mat_a = DeviceBuffer(1)
             self._owned.append(mat_a)
         elif hasattr(mat_a, "tocsr"):
@@ -149,6 +173,7 @@ class FusedSolver:
             else:
                 self._spt = SpTile(mat_a)
                 self._spt_owned = True
+                self.a_layout = "tiled"
             mat_a = DeviceBuffer(1)
             self._owned.append(mat_a)
         self._a16 = mat_a if isinstance(mat_a, Bf16Matrix) else None
@@ -242,6 +267,10 @@ class FusedSolver:
             lib.thip_solver_set_param(self.h, C.byref(par))
         lib.thip_solver_resume(self.h)
 
+    def sptile_info(self):
+        """SpTile.info() of the tiled sparse copy in use, or None (A held dense, or as two CSR copies)"""
+        return None if self._spt is None else self._spt.info()
+
     def set_a_storage(self, kind):
         """Switch the stored form of the dense A ("f32" | "bf16" | "f16"); allowed between run() calls."""
         lib.thip_solver_set_a_storage(self.h, A_STORAGE[kind])
@@ -249,6 +278,7 @@ class FusedSolver:
 
     @staticmethod
     def from_dense(d, param=None, schedule="fused", a_storage="f32", **kw):
+        """the stacked description of Prob*.dense(); a_layout="tiled" / "auto" holds its mostly-zero mat_a as a tiled sparse copy"""
         return FusedSolver(d.n, d.m, d.mat_a, d.vec_b, d.vec_c, d.seg_type, d.seg_len, param, schedule,
                            d.vec_b_rowabs, a_storage=a_storage, **kw)
 

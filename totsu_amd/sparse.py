@@ -53,7 +53,8 @@ class _Csr:
 
 class SpTile:
     """A sparse matrix held ONCE on the device in 4096 x 4096 tiles (thip_sptile_*, totsu_amd/csrc/thip_sptile.hip): both
-    products stream the same stored entries.  Built from a scipy.sparse matrix through its CSC arrays on the host."""
+    products stream the same stored entries.  Built from a scipy.sparse matrix through its CSC arrays on the host, or -- `from_dense`,
+    `Builder` -- on the device from a dense column-major array, which is what every Prob* builder and MatBuild produce."""
 
     def __init__(self, mat):
         _lib.ensure_init()
@@ -84,6 +85,116 @@ class SpTile:
                                vals.ctypes.data, C.byref(h))
         self.h = h
         return self
+
+    class Builder:
+        """thip_sptile_builder_*: the tiled copy from dense column-major panels ON THE DEVICE, in two passes -- count every column
+        once, plan(), fill every column once, finish() -- for callers that produce panels themselves.  A panel is a DeviceBuffer (or
+        a device address) holding columns [c0, c0 + ncols) with leading dimension ld >= n_row; panels may come in any order and width,
+        and may all live in one staging buffer refilled between the calls."""
+
+        def __init__(self, n_row, n_col):
+            _lib.ensure_init()
+            self.shape = (int(n_row), int(n_col))
+            self.planned = None
+            h = C.c_void_p()
+            lib.thip_sptile_builder_create(self.shape[0], self.shape[1], C.byref(h))
+            self.h = h
+
+        def _panel(self, panel, ncols, ld):
+            ld = self.shape[0] if ld is None else int(ld)
+            ptr = getattr(panel, "ptr", panel)
+            if hasattr(panel, "n") and ncols > 0 and ld >= self.shape[0]:
+                assert panel.n >= (ncols - 1) * ld + self.shape[0], "panel buffer shorter than its columns"
+            return ptr, ld
+
+        def count(self, c0, ncols, panel, ld=None):
+            ptr, ld = self._panel(panel, int(ncols), ld)
+            lib.thip_sptile_builder_count(self.h, int(c0), int(ncols), ptr, ld)
+
+        def plan(self):
+            """after every column was counted: allocates the store and reports what the finished object's info() will -- nnz, tiles
+            held without indices, entries that carry an index, bytes one product streams"""
+            nz, nd, ni, bp = C.c_size_t(), C.c_int(), C.c_size_t(), C.c_size_t()
+            lib.thip_sptile_builder_plan(self.h, C.byref(nz), C.byref(nd), C.byref(ni), C.byref(bp))
+            self.planned = {"nnz": nz.value, "dense_tiles": nd.value, "indexed_entries": ni.value, "bytes_per_product": bp.value}
+            return dict(self.planned)
+
+        def fill(self, c0, ncols, panel, ld=None):
+            ptr, ld = self._panel(panel, int(ncols), ld)
+            lib.thip_sptile_builder_fill(self.h, int(c0), int(ncols), ptr, ld)
+
+        def finish(self):
+            """the finished SpTile (the caller frees it); the builder is destroyed"""
+            h = C.c_void_p()
+            lib.thip_sptile_builder_finish(self.h, C.byref(h))
+            out = SpTile.__new__(SpTile)
+            out.shape, out.nnz, out.h = self.shape, int(self.planned["nnz"]), h
+            self.destroy()
+            return out
+
+        def destroy(self):
+            if getattr(self, "h", None) is not None:
+                lib.thip_sptile_builder_destroy(self.h)
+                self.h = None
+
+        def __del__(self):
+            try:
+                self.destroy()
+            except Exception:
+                pass
+
+    @staticmethod
+    def _dense_feed(a, n_row, n_col, ld=None, panel_cols=None):
+        """-> (pass, release): pass(f) calls f(c0, ncols, panel, ld) once per panel of the dense column-major matrix `a`.  A
+        DeviceBuffer holding the whole matrix is one panel.  A host array -- flat column-major with leading dimension ld, or 2-D
+        (n_row, n_col), read column by column: no F-ordered copy of the whole is made -- is streamed through ONE staging DeviceBuffer
+        of panel_cols columns (default: about 256 MB of them) with thip_h2d, so the dense matrix never exists on the device."""
+        from .fused import DeviceBuffer
+        n_row, n_col = int(n_row), int(n_col)
+        if isinstance(a, DeviceBuffer):
+            ld_ = n_row if ld is None else int(ld)
+            return (lambda f: f(0, n_col, a, ld_)), (lambda: None)
+        a = np.asarray(a)
+        two_d = a.ndim == 2
+        if two_d:
+            assert a.shape == (n_row, n_col) and ld is None
+            ld_ = n_row
+        else:
+            ld_ = n_row if ld is None else int(ld)
+            assert ld_ >= n_row and (n_col == 0 or a.size >= (n_col - 1) * ld_ + n_row)
+        pc = max(1, (256 << 20) // (4 * max(ld_, 1))) if panel_cols is None else max(1, int(panel_cols))
+        pc = max(1, min(pc, n_col))
+        stage = DeviceBuffer(max(pc * ld_, 1))
+
+        def run(f):
+            for c0 in range(0, n_col, pc):
+                nc = min(pc, n_col - c0)
+                if two_d:
+                    host = np.ascontiguousarray(a[:, c0:c0 + nc].T, dtype=np.float32)      # nc columns, each contiguous
+                else:
+                    host = np.ascontiguousarray(a[c0 * ld_:min(a.size, (c0 + nc) * ld_)], dtype=np.float32)
+                if host.size:
+                    lib.thip_h2d(stage.ptr, host.ctypes.data, host.size)
+                f(c0, nc, stage, ld_)
+        return run, stage.free
+
+    @staticmethod
+    def from_dense(a, n_row, n_col, ld=None, panel_cols=None):
+        """The tiled copy of a DENSE column-major n_row x n_col matrix, zeros dropped (an entry is stored iff its bit pattern
+        without the sign is non-zero): the object SpTile(scipy.sparse.csc_matrix(a)) builds, made on the device in two passes over
+        the matrix.  `a`: a DeviceBuffer holding the whole matrix (leading dimension ld, default n_row) -- the count / plan / fill /
+        finish sequence of thip_sptile_from_dense, through the builder so that nnz is known --, or a host array (flat column-major
+        or 2-D), streamed twice through one staging buffer of panel_cols columns (see _dense_feed)."""
+        b = SpTile.Builder(n_row, n_col)
+        run, release = SpTile._dense_feed(a, n_row, n_col, ld, panel_cols)
+        try:
+            run(b.count)
+            b.plan()
+            run(b.fill)
+            return b.finish()
+        finally:
+            b.destroy()
+            release()
 
     def mv(self, transpose, alpha, x, beta, y, abs_mode=0):
         xp = y.dev() if abs_mode else x.dev()          # abs mode ignores x (taken as all-ones)
@@ -149,3 +260,17 @@ class SparseMatOp:
         for d in (self.t, self.a, self.at):
             if d is not None:
                 d.free()
+
+
+# the read rates the README records for the two schedules, as fractions of the HBM peak: the dense one-pass sweep, and the tiled
+# products on the worst scattered pattern
+DENSE_RATE, TILED_WORST_RATE = 0.90, 0.53
+
+
+def choose_layout(n_row, n_col, bytes_per_product):
+    """"tiled" or "dense" for a matrix whose tiled copy streams `bytes_per_product` bytes per product (SpTile.info(), Builder.plan()).
+    Per iteration the dense one-pass schedule reads 4 n_row n_col bytes once, the tiled schedule reads bytes_per_product twice, and
+    the tiled products run at best 1.7 times slower per byte on a scattered pattern (0.90 / 0.53 of peak, the README's recorded
+    rates).  The rule: tiled iff 2 * 1.7 * bytes_per_product < 4 * n_row * n_col.  That 1.7 is a MODEL built from two recorded rates,
+    not a measured crossover.  Pure host code."""
+    return "tiled" if 2 * 1.7 * int(bytes_per_product) < 4 * int(n_row) * int(n_col) else "dense"
