@@ -456,6 +456,62 @@ int thip_solver_set_column_shard(thip_solver *s, int on);
  * THIP_E_TIMEOUT at the same batch. */
 int thip_sweep_probe(size_t m, size_t n_local, size_t lda, int elem, int *host_ok);
 
+/* ---------------------------------------------------------------------------------------------
+ * A batch of problems that share A: B instances with their own b_i, c_i over ONE dense f32 matrix and one cone layout (a
+ * regularisation path, a parameter sweep, a set of scenarios: what the reference serves by handing op_c / op_a / op_b to every
+ * Solver::solve call, solver.rs:285-321), iterated in lockstep under the 2-pass carried schedule.  One multi-vector launch
+ * (thip_gemv_multi.hip) forms the products of up to eight instances from ONE read of A, so an iteration of the batch costs
+ * 2 * ceil(B / 8) passes over A instead of 2 B.  Everything after the products is the ordinary solver's own kernels on the
+ * instance's own state: the instances do not interact, each one stops by its own termination test and is then frozen (iterate
+ * and iteration count) while the others go on; a group whose members have all stopped is no longer launched.
+ * Limits: dense f32 A on one GPU (no sparse, 16-bit or sharded A, no one-pass schedule), 1 .. THIP_BATCH_MAX instances.
+ * A is held once: the caller's array and, when m is no multiple of 16 floats, one library-owned padded copy for all instances.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_batch thip_batch;
+#define THIP_BATCH_MAX 64
+#define THIP_BATCH_GROUP_DEFAULT 8    /* instances per multi-vector launch (thip_batch_set_max_group) */
+typedef struct thip_batch_info_t {
+    int32_t n_inst, max_group;        /* instances; instances per launch */
+    int32_t groups;                   /* launches per pass: ceil(n_inst / max_group) */
+    int32_t passes_per_iteration;     /* 2 * groups */
+    int32_t a_copies;                 /* library-owned copies of A held by the batch: 0, or 1 (the padded copy) */
+    int32_t reserved;
+    size_t  a_bytes;                  /* bytes of that copy */
+    size_t  bytes_per_pass;           /* 4 m n */
+    size_t  arena_bytes;              /* the instances' state vectors, summed */
+    size_t  device_bytes;             /* everything the batch holds on the device (copy of A, arenas, GEMV scratch, tables) */
+    int32_t plan_nj[4], plan_blocks[4];   /* tuned tiling of the multi-vector kernel by instance, [1] NV = 2, [2] NV = 4, [3] NV = 8 */
+    float   plan_ms[4];               /* (0 = the shape heuristic) and its measured ms per launch + second stage */
+} thip_batch_info_t;
+/* prob_template: n, m, mat_a, the cone segments and (optionally) vec_b_rowabs shared by all instances; its vec_b / vec_c are not
+ * read.  host_vec_b / host_vec_c: HOST arrays of n_inst DEVICE pointers (m / n floats each), caller-owned like mat_a.
+ * THIP_E_INVALID: n_inst < 1 or > THIP_BATCH_MAX, a null array or entry, no dense mat_a (a sparse operator cannot be batched),
+ * a mat_a that is not 16-byte aligned, bad cone segments. */
+int thip_batch_create(const thip_problem *prob_template, int n_inst, const float *const *host_vec_b,
+                      const float *const *host_vec_c, const thip_param *par, thip_batch **out);
+/* the stored form of A: THIP_A_F32 is the only one a batch takes (THIP_E_INVALID for the 16-bit kinds) */
+int thip_batch_set_a_storage(thip_batch *b, int a_kind);
+/* the autotune of the GEMV tilings (the multi-vector kernel's per group size in use, on the actual matrix; a group of one uses
+ * the instance's own single-vector plan): on = 0 pins the shape heuristic -- bit-reproducible.  Before thip_batch_init. */
+int thip_batch_set_gemv_autotune(thip_batch *b, int on);
+/* instances per multi-vector launch: 2, 4 or 8 (default THIP_BATCH_GROUP_DEFAULT).  Before thip_batch_init. */
+int thip_batch_set_max_group(thip_batch *b, int max_group);
+int thip_batch_set_param(thip_batch *b, const thip_param *par);      /* thip_solver_set_param on every instance */
+/* every instance's norms, init_vecs and preconditioner (the |A| row and column sums once for all), the carried products primed */
+int thip_batch_init(thip_batch *b);
+/* every RUNNING instance advances by up to max_steps iterations (< 0: until all have stopped), poll_every iterations enqueued
+ * back to back between looks at the status records; host_status: n_inst records or NULL.  SYNC. */
+int thip_batch_run(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_batch_status(thip_batch *b, int i, thip_status *host_status);                       /* SYNC; thip_solver_status of instance i */
+int thip_batch_solution(thip_batch *b, int i, float *host_x, float *host_y);                 /* thip_solver_solution of instance i */
+int thip_batch_iterate(thip_batch *b, int i, float *host_x, float *host_y);                  /* thip_solver_iterate of instance i */
+int thip_batch_precond(thip_batch *b, int i, float *host_dp_tau, float *host_dp_sigma);      /* thip_solver_precond of instance i */
+int thip_batch_info(const thip_batch *b, thip_batch_info_t *host_info);
+/* how n_inst instances are grouped into launches of at most max_group: *host_groups, and the members of each (host_members:
+ * up to THIP_BATCH_MAX ints or NULL).  Needs no device. */
+int thip_batch_grouping(int n_inst, int max_group, int *host_groups, int *host_members);
+int thip_batch_destroy(thip_batch *b);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

@@ -102,6 +102,16 @@ int thip_test_sptile_time(thip_sptile *mat, int reps, float *host_ms);
  * 9 idx; 10 vals, bit for bit.  *host_first_difference = 0 when the objects are equal, else the number of the first differing part. */
 int thip_test_sptile_equal(const thip_sptile *a, const thip_sptile *b, int *host_first_difference);
 
+/* test entry point of the multi-vector dual GEMV (thip_gemv_multi.hip; tests/test_gpu_batch.py, tools/batch_rate.py): ONE launch of
+ * the m x n matrix `mat` (device, column-major, lda = m; streamed from a zero-padded copy when m % 16 != 0, as the batch object does)
+ * against nv = 2 .. 8 pairs, its partial sums finished into out_n[i] = A xn[i] (m) and out_t[i] = A^T xt[i] (n).  The four host arrays
+ * hold nv DEVICE pointers.  host_stopped[i] != 0 (may be NULL): slot i's stop flag is set -- its outputs are left as they are.
+ * nj / target_blocks > 0 pin the tiling (0: the shape heuristic).  nv = 1 runs the single-vector dual_gemv_k the same way (the
+ * yardstick).  The launch is repeated `reps` times; *host_ms = the best time of one launch (HIP events). */
+int thip_test_gemv_multi(size_t m, size_t n, const float *mat, int nv, const float *const *host_xn, const float *const *host_xt,
+                         float *const *host_out_n, float *const *host_out_t, const int *host_stopped, int nj, int target_blocks,
+                         int reps, float *host_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,16 @@ pub struct thip_status {
 }
 
 #[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_batch_info_t {
+    pub n_inst: i32, pub max_group: i32, pub groups: i32, pub passes_per_iteration: i32, pub a_copies: i32, pub reserved: i32,
+    pub a_bytes: usize, pub bytes_per_pass: usize, pub arena_bytes: usize, pub device_bytes: usize,
+    pub plan_nj: [i32; 4], pub plan_blocks: [i32; 4], pub plan_ms: [f32; 4],
+}
+pub const THIP_BATCH_MAX: c_int = 64;
+pub const THIP_BATCH_GROUP_DEFAULT: c_int = 8;
+
+#[repr(C)]
 pub struct thip_sweep_test {
     pub m: usize, pub n: usize, pub lda: usize,
     pub mat_a: *const f32, pub v: *const f32, pub xy: *const f32, pub c: *const f32, pub su: *const f32, pub tx: *const f32,
@@ -36,6 +46,7 @@ pub struct thip_sweep_test {
 }
 
 pub enum thip_solver {}
+pub enum thip_batch {}
 pub enum thip_sptile {}
 pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
@@ -182,6 +193,22 @@ extern "C" {
     pub fn thip_sweep_publish_selftest(mode: c_int, host_agent_scope: *mut c_int, host_info: *mut c_int) -> c_int;
     pub fn thip_solver_gemv_plan(s: *const thip_solver, host_nj: *mut c_int, host_blocks: *mut c_int, host_ms: *mut f32) -> c_int;
 
+    pub fn thip_batch_create(prob_template: *const thip_problem, n_inst: c_int, host_vec_b: *const *const f32,
+                             host_vec_c: *const *const f32, par: *const thip_param, out: *mut *mut thip_batch) -> c_int;
+    pub fn thip_batch_set_a_storage(b: *mut thip_batch, a_kind: c_int) -> c_int;
+    pub fn thip_batch_set_gemv_autotune(b: *mut thip_batch, on: c_int) -> c_int;
+    pub fn thip_batch_set_max_group(b: *mut thip_batch, max_group: c_int) -> c_int;
+    pub fn thip_batch_set_param(b: *mut thip_batch, par: *const thip_param) -> c_int;
+    pub fn thip_batch_init(b: *mut thip_batch) -> c_int;
+    pub fn thip_batch_run(b: *mut thip_batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_batch_status(b: *mut thip_batch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_batch_solution(b: *mut thip_batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_batch_iterate(b: *mut thip_batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_batch_precond(b: *mut thip_batch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_batch_info(b: *const thip_batch, host_info: *mut thip_batch_info_t) -> c_int;
+    pub fn thip_batch_grouping(n_inst: c_int, max_group: c_int, host_groups: *mut c_int, host_members: *mut c_int) -> c_int;
+    pub fn thip_batch_destroy(b: *mut thip_batch) -> c_int;
+
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;
     pub fn thip_comm_allreduce(dev_buf: *mut f32, n: usize) -> c_int;
@@ -212,6 +239,9 @@ extern "C" {
 #[cfg(feature = "test-hooks")]
 extern "C" {
     pub fn thip_test_eig_force(engine: c_int) -> c_int;
+    pub fn thip_test_gemv_multi(m: usize, n: usize, mat: *const f32, nv: c_int, host_xn: *const *const f32, host_xt: *const *const f32,
+                                host_out_n: *const *mut f32, host_out_t: *const *mut f32, host_stopped: *const c_int, nj: c_int,
+                                target_blocks: c_int, reps: c_int, host_ms: *mut f32) -> c_int;
     pub fn thip_test_spin_allreduce(s: *mut thip_solver, latency_us: c_int) -> c_int;
     pub fn thip_test_sweep(t: *const thip_sweep_test, host_ms: *mut f32, host_info: *mut c_int) -> c_int;
     pub fn thip_test_solver_kahan(s: *mut thip_solver, host_kx: *mut f32, host_ky: *mut f32, host_ks: *mut f32, host_ku: *mut f32,

@@ -10,7 +10,12 @@ bump that moves it over the edge must fail the BUILD, not halve the bench silent
     is how a compiler bump shows first): at most MAX_SGPR_SPILL[element kind] -- the round-4 build's worst instances (f32: 78,
     16-bit: 117) plus a margin wide enough for the +-25 that any edit of the kernel's prologue moves them by.
 
-usage: check_kernel_resources.py <remarks file> [--report]"""
+The multi-vector dual GEMV (thip_gemv_multi.hip, --family gemv_multi) is designed against a register budget too -- NV x row
+accumulators + NV x entries of x_T + the columns of A in flight -- and a spill inside its column loop would sit on the streaming path:
+
+    every dual_gemv_multi_k<NV, NJ, KU> instance: the same scratch and occupancy bounds (no SGPR bound: it has no service chain).
+
+usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi]"""
 import re
 import sys
 
@@ -39,9 +44,36 @@ def parse(txt):
     return out
 
 
+def check_gemv_multi(res):
+    bad, seen = [], 0
+    for name, r in sorted(res.items()):
+        m = re.search(r"dual_gemv_multi_kILi(\d+)ELi(\d+)ELi(\d+)E", name)
+        if not m or "scratch" not in r:
+            continue
+        inst = tuple(int(v) for v in m.groups())
+        seen += 1
+        ok = r["scratch"] <= MAX_SCRATCH and r.get("occupancy", 0) >= MIN_OCC
+        if "--report" in sys.argv or not ok:
+            print("dual_gemv_multi_k<%s>: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD, %d B LDS"
+                  % (",".join(map(str, inst)), r.get("vgprs", -1), r.get("vgpr_spill", -1), r["scratch"], r.get("occupancy", -1),
+                     r.get("lds", -1)))
+        if not ok:
+            bad.append(inst)
+    if seen == 0:
+        print("check_kernel_resources: no dual_gemv_multi_k instance in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
+        return 2
+    if bad:
+        print("check_kernel_resources: FAILED for dual_gemv_multi_k%s: scratch > %d B/lane or < %d waves/SIMD -- the multi-vector "
+              "product has fallen off its register budget with this compiler (thip_gemv_multi.hip)" % (bad, MAX_SCRATCH, MIN_OCC))
+        return 1
+    return 0
+
+
 def main():
     txt = open(sys.argv[1]).read()
     res = parse(txt)
+    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "gemv_multi":
+        return check_gemv_multi(res)
     bad, seen = [], 0
     for name, r in sorted(res.items()):
         m = re.search(r"sweep_kILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", name)

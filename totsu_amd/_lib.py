@@ -51,6 +51,15 @@ class SweepTest(C.Structure):
                 ("host_sums", C.POINTER(C.c_float))]
 
 
+class BatchInfo(C.Structure):
+    _fields_ = [("n_inst", C.c_int32), ("max_group", C.c_int32), ("groups", C.c_int32), ("passes_per_iteration", C.c_int32),
+                ("a_copies", C.c_int32), ("reserved", C.c_int32), ("a_bytes", C.c_size_t), ("bytes_per_pass", C.c_size_t),
+                ("arena_bytes", C.c_size_t), ("device_bytes", C.c_size_t), ("plan_nj", C.c_int32 * 4),
+                ("plan_blocks", C.c_int32 * 4), ("plan_ms", C.c_float * 4)]
+
+
+BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/totsu_f32hip.h declares
@@ -177,6 +186,22 @@ PROTOTYPES = {
     "thip_test_sptile_equal": (_i, [_vp, _vp, C.POINTER(_i)]),
     "thip_test_gemm_dual": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "thip_solver_gemv_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
+    "thip_batch_create": (_i, [C.POINTER(Problem), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(Param), C.POINTER(_vp)]),
+    "thip_batch_set_a_storage": (_i, [_vp, _i]),
+    "thip_batch_set_gemv_autotune": (_i, [_vp, _i]),
+    "thip_batch_set_max_group": (_i, [_vp, _i]),
+    "thip_batch_set_param": (_i, [_vp, _vp]),
+    "thip_batch_init": (_i, [_vp]),
+    "thip_batch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_batch_status": (_i, [_vp, _i, C.POINTER(Status)]),
+    "thip_batch_solution": (_i, [_vp, _i, _vp, _vp]),
+    "thip_batch_iterate": (_i, [_vp, _i, _vp, _vp]),
+    "thip_batch_precond": (_i, [_vp, _i, _vp, _vp]),
+    "thip_batch_info": (_i, [_vp, C.POINTER(BatchInfo)]),
+    "thip_batch_grouping": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "thip_batch_destroy": (_i, [_vp]),
+    "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                  C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "thip_prof_read_psd": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -1,0 +1,152 @@
+"""`BatchSolver`: B problems over the SAME dense f32 A (their own b_i, c_i; one cone layout) iterated in lockstep on the device
+(thip_batch_* in include/totsu_f32hip.h) -- a regularisation path, a parameter sweep, a set of scenarios.  One multi-vector launch
+forms the products of up to eight instances from one read of A, so an iteration of the batch costs 2 * ceil(B / 8) passes over A
+instead of 2 B; everything else is the ordinary fused loop (2-pass carried schedule) on each instance's own state."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib
+from .fused import Bf16Matrix, DeviceBuffer, FusedResult, _c_param
+from .solver import SolverError, SolverParam
+
+
+def group_sizes(n_inst, max_group=_lib.BATCH_GROUP_DEFAULT):
+    """instances per multi-vector launch of one pass (thip_batch_grouping; needs no GPU)"""
+    g, mem = C.c_int(), (C.c_int * _lib.BATCH_MAX)()
+    lib.thip_batch_grouping(int(n_inst), int(max_group), C.byref(g), mem)
+    return [mem[i] for i in range(g.value)]
+
+
+def kernel_instance(members):
+    """the kernel a group of `members` instances runs on: 1 = the single-vector dual GEMV, else NV = 2, 4 or 8"""
+    return 1 if members <= 1 else 2 if members <= 2 else 4 if members <= 4 else 8
+
+
+class BatchSolver:
+    def __init__(self, n, m, mat_a, vecs_b, vecs_c, seg_type, seg_len, param=None, vec_b_rowabs=None, a_storage="f32",
+                 gemv_autotune=None, max_group=None):
+        """mat_a: DeviceBuffer or host array (column-major m x n, dense f32).  vecs_b / vecs_c: one array (or DeviceBuffer) per
+        instance.  Refused (ValueError): a sparse or 16-bit A, an a_storage other than "f32", lists of different lengths, vectors
+        of the wrong length, no instance or more than 64."""
+        self.h = None
+        self._owned = []
+        if hasattr(mat_a, "tocsr") or isinstance(mat_a, Bf16Matrix) or type(mat_a).__name__ == "SpTile":
+            raise ValueError("BatchSolver streams a dense f32 A: sparse and 16-bit matrices are not taken")
+        if a_storage != "f32":
+            raise ValueError("BatchSolver streams A in f32 only (a_storage=%r)" % (a_storage,))
+        if len(vecs_b) != len(vecs_c):
+            raise ValueError("vecs_b and vecs_c differ in length: %d vs %d" % (len(vecs_b), len(vecs_c)))
+        if not 1 <= len(vecs_b) <= _lib.BATCH_MAX:
+            raise ValueError("a batch holds 1 .. %d instances, not %d" % (_lib.BATCH_MAX, len(vecs_b)))
+        self.n, self.m, self.n_inst = int(n), int(m), len(vecs_b)
+        for name, vs, want in (("vecs_b", vecs_b, self.m), ("vecs_c", vecs_c, self.n)):
+            for v in vs:
+                got = v.n if isinstance(v, DeviceBuffer) else np.asarray(v).size
+                if (got < want) if isinstance(v, DeviceBuffer) else (got != want):
+                    raise ValueError("%s: a vector of %d entries where %d are needed" % (name, got, want))
+        if not isinstance(mat_a, DeviceBuffer) and np.asarray(mat_a).size != self.n * self.m:
+            raise ValueError("mat_a: %d entries where m * n = %d are needed" % (np.asarray(mat_a).size, self.n * self.m))
+        _lib.ensure_init()
+        self.mat_a = self._dev(mat_a)
+        self.vecs_b = [self._dev(v) for v in vecs_b]
+        self.vecs_c = [self._dev(v) for v in vecs_c]
+        self.vec_b_rowabs = None if vec_b_rowabs is None else self._dev(vec_b_rowabs)
+        self.param = param or SolverParam()
+        self._st = np.ascontiguousarray(seg_type, dtype=np.int32)
+        self._sl = np.ascontiguousarray(seg_len, dtype=np.int64)
+        prob = _lib.Problem(self.n, self.m, self.mat_a.ptr, None, None, None if self.vec_b_rowabs is None else self.vec_b_rowabs.ptr,
+                            len(self._st), self._st.ctypes.data_as(C.POINTER(C.c_int32)), self._sl.ctypes.data_as(C.POINTER(C.c_int64)))
+        pb = (C.c_void_p * self.n_inst)(*[v.ptr for v in self.vecs_b])
+        pc = (C.c_void_p * self.n_inst)(*[v.ptr for v in self.vecs_c])
+        par = _c_param(self.param)
+        h = C.c_void_p()
+        lib.thip_batch_create(C.byref(prob), self.n_inst, pb, pc, C.byref(par), C.byref(h))
+        self.h = h
+        if gemv_autotune is not None:
+            lib.thip_batch_set_gemv_autotune(self.h, 1 if gemv_autotune else 0)     # False: bit-reproducible across runs
+        if max_group is not None:
+            lib.thip_batch_set_max_group(self.h, int(max_group))
+        lib.thip_batch_init(self.h)
+
+    @staticmethod
+    def from_dense(d, vecs_b, vecs_c, param=None, **kw):
+        """the stacked description of Prob*.dense() for A and the cones; its own vec_b / vec_c are not used"""
+        return BatchSolver(d.n, d.m, d.mat_a, vecs_b, vecs_c, d.seg_type, d.seg_len, param, **kw)
+
+    def _dev(self, a):
+        if isinstance(a, DeviceBuffer):
+            return a
+        d = DeviceBuffer.from_host(a)
+        self._owned.append(d)
+        return d
+
+    def reinit(self):
+        """thip_batch_init again: a fresh solve of every instance"""
+        lib.thip_batch_init(self.h)
+
+    def set_param(self, param):
+        self.param = param
+        par = _c_param(param)
+        lib.thip_batch_set_param(self.h, C.byref(par))
+
+    def run(self, max_steps=-1, poll_every=16):
+        """every running instance advances by up to max_steps iterations; returns the list of the instances' FusedResult"""
+        st = (_lib.Status * self.n_inst)()
+        lib.thip_batch_run(self.h, int(max_steps), int(poll_every), st)
+        return [FusedResult(s) for s in st]
+
+    def status(self, i):
+        st = _lib.Status()
+        lib.thip_batch_status(self.h, int(i), C.byref(st))
+        return FusedResult(st)
+
+    def solution(self, i):
+        x = np.empty(self.n, dtype=np.float32)
+        y = np.empty(self.m, dtype=np.float32)
+        lib.thip_batch_solution(self.h, int(i), x.ctypes.data, y.ctypes.data)
+        return x, y
+
+    def iterate(self, i):
+        x = np.empty(self.n + 2 * self.m + 1, dtype=np.float32)
+        y = np.empty(self.n + self.m + 1, dtype=np.float32)
+        lib.thip_batch_iterate(self.h, int(i), x.ctypes.data, y.ctypes.data)
+        return x, y
+
+    def precond(self, i):
+        t = np.empty(self.n + 2 * self.m + 1, dtype=np.float32)
+        s = np.empty(self.n + self.m + 1, dtype=np.float32)
+        lib.thip_batch_precond(self.h, int(i), t.ctypes.data, s.ctypes.data)
+        return t, s
+
+    def info(self):
+        o = _lib.BatchInfo()
+        lib.thip_batch_info(self.h, C.byref(o))
+        d = {k: getattr(o, k) for k in ("n_inst", "max_group", "groups", "passes_per_iteration", "a_copies", "a_bytes",
+                                        "bytes_per_pass", "arena_bytes", "device_bytes")}
+        d["group_sizes"] = group_sizes(self.n_inst, o.max_group)
+        d["plans"] = {nv: {"rows_groups_per_lane": o.plan_nj[q], "target_workgroups": o.plan_blocks[q], "autotune_ms": o.plan_ms[q]}
+                      for q, nv in ((1, 2), (2, 4), (3, 8))}
+        return d
+
+    def solve(self, poll_every=16):
+        """Solver::solve semantics per instance: the list of (x, y), or a SolverError for an instance that did not converge"""
+        out = []
+        for i, r in enumerate(self.run(-1, poll_every)):
+            out.append(self.solution(i) if r.state == _lib.ST_OK else SolverError(r.state))
+        return out
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def destroy(self):
+        if getattr(self, "h", None) is not None:
+            lib.thip_batch_destroy(self.h)
+            self.h = None
+        for d in getattr(self, "_owned", []):
+            d.free()
+        self._owned = []

@@ -36,3 +36,4 @@ using namespace thip;
 #include "thip_solver_sweep.inc"
 #include "thip_solver_recovery.inc"
 #include "thip_solver_api.inc"
+#include "thip_solver_batch.inc"

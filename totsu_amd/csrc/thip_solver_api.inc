@@ -193,30 +193,51 @@ int thip_solver_set_overlap(thip_solver *s, int on)
     return 0;
 }
 
-int thip_solver_init(thip_solver *s)
+// thip_solver_init in its parts, so that a batch of solvers sharing A (thip_solver_batch.inc) initialises its instances with the same
+// launches.  The per-solve host state and init_vecs (solver.rs:483-494): x = 0, y = 0, tau = 1
+static int init_reset(thip_solver *s)
 {
-    THIP_NEED_INIT();
-    if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
     hipStream_t st = ctx().stream;
-    const size_t n = s->n, m = s->m;
-    const unsigned g = egrid(n > m ? n : m);
-
     // per-solve host state: a solver may be initialised again after a solve that terminated
     s->finalized = false;
     s->carried_stale = false;
     s->hst->state = THIP_ST_RUNNING;
-    THIP_RC(ensure_gemv_scratch(s));
-    if (!s->sa.is16()) THIP_RC(ensure_apad(s, true));      // a fresh solve re-reads the caller's A (it may have changed in place)
     s->xx = s->xx_home; s->kx = s->kx_home; s->xbuf = 0;
     s->sw_first = true; s->sweep_state = 0; s->pn_par = 0; s->status_pending = false; s->step_par = 0; s->pm_par = 0;
     s->sweep_faults = 0; s->sweep_fault_word = 0; s->sweep_fault_iter = -1; s->snap_iter = -1;
     // init_vecs (solver.rs:483-494): x = 0, y = 0, tau = 1
     THIP_TRY(hipMemsetAsync(s->arena, 0, s->arena_n * sizeof(float), st));
     hipLaunchKernelGGL(init_status_k, dim3(1), dim3(1), 0, st, s->dst, 0.0f);
+    return 0;
+}
+
+static int init_norms_precond(thip_solver *s, const float *shared_rowabs, const float *shared_colabs);
+
+int thip_solver_init(thip_solver *s)
+{
+    THIP_NEED_INIT();
+    if (!s) return fail(THIP_E_INVALID, "null solver", __FILE__, __LINE__);
+    hipStream_t st = ctx().stream;
+    THIP_RC(ensure_gemv_scratch(s));
+    if (!s->sa.is16()) THIP_RC(ensure_apad(s, true));      // a fresh solve re-reads the caller's A (it may have changed in place)
+    THIP_RC(init_reset(s));
     THIP_RC(sweep_prepare(s));        // (its plan autotune runs idempotent sweeps: after the stop flag has been cleared)
     if (s->sw_part) THIP_TRY(hipMemsetAsync(s->sw_part, 0, 12 * EG * sizeof(float), st));
     THIP_TRY(hipMemsetAsync(s->arena, 0, s->arena_n * sizeof(float), st));
+    THIP_RC(init_norms_precond(s, nullptr, nullptr));
+    s->split_plan = false;           // the one-launch form here; the column-split form is tuned by the first run that uses it
+    if (!sweep_active(s)) THIP_RC(autotune_gemv(s));      // (a run that falls back to the dual GEMV tunes it then: prepare_split)
+    s->inited = true;
+    return 0;
+}
 
+// calc_norms and calc_precond (solver.rs:460-481, 496-524).  shared_rowabs / shared_colabs != NULL: the |A| row and column sums as
+// finished vectors computed elsewhere (a batch: once for all its instances) instead of by a pass of this solver's own
+static int init_norms_precond(thip_solver *s, const float *shared_rowabs, const float *shared_colabs)
+{
+    hipStream_t st = ctx().stream;
+    const size_t n = s->n, m = s->m;
+    const unsigned g = egrid(n > m ? n : m);
     // calc_norms (solver.rs:460-481) + scalar parts of abssum (solver.rs:171-172)
     hipLaunchKernelGGL(init_sums_k, dim3(g), dim3(BLK), 0, st, (int)m, s->b, (int)n, s->c, s->part);
     float *sums = s->g1 + n;        // [0] sum b^2, [1] sum |b|  (sharded -> all-reduce)
@@ -225,8 +246,9 @@ int thip_solver_init(thip_solver *s)
     hipLaunchKernelGGL(sum_partials_k, dim3(1), dim3(BLK), 0, st, 2, (int)g, s->part + 2 * g, loc, (const int *)nullptr);
 
     // |A| column sums (sharded partial -> all-reduce with the two scalars in the tail) and row sums
-    float *colabs = s->g1, *rowabs = s->h1;
-    THIP_RC(abs_sums(s, rowabs, colabs));
+    const float *colabs = s->g1, *rowabs = s->h1;
+    if (shared_rowabs && shared_colabs) { rowabs = shared_rowabs; colabs = shared_colabs; }
+    else THIP_RC(abs_sums(s, s->h1, s->g1));
     if (s->col_shard) {
         // this rank holds a block of columns: b and the m-vectors are replicated, c is its block.  What the ranks have to
         // add up is the |A| row sums and sum c^2, sum |c| (the b sums and the column sums are complete as they are)
@@ -236,7 +258,7 @@ int thip_solver_init(thip_solver *s)
         THIP_TRY(hipMemcpyAsync(s->cs_buf, rowabs, m * sizeof(float), hipMemcpyDeviceToDevice, st));
         THIP_TRY(hipMemcpyAsync(s->cs_buf + m, loc, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
         THIP_RC(do_allreduce(s, s->cs_buf, s->cs_n));
-        THIP_TRY(hipMemcpyAsync(rowabs, s->cs_buf, m * sizeof(float), hipMemcpyDeviceToDevice, st));
+        THIP_TRY(hipMemcpyAsync(s->h1, s->cs_buf, m * sizeof(float), hipMemcpyDeviceToDevice, st));
         THIP_TRY(hipMemcpyAsync(loc, s->cs_buf + m, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
         THIP_TRY(hipMemsetAsync(s->cs_buf, 0, s->cs_n * sizeof(float), st));
     } else {
@@ -252,9 +274,6 @@ int thip_solver_init(thip_solver *s)
     THIP_TRY(hipMemsetAsync(s->g1, 0, (n + TAIL) * sizeof(float), st));
     THIP_TRY(hipMemsetAsync(s->h1, 0, (m ? m : 1) * sizeof(float), st));
     THIP_LAUNCH_CHECK();
-    s->split_plan = false;           // the one-launch form here; the column-split form is tuned by the first run that uses it
-    if (!sweep_active(s)) THIP_RC(autotune_gemv(s));      // (a run that falls back to the dual GEMV tunes it then: prepare_split)
-    s->inited = true;
     return 0;
 }
 

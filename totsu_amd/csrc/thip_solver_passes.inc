@@ -145,40 +145,51 @@ int project_blocks(thip_solver *s)
     return 0;
 }
 
-int one_iteration(thip_solver *s)
-{
-    hipStream_t st = ctx().stream;
-    const int n = (int)s->n, m = (int)s->m;
-    const unsigned g = egrid(s->n > s->m ? s->n : s->m);
-    float *const part = s->part;
-    const bool carried = s->carried_like();
-    const float ez = s->par.eps_zero;
-    GemvPartials gp;
-    // post_k leaves its sums as block partials: q0 (over the replicated n-vectors) in `part`, q1..q3 (over the local
-    // rows) in `part` too on a single GPU, or -- row-sharded -- in the tail of the n-vector that is all-reduced next,
-    // with a fixed grid of NPS blocks so that every rank fills the same NPS slots per sum.
-    const bool local = s->allreduce == nullptr;
-    const unsigned gq = local ? grid_for(s->n > s->m ? s->n : s->m, 64, PG) : NPS;
-    auto shp = [&](float *nvec) { return local ? part : nvec + s->n; };
-    const size_t arcount = s->n + TAIL;
-    float *const part_y = s->part + 4 * PG;          // ycrit_k's own partials (read by status_k)
-    const bool split = !local && (s->overlap == 1 || s->overlap == 2);   // m-part under the all-reduce, n-part after it
-    float *const kx = s->comp() ? s->kx : nullptr, *const ky = s->comp() ? s->ky : nullptr;
-    float *const ks = s->comp() ? s->ks : nullptr, *const ku = s->comp() ? s->ku : nullptr;
-    float *const kv = s->comp() ? s->kv : nullptr;
+// What every stage of one_iteration works with: grids, the block-partial buffers, the Kahan terms in use
+struct IterCtx {
+    thip_solver *s; hipStream_t st; int n, m; unsigned g, gq; float *part, *part_y; bool carried, local, split; float ez;
+    size_t arcount; float *kx, *ky, *ks, *ku, *kv;
+    explicit IterCtx(thip_solver *s_) : s(s_)
+    {
+        st = ctx().stream;
+        n = (int)s->n; m = (int)s->m;
+        g = egrid(s->n > s->m ? s->n : s->m);
+        part = s->part;
+        carried = s->carried_like();
+        ez = s->par.eps_zero;
+        // post_k leaves its sums as block partials: q0 (over the replicated n-vectors) in `part`, q1..q3 (over the local
+        // rows) in `part` too on a single GPU, or -- row-sharded -- in the tail of the n-vector that is all-reduced next,
+        // with a fixed grid of NPS blocks so that every rank fills the same NPS slots per sum.
+        local = s->allreduce == nullptr;
+        gq = local ? grid_for(s->n > s->m ? s->n : s->m, 64, PG) : NPS;
+        arcount = s->n + TAIL;
+        part_y = s->part + 4 * PG;          // ycrit_k's own partials (read by status_k)
+        split = !local && (s->overlap == 1 || s->overlap == 2);   // m-part under the all-reduce, n-part after it
+        kx = s->comp() ? s->kx : nullptr; ky = s->comp() ? s->ky : nullptr;
+        ks = s->comp() ? s->ks : nullptr; ku = s->comp() ? s->ku : nullptr;
+        kv = s->comp() ? s->kv : nullptr;
+    }
+    float *shp(float *nvec) const { return local ? part : nvec + s->n; }
+};
 
+// ---- stage X after its products: x update (solver.rs:538-555) ------------------------------------
+int stage_x_tail(thip_solver *s, const GemvPartials &gp)
+{
+    const IterCtx c(s);
+    hipStream_t st = c.st;
+    const int n = c.n, m = c.m;
+    const unsigned g = c.g, gq = c.gq;
+    float *const part = c.part;
     auto xupdate = [&](int do_n, int do_m) {
         hipLaunchKernelGGL(xupdate_k, dim3(g), dim3(BLK), 0, st, n, m, s->g1, s->h1, s->c, s->b, s->v, s->Tx, s->Ty, s->Ts,
-                           s->cls, s->xx, s->xy, s->xs, s->rxx, s->rxy, s->rxs, s->dst, part, (int)gq, shp(s->g1) + gq, (int)gq,
-                           do_n, do_m, do_n, kx, ky, ks);
+                           s->cls, s->xx, s->xy, s->xs, s->rxx, s->rxy, s->rxs, s->dst, part, (int)gq, c.shp(s->g1) + gq, (int)gq,
+                           do_n, do_m, do_n, c.kx, c.ky, c.ks);
     };
-    // ---- stage X: x update (solver.rs:538-555) ----------------------------------------------------
-    THIP_RC(products(s, s->u, s->v, &gp, s->h1, s->g1));
     hipLaunchKernelGGL(post_k, dim3(gq), dim3(BLK), 0, st, n, m, gp.partT, gp.nT, gp.strideT, s->g1, gp.partN, gp.nN,
                        gp.strideN, s->h1, s->c, s->u, s->b, s->v, 0, (const float *)nullptr, (const float *)nullptr,
-                       (const float *)nullptr, ez, part, shp(s->g1), s->dst, 1);
-    THIP_RC(allreduce_begin(s, s->g1, arcount));
-    if (split) {
+                       (const float *)nullptr, c.ez, part, c.shp(s->g1), s->dst, 1);
+    THIP_RC(allreduce_begin(s, s->g1, c.arcount));
+    if (c.split) {
         xupdate(0, 1);
         THIP_RC(project_blocks(s));      // the block cones live on the local rows
         THIP_RC(allreduce_end(s));
@@ -188,45 +199,74 @@ int one_iteration(thip_solver *s)
         xupdate(1, 1);
         THIP_RC(project_blocks(s));
     }
+    return 0;
+}
 
-    // ---- stage Y: y update from K rx (solver.rs:557-567), own products unless carried ---------------
-    if (!carried) {
-        THIP_RC(products(s, s->rxx, s->rxy, &gp, s->h2, s->g2));
-        hipLaunchKernelGGL(post_k, dim3(gq), dim3(BLK), 0, st, n, m, gp.partT, gp.nT, gp.strideT, s->g2, gp.partN, gp.nN,
-                           gp.strideN, s->h2, s->c, s->rxx, s->b, s->rxy, 0, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, ez, part, shp(s->g2), s->dst, 1);
-        auto yupdate = [&](int do_n, int do_m) {
-            hipLaunchKernelGGL(ycrit_k, dim3(g), dim3(BLK), 0, st, n, m, 1, 0, 0, (const float *)nullptr,
-                               (const float *)nullptr, (float *)nullptr, (float *)nullptr, s->g2, s->h2, s->c, s->b, s->rxs,
-                               s->Su, s->Sv, s->u, s->v, s->xx, ez, part_y, s->dst, part, (int)gq, shp(s->g2) + gq, (int)gq,
-                               do_n, do_m, do_n, 0, (int)g, ku, kv);
-        };
-        THIP_RC(allreduce_begin(s, s->g2, arcount));
-        if (split) { yupdate(0, 1); THIP_RC(allreduce_end(s)); yupdate(1, 0); }
-        else       { THIP_RC(allreduce_end(s)); yupdate(1, 1); }
-    }
+// ---- stage Y: y update from K rx (solver.rs:557-567), own products (the schedules that do not carry them) ----
+int stage_y(thip_solver *s)
+{
+    const IterCtx c(s);
+    hipStream_t st = c.st;
+    const int n = c.n, m = c.m;
+    const unsigned g = c.g, gq = c.gq;
+    float *const part = c.part;
+    GemvPartials gp;
+    THIP_RC(products(s, s->rxx, s->rxy, &gp, s->h2, s->g2));
+    hipLaunchKernelGGL(post_k, dim3(gq), dim3(BLK), 0, st, n, m, gp.partT, gp.nT, gp.strideT, s->g2, gp.partN, gp.nN,
+                       gp.strideN, s->h2, s->c, s->rxx, s->b, s->rxy, 0, (const float *)nullptr,
+                       (const float *)nullptr, (const float *)nullptr, c.ez, part, c.shp(s->g2), s->dst, 1);
+    auto yupdate = [&](int do_n, int do_m) {
+        hipLaunchKernelGGL(ycrit_k, dim3(g), dim3(BLK), 0, st, n, m, 1, 0, 0, (const float *)nullptr,
+                           (const float *)nullptr, (float *)nullptr, (float *)nullptr, s->g2, s->h2, s->c, s->b, s->rxs,
+                           s->Su, s->Sv, s->u, s->v, s->xx, c.ez, c.part_y, s->dst, part, (int)gq, c.shp(s->g2) + gq, (int)gq,
+                           do_n, do_m, do_n, 0, (int)g, c.ku, c.kv);
+    };
+    THIP_RC(allreduce_begin(s, s->g2, c.arcount));
+    if (c.split) { yupdate(0, 1); THIP_RC(allreduce_end(s)); yupdate(1, 0); }
+    else         { THIP_RC(allreduce_end(s)); yupdate(1, 1); }
+    return 0;
+}
 
-    // ---- stage C: criteria products of the new iterate (solver.rs:573-656) --------------------------
-    THIP_RC(products(s, s->xx, s->xy, &gp, s->h3, s->g3));
+// ---- stage C after its products: criteria of the new iterate (solver.rs:573-656), the carried y update, the termination test ----
+int stage_c_tail(thip_solver *s, const GemvPartials &gp)
+{
+    const IterCtx c(s);
+    hipStream_t st = c.st;
+    const int n = c.n, m = c.m;
+    const unsigned g = c.g, gq = c.gq;
+    float *const part = c.part;
+    const bool carried = c.carried;
     // block partials: q0 = c.rx_x, q1 = b.rx_y (carried), q2 = ||p||^2, q3 = b.x_y
     hipLaunchKernelGGL(post_k, dim3(gq), dim3(BLK), 0, st, n, m, gp.partT, gp.nT, gp.strideT, s->g3, gp.partN, gp.nN,
                        gp.strideN, s->h3, carried ? s->c : (const float *)nullptr, s->rxx,
-                       carried ? s->b : (const float *)nullptr, s->rxy, 1, s->xs, s->xy, s->b, ez, part, shp(s->g3), s->dst, 1);
+                       carried ? s->b : (const float *)nullptr, s->rxy, 1, s->xs, s->xy, s->b, c.ez, part, c.shp(s->g3), s->dst, 1);
     auto ycrit = [&](int do_n, int do_m) {
         hipLaunchKernelGGL(ycrit_k, dim3(g), dim3(BLK), 0, st, n, m, carried ? 1 : 0, 1, 1, s->g3, s->h3, s->gP, s->hP,
                            (const float *)nullptr, (const float *)nullptr, s->c, s->b, s->rxs, s->Su, s->Sv, s->u, s->v, s->xx,
-                           ez, part_y, s->dst, part, (int)gq, shp(s->g3) + gq, (int)gq, do_n, do_m, do_n, 0, (int)g, ku, kv);
+                           c.ez, c.part_y, s->dst, part, (int)gq, c.shp(s->g3) + gq, (int)gq, do_n, do_m, do_n, 0, (int)g, c.ku, c.kv);
     };
-    THIP_RC(allreduce_begin(s, s->g3, arcount));
-    if (split && carried) { ycrit(0, 1); THIP_RC(allreduce_end(s)); ycrit(1, 0); }
-    else                  { THIP_RC(allreduce_end(s)); ycrit(1, 1); }
+    THIP_RC(allreduce_begin(s, s->g3, c.arcount));
+    if (c.split && carried) { ycrit(0, 1); THIP_RC(allreduce_end(s)); ycrit(1, 0); }
+    else                    { THIP_RC(allreduce_end(s)); ycrit(1, 1); }
     {
-        const StatArgs sa{ (int)g, part_y, shp(s->g3) + 2 * gq, shp(s->g3) + 3 * gq, (int)gq, nullptr, 0, nullptr, 0, nullptr,
-                           s->par.eps_acc, s->par.eps_inf, ez, (long long)s->par.max_iter, s->xbuf };
+        const StatArgs sa{ (int)g, c.part_y, c.shp(s->g3) + 2 * gq, c.shp(s->g3) + 3 * gq, (int)gq, nullptr, 0, nullptr, 0, nullptr,
+                           s->par.eps_acc, s->par.eps_inf, c.ez, (long long)s->par.max_iter, s->xbuf };
         hipLaunchKernelGGL(status_k, dim3(1), dim3(BLK), 0, st, sa, s->dst);
     }
     THIP_LAUNCH_CHECK();
     return 0;
+}
+
+// One iteration = the products of a stage, then its tail.  The tails take the partial sums from wherever the product left them:
+// a batch of solvers that share A (thip_solver_batch.inc) forms them for several instances from one read of A.
+int one_iteration(thip_solver *s)
+{
+    GemvPartials gp;
+    THIP_RC(products(s, s->u, s->v, &gp, s->h1, s->g1));
+    THIP_RC(stage_x_tail(s, gp));
+    if (!s->carried_like()) THIP_RC(stage_y(s));
+    THIP_RC(products(s, s->xx, s->xy, &gp, s->h3, s->g3));
+    return stage_c_tail(s, gp);
 }
 
 // ---------------------------------------------------------------------------------------------------
