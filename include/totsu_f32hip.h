@@ -512,6 +512,42 @@ int thip_batch_info(const thip_batch *b, thip_batch_info_t *host_info);
 int thip_batch_grouping(int n_inst, int max_group, int *host_groups, int *host_members);
 int thip_batch_destroy(thip_batch *b);
 
+/* ---- a batch as a set of SLOTS that problems stream through, and launches that follow the live set (both opt-in: without
+ * these calls a batch behaves as described above, bit for bit) ----
+ *
+ * thip_batch_replace: after thip_batch_init.  Slot i -- running or stopped, for whatever reason -- is pointed at the new
+ * caller-owned device vectors (m / n floats) and becomes exactly what thip_batch_init would have made of an instance created with
+ * them: norms of b and c, x = 0, y = 0, tau = 1, the preconditioner and group minima from the batch's shared |A| sums (no pass
+ * over A), Kahan terms zero, the (zero) carried products of the start iterate, iteration count 0, state RUNNING.  No other
+ * instance is touched.  The launches go into the stream in order; the call reads the retired occupant's status first (a
+ * synchronise), so the old b / c are no longer read once it has returned: the caller may free them AFTER the call returns, not
+ * before.  THIP_E_INVALID: a null argument, no such slot, a batch that is not initialised. */
+int thip_batch_replace(thip_batch *b, int i, const float *dev_vec_b, const float *dev_vec_c);
+/* on = 1: at every poll the instances the host saw RUNNING are packed in ascending index order into groups of at most max_group
+ * (thip_batch_live_grouping), so a pass costs ceil(live / max_group) launches; a group of k runs on the kernel instance of k
+ * vectors, a group of one on the single-vector kernel.  thip_batch_init then tunes every kernel instance the batch can come to
+ * use (NV = 2, 4, 8 up to max_group and the single-vector plan, once, shared by all instances); thip_batch_run tunes nothing.
+ * on = 0 (default): the groups fixed by index at init.  Before thip_batch_init (THIP_E_INVALID after it). */
+int thip_batch_set_regroup(thip_batch *b, int on);
+/* thip_batch_run that returns at the first poll which finds stopped an instance that was RUNNING when the call began (and, like
+ * it, when nothing is running or after max_steps iterations).  SYNC. */
+int thip_batch_run_until_any(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+/* the regroup rule: host_live[n_inst] (non-zero = running) -> *host_groups launches per pass, their sizes (host_group_sizes: up
+ * to THIP_BATCH_MAX ints or NULL; full groups first, the rest last) and the live instance indices in launch order (host_members:
+ * up to THIP_BATCH_MAX ints or NULL).  Needs no device. */
+int thip_batch_live_grouping(int n_inst, int max_group, const int *host_live, int *host_groups, int *host_group_sizes,
+                             int *host_members);
+/* what thip_batch_run / thip_batch_run_until_any have issued since thip_batch_init (which zeroes the counters) */
+typedef struct thip_batch_counters_t {
+    int64_t launches[4];              /* product launches by kernel instance: [0] single-vector, [1] NV = 2, [2] NV = 4, [3] NV = 8 */
+    int64_t passes;                   /* their sum: passes over A */
+    int64_t instance_iterations;      /* iterations completed, summed over the slots (a retired occupant's count is added when its
+                                         slot is replaced) */
+    int64_t replaced;                 /* thip_batch_replace calls */
+    int32_t live, groups_now;         /* as of the last poll: instances RUNNING, launches per pass */
+} thip_batch_counters_t;
+int thip_batch_counters(const thip_batch *b, thip_batch_counters_t *host);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

@@ -29,6 +29,12 @@ pub struct thip_batch_info_t {
     pub a_bytes: usize, pub bytes_per_pass: usize, pub arena_bytes: usize, pub device_bytes: usize,
     pub plan_nj: [i32; 4], pub plan_blocks: [i32; 4], pub plan_ms: [f32; 4],
 }
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_batch_counters_t {
+    pub launches: [i64; 4], pub passes: i64, pub instance_iterations: i64, pub replaced: i64,
+    pub live: i32, pub groups_now: i32,
+}
 pub const THIP_BATCH_MAX: c_int = 64;
 pub const THIP_BATCH_GROUP_DEFAULT: c_int = 8;
 
@@ -208,6 +214,12 @@ extern "C" {
     pub fn thip_batch_info(b: *const thip_batch, host_info: *mut thip_batch_info_t) -> c_int;
     pub fn thip_batch_grouping(n_inst: c_int, max_group: c_int, host_groups: *mut c_int, host_members: *mut c_int) -> c_int;
     pub fn thip_batch_destroy(b: *mut thip_batch) -> c_int;
+    pub fn thip_batch_replace(b: *mut thip_batch, i: c_int, dev_vec_b: *const f32, dev_vec_c: *const f32) -> c_int;
+    pub fn thip_batch_set_regroup(b: *mut thip_batch, on: c_int) -> c_int;
+    pub fn thip_batch_run_until_any(b: *mut thip_batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_batch_live_grouping(n_inst: c_int, max_group: c_int, host_live: *const c_int, host_groups: *mut c_int,
+                                    host_group_sizes: *mut c_int, host_members: *mut c_int) -> c_int;
+    pub fn thip_batch_counters(b: *const thip_batch, host: *mut thip_batch_counters_t) -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

@@ -11,11 +11,11 @@ from .cone import ConeZero, ConeRPos, ConeSOC, ConeRotSOC, ConePSD
 from .matbuild import MatBuild
 from .problem import ProbLP, ProbSOCP, ProbSDP, ProbQP, ProbQCQP
 from .fused import FusedSolver, DeviceBuffer, Bf16Matrix
-from .batch import BatchSolver
+from .batch import BatchSolver, solve_many
 from .parallel import ShardedSolver, TorchComm, shard_segments
 from .sparse import SparseMatOp, SpTile
 
 __all__ = ["MatOp", "MatType", "Solver", "SolverError", "SolverParam", "F32HIP", "F32HIPSlice", "splitm",
            "ConeZero", "ConeRPos", "ConeSOC", "ConeRotSOC", "ConePSD", "MatBuild", "ProbLP", "ProbSOCP",
-           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
+           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "solve_many", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
            "shard_segments", "SparseMatOp", "SpTile"]

@@ -58,6 +58,11 @@ class BatchInfo(C.Structure):
                 ("plan_blocks", C.c_int32 * 4), ("plan_ms", C.c_float * 4)]
 
 
+class BatchCounters(C.Structure):
+    _fields_ = [("launches", C.c_int64 * 4), ("passes", C.c_int64), ("instance_iterations", C.c_int64), ("replaced", C.c_int64),
+                ("live", C.c_int32), ("groups_now", C.c_int32)]
+
+
 BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -200,6 +205,11 @@ PROTOTYPES = {
     "thip_batch_info": (_i, [_vp, C.POINTER(BatchInfo)]),
     "thip_batch_grouping": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "thip_batch_destroy": (_i, [_vp]),
+    "thip_batch_replace": (_i, [_vp, _i, _vp, _vp]),
+    "thip_batch_set_regroup": (_i, [_vp, _i]),
+    "thip_batch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_batch_live_grouping": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "thip_batch_counters": (_i, [_vp, C.POINTER(BatchCounters)]),
     "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
     "thip_prof_enable": (_i, [_i]),

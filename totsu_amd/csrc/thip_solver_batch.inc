@@ -8,6 +8,10 @@
 // The stored form of A exists once: the caller's array and -- when m is no multiple of 16 floats -- ONE library-owned padded copy,
 // which every instance borrows through its StoredA (the batch frees it).  The |A| row and column sums of the preconditioner are
 // computed once.  Passes over A per iteration: 2 * ceil(B / max_group) instead of 2 B.
+//
+// The instances are slots: thip_batch_replace hands one the next problem (b, c by pointer, a fresh init from the shared |A| sums), and
+// with thip_batch_set_regroup the launches of a pass are formed anew from the live instances after every poll -- ceil(live / max_group)
+// of them.  Both are host-side bookkeeping over the same kernels; without them the groups stay fixed by index as above.
 
 struct thip_batch {
     size_t n = 0, m = 0;
@@ -20,7 +24,9 @@ struct thip_batch {
     GemvPlan mplan[4];                   // tuned tilings of the multi-vector kernel, by instance: [1] NV = 2, [2] NV = 4, [3] NV = 8
     int autotune = -1;                   // as thip_solver::autotune
     int max_group = THIP_BATCH_GROUP_DEFAULT;
+    bool regroup = false;                // the launches follow the live set (thip_batch_set_regroup)
     bool inited = false;
+    thip_batch_counters_t ctr{};         // what run / run_until_any issued since init; instance_iterations: the retired occupants' only
     DenseA A() const { return pad ? DenseA{ pad, ldpad, THIP_A_F32, nullptr, true } : dense_f32(a_f32, m); }
 };
 
@@ -35,19 +41,30 @@ void batch_groups(int n_inst, int max_group, std::vector<std::pair<int, int>> *o
     for (int i = 0; i < n_inst; i += max_group) out->push_back({ i, std::min(max_group, n_inst - i) });
 }
 
+// the regroup rule: the live instances in ascending index order (members), cut into groups of at most max_group -- (offset into
+// members, size) per group, full groups first and the rest last
+void live_groups(int n_inst, int max_group, const char *live, std::vector<int> *members, std::vector<std::pair<int, int>> *out)
+{
+    members->clear();
+    for (int i = 0; i < n_inst; ++i) if (live[i]) members->push_back(i);
+    batch_groups((int)members->size(), max_group, out);
+}
+
+int counter_slot(int members) { return members == 1 ? 0 : plan_slot(gemv_multi_instance(members)); }
+
 const GemvHint *batch_hint(const thip_batch *b, int members)
 {
     const GemvPlan &p = b->mplan[plan_slot(gemv_multi_instance(members))];
     return p.tuned ? &p.hint : nullptr;
 }
 
-// one pass over A for a group: which = 0 the stage-X products (u, v), 1 the stage-C products (x_x, x_y); stop = the members' own
-// flags (nullptr: unconditionally, outside the loop)
-int batch_products(thip_batch *b, int first, int members, int which, bool with_stop, GemvPartials *gp, const GemvHint *hint)
+// one pass over A for a group, given as the list of its members' indices: which = 0 the stage-X products (u, v), 1 the stage-C
+// products (x_x, x_y); stop = the members' own flags (nullptr: unconditionally, outside the loop)
+int batch_products(thip_batch *b, const int *idx, int members, int which, bool with_stop, GemvPartials *gp, const GemvHint *hint)
 {
     hipStream_t st = ctx().stream;
     if (members == 1) {          // the single-vector kernel under the instance's own plan
-        thip_solver *s = b->inst[first];
+        thip_solver *s = b->inst[idx[0]];
         if (with_stop) return which == 0 ? products(s, s->u, s->v, gp, s->h1, s->g1) : products(s, s->xx, s->xy, gp, s->h3, s->g3);
         *gp = GemvPartials{};
         if (s->m == 0 || s->n == 0) return 0;
@@ -58,7 +75,7 @@ int batch_products(thip_batch *b, int first, int members, int which, bool with_s
     float *scr[GEMV_MULTI_MAX];
     const int *stop[GEMV_MULTI_MAX];
     for (int j = 0; j < members; ++j) {
-        thip_solver *s = b->inst[first + j];
+        thip_solver *s = b->inst[idx[j]];
         xn[j] = which == 0 ? s->u : s->xx; xt[j] = which == 0 ? s->v : s->xy;
         scr[j] = s->gemv_scr; stop[j] = with_stop ? &s->dst->stop : nullptr;
     }
@@ -66,6 +83,14 @@ int batch_products(thip_batch *b, int first, int members, int which, bool with_s
     THIP_RC(dual_gemv_multi_partials(st, b->m, b->n, b->A(), members, xn, xt, scr, b->scr_floats, stop, gp, hint));
     prof_end(st);
     return 0;
+}
+
+// the same for members first .. first + members - 1
+int batch_products(thip_batch *b, int first, int members, int which, bool with_stop, GemvPartials *gp, const GemvHint *hint)
+{
+    int idx[GEMV_MULTI_MAX];
+    for (int j = 0; j < members; ++j) idx[j] = first + j;
+    return batch_products(b, idx, members, which, with_stop, gp, hint);
 }
 
 // the padded copy (m % 16 != 0), made once and refreshed by every init: the caller may have rewritten A in place between solves
@@ -240,6 +265,7 @@ int thip_batch_init(thip_batch *b)
             s->gemv_scr_n = b->scr_floats;
         }
         THIP_RC(init_reset(s));
+        s->hst->iter = 0;            // (the host record is next written by a poll: thip_batch_counters reads it before that)
     }
     // the |A| row and column sums of the preconditioner: one pass for all instances
     if (b->m && b->n) THIP_RC(abs_sums(b->inst[0], b->rowabs, b->colabs));
@@ -248,11 +274,23 @@ int thip_batch_init(thip_batch *b)
         s->split_plan = false;
         s->inited = true;
     }
+    const int B = (int)b->inst.size();
     std::vector<std::pair<int, int>> groups;
-    batch_groups((int)b->inst.size(), b->max_group, &groups);
-    for (auto &g : groups) {
-        if (g.second == 1) THIP_RC(autotune_gemv(b->inst[g.first]));
-        else THIP_RC(autotune_multi(b, g.first, g.second));
+    batch_groups(B, b->max_group, &groups);
+    if (b->regroup) {
+        // every kernel instance the live set can come to be served by: NV = 2, 4, 8 as far as max_group and B reach, and the
+        // single-vector plan -- timed once on instance 0 and handed to the others (the matrix is the same)
+        for (int nv = 2; nv <= b->max_group; nv *= 2) {
+            const int members = std::min(nv, B);
+            if (members >= 2 && gemv_multi_instance(members) == nv) THIP_RC(autotune_multi(b, 0, members));
+        }
+        THIP_RC(autotune_gemv(b->inst[0]));
+        for (thip_solver *s : b->inst) s->plan[0][0] = b->inst[0]->plan[0][0];
+    } else {
+        for (auto &g : groups) {
+            if (g.second == 1) THIP_RC(autotune_gemv(b->inst[g.first]));
+            else THIP_RC(autotune_multi(b, g.first, g.second));
+        }
     }
     // the carried products gP = A^T x_y, hP = A x_x of the start iterate (what rebuild_carried does for one solver), a pass per group
     for (auto &g : groups) {
@@ -266,43 +304,137 @@ int thip_batch_init(thip_batch *b)
         }
     }
     for (size_t i = 0; i < b->inst.size(); ++i) b->live[i] = 1;
+    b->ctr = thip_batch_counters_t{};
+    b->ctr.live = B;
+    b->ctr.groups_now = (int32_t)groups.size();
     b->inited = true;
     return 0;
 }
 
-int thip_batch_run(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status)
+// thip_batch_run and thip_batch_run_until_any.  The launches of a pass: the groups fixed by index, each launched while a member is
+// live (its stopped members are masked by their stop flags) -- or, regroup, the live instances packed anew after every poll
+static int batch_run_impl(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status, bool until_any)
 {
     THIP_NEED_INIT();
     if (!b || !b->inited) return fail(THIP_E_INVALID, "batch not initialised", __FILE__, __LINE__);
     if (poll_every <= 0) poll_every = 16;
-    std::vector<std::pair<int, int>> groups;
-    batch_groups((int)b->inst.size(), b->max_group, &groups);
+    const int B = (int)b->inst.size();
+    std::vector<int> members(B);
+    std::vector<std::pair<int, int>> fixed, groups;      // (offset into members, size)
+    batch_groups(B, b->max_group, &fixed);
+    auto any_live = [&](int first, int n) {
+        for (int j = 0; j < n; ++j) if (b->live[first + j]) return true;
+        return false;
+    };
+    // after a poll: the launches of the next iterations, and what the counters say of the live set
+    auto regroup = [&]() {
+        if (b->regroup) {
+            live_groups(B, b->max_group, b->live.data(), &members, &groups);
+        } else {
+            members.resize(B);
+            for (int i = 0; i < B; ++i) members[i] = i;
+            groups.clear();
+            for (auto &g : fixed) if (any_live(g.first, g.second)) groups.push_back(g);      // every member stopped: skipped
+        }
+        int live = 0;
+        for (int i = 0; i < B; ++i) live += b->live[i] != 0;
+        b->ctr.live = live;
+        b->ctr.groups_now = (int32_t)groups.size();
+    };
     THIP_RC(batch_poll(b, host_status));
-    auto any_live = [&](int first, int members) {
-        for (int j = 0; j < members; ++j) if (b->live[first + j]) return true;
+    regroup();
+    const std::vector<char> was_live = b->live;
+    auto one_stopped = [&]() {
+        for (int i = 0; i < B; ++i) if (was_live[i] && !b->live[i]) return true;
         return false;
     };
     int64_t done = 0;
-    while (any_live(0, (int)b->inst.size()) && (max_steps < 0 || done < max_steps)) {
+    while (any_live(0, B) && (max_steps < 0 || done < max_steps) && !(until_any && one_stopped())) {
         int64_t batch = poll_every;
         if (max_steps >= 0 && done + batch > max_steps) batch = max_steps - done;
         for (int64_t k = 0; k < batch; ++k) {
             prof_tick();
             for (int which = 0; which < 2; ++which)
                 for (auto &g : groups) {
-                    if (!any_live(g.first, g.second)) continue;      // every member has stopped: the group's launches are skipped
+                    const int *idx = members.data() + g.first;
                     GemvPartials gp[GEMV_MULTI_MAX];
-                    THIP_RC(batch_products(b, g.first, g.second, which, true, gp, batch_hint(b, g.second)));
+                    THIP_RC(batch_products(b, idx, g.second, which, true, gp, g.second > 1 ? batch_hint(b, g.second) : nullptr));
+                    b->ctr.launches[counter_slot(g.second)] += 1;
+                    b->ctr.passes += 1;
                     for (int j = 0; j < g.second; ++j) {
-                        thip_solver *s = b->inst[g.first + j];
-                        if (!b->live[g.first + j]) continue;        // (its kernels would return at entry)
-                        THIP_RC(which == 0 ? stage_x_tail(s, gp[j]) : stage_c_tail(s, gp[j]));
+                        if (!b->live[idx[j]]) continue;        // (its kernels would return at entry)
+                        THIP_RC(which == 0 ? stage_x_tail(b->inst[idx[j]], gp[j]) : stage_c_tail(b->inst[idx[j]], gp[j]));
                     }
                 }
         }
         done += batch;
         THIP_RC(batch_poll(b, host_status));
+        regroup();
     }
+    return 0;
+}
+
+int thip_batch_run(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status)
+{
+    return batch_run_impl(b, max_steps, poll_every, host_status, false);
+}
+
+int thip_batch_run_until_any(thip_batch *b, int64_t max_steps, int64_t poll_every, thip_status *host_status)
+{
+    return batch_run_impl(b, max_steps, poll_every, host_status, true);
+}
+
+int thip_batch_set_regroup(thip_batch *b, int on)
+{
+    if (!b) return fail(THIP_E_INVALID, "null batch", __FILE__, __LINE__);
+    if (b->inited) return fail(THIP_E_INVALID, "thip_batch_set_regroup comes before thip_batch_init", __FILE__, __LINE__);
+    b->regroup = on != 0;
+    return 0;
+}
+
+int thip_batch_replace(thip_batch *b, int i, const float *dev_vec_b, const float *dev_vec_c)
+{
+    THIP_NEED_INIT();
+    if (!b || !b->inited) return fail(THIP_E_INVALID, "batch not initialised", __FILE__, __LINE__);
+    if (i < 0 || (size_t)i >= b->inst.size()) return fail(THIP_E_INVALID, "no such instance", __FILE__, __LINE__);
+    if ((!dev_vec_b && b->m) || (!dev_vec_c && b->n)) return fail(THIP_E_INVALID, "null b or c", __FILE__, __LINE__);
+    thip_solver *s = b->inst[(size_t)i];
+    THIP_RC(poll(s, nullptr));                  // the retired occupant's iteration count; nothing reads its b / c after this
+    b->ctr.instance_iterations += s->hst->iter;
+    b->ctr.replaced += 1;
+    s->b = dev_vec_b; s->c = dev_vec_c;
+    // what thip_batch_init does to an instance, from the shared |A| sums.  init_reset zeroes the whole arena: the iterate, the
+    // Kahan terms, and gP / hP -- which are the carried products of the start iterate x = 0, y = 0 as they stand
+    THIP_RC(init_reset(s));
+    s->hst->iter = 0;
+    THIP_RC(init_norms_precond(s, b->rowabs, b->colabs));
+    s->split_plan = false;
+    s->inited = true;
+    if (!b->live[(size_t)i]) { b->live[(size_t)i] = 1; b->ctr.live += 1; }
+    // (groups_now follows at the next poll, which every run begins with)
+    return 0;
+}
+
+int thip_batch_live_grouping(int n_inst, int max_group, const int *host_live, int *host_groups, int *host_group_sizes, int *host_members)
+{
+    if (n_inst < 1 || n_inst > THIP_BATCH_MAX || (max_group != 2 && max_group != 4 && max_group != 8) || !host_live || !host_groups)
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    std::vector<char> live((size_t)n_inst);
+    for (int i = 0; i < n_inst; ++i) live[(size_t)i] = host_live[i] != 0;
+    std::vector<int> members;
+    std::vector<std::pair<int, int>> g;
+    live_groups(n_inst, max_group, live.data(), &members, &g);
+    *host_groups = (int)g.size();
+    if (host_group_sizes) for (size_t k = 0; k < g.size(); ++k) host_group_sizes[k] = g[k].second;
+    if (host_members) for (size_t k = 0; k < members.size(); ++k) host_members[k] = members[k];
+    return 0;
+}
+
+int thip_batch_counters(const thip_batch *b, thip_batch_counters_t *host)
+{
+    if (!b || !host) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    *host = b->ctr;
+    if (b->inited) for (const thip_solver *s : b->inst) host->instance_iterations += s->hst->iter;      // the current occupants, as of the last poll
     return 0;
 }
 
