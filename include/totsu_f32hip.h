@@ -548,6 +548,53 @@ typedef struct thip_batch_counters_t {
 } thip_batch_counters_t;
 int thip_batch_counters(const thip_batch *b, thip_batch_counters_t *host);
 
+/* ---------------------------------------------------------------------------------------------
+ * Many SMALL problems, each with its own A, iterated on chip (thip_smallbatch.hip).
+ * n_prob problems share n, m and the cone layout and differ in A, b, c (and vec_b_rowabs): problem p's data is at
+ * dev_mats_a + p m n (column-major, lda = m), dev_vecs_b + p m, dev_vecs_c + p n, dev_vecs_b_rowabs + p m (or NULL: |b|); the
+ * arrays stay the caller's and must outlive the object.  One launch gives ONE workgroup to each problem still running: it holds
+ * the problem's A in the LDS of its CU and runs min(poll_every, steps left) whole iterations of the reference's loop -- both
+ * products, the updates, the cone projections, the termination test -- with no launch boundary inside; the host then reads
+ * every status block in one transfer and launches again over the problems still RUNNING.  A problem's iterates depend on its own
+ * data and the workgroup size alone: not on its index, its neighbours, or how the iterations were cut into launches.
+ * Accepted (else THIP_E_INVALID): 1 <= m <= 1024, 1 <= n <= 1024, m n <= 24576, segments of the zero, nonnegative, second-order
+ * and rotated second-order cones that cover m (no PSD segment), 1 <= n_prob <= 1048576.  Both THIP_STATE_* arithmetics.
+ * status / solution / iterate / precond of problem i mean what thip_solver_* mean (the final 1/tau scaling is applied to what
+ * solution and iterate return once the problem has terminated).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_smallbatch thip_smallbatch;
+typedef struct thip_smallbatch_info_t {
+    int32_t n_prob, threads;          /* problems; threads per workgroup (64, 256 or 1024, by shape) */
+    int32_t lds_bytes, live;          /* LDS of one workgroup; problems RUNNING as of the last poll */
+    size_t  arena_bytes;              /* the problems' state (iterates, Kahan terms, preconditioner) */
+    size_t  device_bytes;             /* everything this object allocated on the device */
+    size_t  device_bytes_all;         /* the same, summed over every thip_smallbatch alive in the process */
+    int64_t launches, workgroups;     /* issued by run / run_until_any since thip_smallbatch_init */
+} thip_smallbatch_info_t;
+/* the shape rules alone (needs no device): 0 and the LDS bytes / threads of one workgroup, or THIP_E_INVALID */
+int thip_smallbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                         size_t *host_lds_bytes, int *host_threads);
+int thip_smallbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                           const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                           const int64_t *host_seg_len, const thip_param *par, thip_smallbatch **out);
+int thip_smallbatch_set_param(thip_smallbatch *h, const thip_param *par);
+/* norms, preconditioner and the zero start iterate of every problem, on chip (one launch) */
+int thip_smallbatch_init(thip_smallbatch *h);
+/* every RUNNING problem advances by up to max_steps iterations (< 0: until all have stopped); host_status: n_prob entries or NULL */
+int thip_smallbatch_run(thip_smallbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+/* the same, back at the first poll that finds stopped a problem that was RUNNING when the call began */
+int thip_smallbatch_run_until_any(thip_smallbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_smallbatch_status(thip_smallbatch *h, int i, thip_status *host_status);
+int thip_smallbatch_solution(thip_smallbatch *h, int i, float *host_x, float *host_y);
+int thip_smallbatch_iterate(thip_smallbatch *h, int i, float *host_x, float *host_y);
+int thip_smallbatch_precond(thip_smallbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+/* slot i -- running or stopped -- takes new data (one problem each; dev_vec_b_rowabs may be NULL) and is initialised afresh;
+ * no other slot is touched */
+int thip_smallbatch_replace(thip_smallbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                            const float *dev_vec_b_rowabs);
+int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
+int thip_smallbatch_destroy(thip_smallbatch *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

@@ -112,6 +112,10 @@ int thip_test_gemv_multi(size_t m, size_t n, const float *mat, int nv, const flo
                          float *const *host_out_n, float *const *host_out_t, const int *host_stopped, int nj, int target_blocks,
                          int reps, float *host_ms);
 
+/* TEST HOOK: the workgroup size of a small batch (thip_smallbatch.hip): 64, 256 or 1024 threads, 0 = by shape.  Before
+ * thip_smallbatch_init. */
+int thip_test_smallbatch_force_threads(thip_smallbatch *h, int threads);
+
 #ifdef __cplusplus
 }
 #endif

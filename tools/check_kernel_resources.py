@@ -15,7 +15,12 @@ accumulators + NV x entries of x_T + the columns of A in flight -- and a spill i
 
     every dual_gemv_multi_k<NV, NJ, KU> instance: the same scratch and occupancy bounds (no SGPR bound: it has no service chain).
 
-usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi]"""
+The on-chip small-batch kernels (thip_smallbatch.hip, --family smallbatch) hold one whole problem per workgroup of up to 1024 threads:
+
+    smallbatch_k and smallbatch_init_k: no scratch at all, and >= 4 waves per SIMD (a 1024-thread workgroup is 16 waves on the
+    4 SIMDs of a CU: fewer and the launch fails, i.e. not even one workgroup per CU).
+
+usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch]"""
 import re
 import sys
 
@@ -69,9 +74,33 @@ def check_gemv_multi(res):
     return 0
 
 
+def check_smallbatch(res):
+    bad, seen = [], 0
+    for name, r in sorted(res.items()):
+        if not re.search(r"smallbatch(_init)?_k", name) or "scratch" not in r:
+            continue
+        seen += 1
+        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4
+        if "--report" in sys.argv or not ok:
+            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
+                                                                                 r["scratch"], r.get("occupancy", -1)))
+        if not ok:
+            bad.append(name)
+    if seen < 2:
+        print("check_kernel_resources: smallbatch_k / smallbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
+        return 2
+    if bad:
+        print("check_kernel_resources: FAILED for %s: scratch in use or < 4 waves/SIMD -- a 1024-thread workgroup of the on-chip "
+              "small-batch kernel no longer fits a CU (thip_smallbatch.hip)" % bad)
+        return 1
+    return 0
+
+
 def main():
     txt = open(sys.argv[1]).read()
     res = parse(txt)
+    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "smallbatch":
+        return check_smallbatch(res)
     if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "gemv_multi":
         return check_gemv_multi(res)
     bad, seen = [], 0

@@ -63,7 +63,14 @@ class BatchCounters(C.Structure):
                 ("live", C.c_int32), ("groups_now", C.c_int32)]
 
 
+class SmallBatchInfo(C.Structure):
+    _fields_ = [("n_prob", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("live", C.c_int32),
+                ("arena_bytes", C.c_size_t), ("device_bytes", C.c_size_t), ("device_bytes_all", C.c_size_t),
+                ("launches", C.c_int64), ("workgroups", C.c_int64)]
+
+
 BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
+SMALLBATCH_MAX_DIM, SMALLBATCH_MAX_AREA, SMALLBATCH_MAX_PROB, SMALLBATCH_LDS_MAX = 1024, 24576, 1048576, 163840
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -212,6 +219,21 @@ PROTOTYPES = {
     "thip_batch_counters": (_i, [_vp, C.POINTER(BatchCounters)]),
     "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
+    "thip_smallbatch_fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
+    "thip_smallbatch_create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                    C.POINTER(Param), C.POINTER(_vp)]),
+    "thip_smallbatch_set_param": (_i, [_vp, C.POINTER(Param)]),
+    "thip_smallbatch_init": (_i, [_vp]),
+    "thip_smallbatch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_smallbatch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_smallbatch_status": (_i, [_vp, _i, C.POINTER(Status)]),
+    "thip_smallbatch_solution": (_i, [_vp, _i, _vp, _vp]),
+    "thip_smallbatch_iterate": (_i, [_vp, _i, _vp, _vp]),
+    "thip_smallbatch_precond": (_i, [_vp, _i, _vp, _vp]),
+    "thip_smallbatch_replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "thip_smallbatch_info": (_i, [_vp, C.POINTER(SmallBatchInfo)]),
+    "thip_smallbatch_destroy": (_i, [_vp]),
+    "thip_test_smallbatch_force_threads": (_i, [_vp, _i]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "thip_prof_read_psd": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
