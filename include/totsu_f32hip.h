@@ -595,6 +595,47 @@ int thip_smallbatch_replace(thip_smallbatch *h, int i, const float *dev_mat_a, c
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
 int thip_smallbatch_destroy(thip_smallbatch *h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Many MID-SIZE problems, each with its own A, too big for LDS: A streamed per workgroup (thip_midbatch.hip).
+ * The interface is thip_smallbatch's, one for one: the same arrays (problem p's A at dev_mats_a + p m n, column-major, lda = m,
+ * read in place and never written), the same slots, polls, status / solution / iterate / precond and replace.  One launch gives
+ * ONE workgroup to each problem still running: it holds every vector of the iteration in the LDS of its CU, reads A twice per
+ * iteration from memory (the carried recurrence) and runs min(poll_every, steps left) whole iterations.
+ * Accepted: 1 <= m, n <= 4096 whose vectors fit LDS -- 4 (6208 + 8 n + 13 m) + roundup4(m) <= 163 840 bytes, which holds for every
+ * 8 n + 13 m <= 32 768 --, zero / nonnegative / second-order / rotated second-order segments that cover m, 1 <= n_prob <= 1 048 576.
+ * Everything else is THIP_E_INVALID before anything is allocated.  A problem's iterates do not depend on its index, its
+ * neighbours or how the iterations are cut into launches.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_midbatch thip_midbatch;
+typedef struct thip_midbatch_info_t {
+    int32_t n_prob, threads;          /* problems; threads per workgroup (256 or 1024, by shape) */
+    int32_t lds_bytes, live;          /* LDS of one workgroup; problems RUNNING as of the last poll */
+    size_t  arena_bytes;              /* the problems' state (iterates, Kahan terms, preconditioner, the carried products) */
+    size_t  device_bytes;             /* everything this object allocated on the device */
+    size_t  device_bytes_all;         /* the same, summed over every thip_midbatch alive in the process */
+    int64_t launches, workgroups;     /* issued by run / run_until_any since thip_midbatch_init */
+    int32_t load_bytes, reserved;     /* 16: every problem's A is read with 16-byte loads (m % 4 == 0, bases aligned); else 4 */
+    size_t  a_bytes_per_iter;         /* bytes of A read per problem-iteration: 2 m n 4 */
+} thip_midbatch_info_t;
+/* the shape rules alone (needs no device): 0 and the LDS bytes / threads of one workgroup, or THIP_E_INVALID */
+int thip_midbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                       size_t *host_lds_bytes, int *host_threads);
+int thip_midbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                         const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                         const int64_t *host_seg_len, const thip_param *par, thip_midbatch **out);
+int thip_midbatch_set_param(thip_midbatch *h, const thip_param *par);
+int thip_midbatch_init(thip_midbatch *h);
+int thip_midbatch_run(thip_midbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_midbatch_run_until_any(thip_midbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_midbatch_status(thip_midbatch *h, int i, thip_status *host_status);
+int thip_midbatch_solution(thip_midbatch *h, int i, float *host_x, float *host_y);
+int thip_midbatch_iterate(thip_midbatch *h, int i, float *host_x, float *host_y);
+int thip_midbatch_precond(thip_midbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_midbatch_replace(thip_midbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                          const float *dev_vec_b_rowabs);
+int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
+int thip_midbatch_destroy(thip_midbatch *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

@@ -116,6 +116,10 @@ int thip_test_gemv_multi(size_t m, size_t n, const float *mat, int nv, const flo
  * thip_smallbatch_init. */
 int thip_test_smallbatch_force_threads(thip_smallbatch *h, int threads);
 
+/* TEST HOOK: the workgroup size of a mid batch (thip_midbatch.hip): 256 or 1024 threads, 0 = by shape.  Before
+ * thip_midbatch_init. */
+int thip_test_midbatch_force_threads(thip_midbatch *h, int threads);
+
 #ifdef __cplusplus
 }
 #endif

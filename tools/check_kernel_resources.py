@@ -20,7 +20,12 @@ The on-chip small-batch kernels (thip_smallbatch.hip, --family smallbatch) hold 
     smallbatch_k and smallbatch_init_k: no scratch at all, and >= 4 waves per SIMD (a 1024-thread workgroup is 16 waves on the
     4 SIMDs of a CU: fewer and the launch fails, i.e. not even one workgroup per CU).
 
-usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch]"""
+The streamed mid-size batch (thip_midbatch.hip, --family midbatch) keeps a problem's vectors in LDS and streams its A, eight columns
+in flight per lane, with up to 1024 threads:
+
+    midbatch_k and midbatch_init_k: the same -- no scratch at all, and >= 4 waves per SIMD.
+
+usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch]"""
 import re
 import sys
 
@@ -96,11 +101,35 @@ def check_smallbatch(res):
     return 0
 
 
+def check_midbatch(res):
+    bad, seen = [], 0
+    for name, r in sorted(res.items()):
+        if not re.search(r"midbatch(_init)?_k", name) or "scratch" not in r:
+            continue
+        seen += 1
+        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4
+        if "--report" in sys.argv or not ok:
+            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
+                                                                                 r["scratch"], r.get("occupancy", -1)))
+        if not ok:
+            bad.append(name)
+    if seen < 2:
+        print("check_kernel_resources: midbatch_k / midbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
+        return 2
+    if bad:
+        print("check_kernel_resources: FAILED for %s: scratch in use or < 4 waves/SIMD -- a 1024-thread workgroup of the streamed "
+              "mid-size batch kernel no longer fits a CU (thip_midbatch.hip)" % bad)
+        return 1
+    return 0
+
+
 def main():
     txt = open(sys.argv[1]).read()
     res = parse(txt)
     if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "smallbatch":
         return check_smallbatch(res)
+    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "midbatch":
+        return check_midbatch(res)
     if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "gemv_multi":
         return check_gemv_multi(res)
     bad, seen = [], 0

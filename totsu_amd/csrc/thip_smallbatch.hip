@@ -13,32 +13,18 @@
 //
 // Sums: per-thread fmaf chains, DPP wave sums, then the waves' values through LDS added in wave order (f64).  No atomics: a
 // problem's result is a function of (its data, the workgroup size) alone -- not of its index, its neighbours or the launch.
-#include "thip_common.h"
+//
+// The status block, the slots, the device functions that do not touch A and the host machinery are shared with the streamed
+// mid-size batch (thip_midbatch.hip): thip_ownbatch.h.
+#include "thip_ownbatch.h"
 
-#include <algorithm>
 #include <mutex>
-#include <string.h>
-#include <vector>
 
 using namespace thip;
 
 namespace {
 
-constexpr size_t SB_MAX_DIM = 1024, SB_MAX_AREA = 24576, SB_MAX_PROB = 1048576, SB_LDS_MAX = 163840;
-
-struct SbStatus {                // 64 bytes, one per problem; the host copies all of them in one transfer
-    int       stop;              // != 0: the problem's workgroup returns at entry
-    int       state;             // THIP_ST_*
-    int       kind, pad;
-    long long iter;              // index of the iteration being / last executed
-    float     cri[3];
-    float     tau, kappa, norm_b, norm_c;
-    float     t_tau, s_kappa;    // preconditioner entries of tau / kappa
-    float     r_tau;
-};
-static_assert(sizeof(SbStatus) == 64, "SbStatus is copied as an array");
-
-struct SbSlot { const float *a, *b, *c, *rowabs; };      // where problem p's data lives (rowabs may be NULL: |b|)
+constexpr size_t SB_MAX_DIM = 1024, SB_MAX_AREA = 24576, SB_LDS_MAX = OB_LDS_MAX;
 
 struct SbArgs {
     int n, m, lda, n_cones, comp, steps;
@@ -70,27 +56,6 @@ struct SbMap {
 };
 __host__ __device__ inline int sb_lda(int m) { return m | 1; }
 __host__ __device__ inline size_t sb_stride(size_t n, size_t m) { return 5 * n + 9 * m; }
-
-// Q sums over the workgroup; every thread gets every result.  sh: 64 floats of LDS
-template <int Q>
-__device__ __forceinline__ void block_sums(float *q, float *sh)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < Q; ++k) q[k] = wave_sum_dpp(q[k]);
-    __syncthreads();                        // (the previous sums have been read)
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < Q; ++k) sh[w * 4 + k] = q[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < Q; ++k) {
-        double a = 0.0;
-        for (int j = 0; j < nw; ++j) a += (double)sh[j * 4 + k];
-        q[k] = (float)a;
-    }
-}
 
 // A (global, column-major, lda = m, contiguous) -> LDS with leading dimension lda.  16-byte loads when the base allows them
 __device__ __forceinline__ void load_a(const float *__restrict__ src, float *A, int m, int n, int lda)
@@ -167,75 +132,6 @@ __device__ __forceinline__ void products(const float *A, int lda, int m, int n, 
     product_finish(m, h, red);
     product_finish(n, g, red + blockDim.x);
     __syncthreads();
-}
-
-// comp_add of thip_solver_kernels.inc
-__device__ __forceinline__ float sb_comp_add(float x, float inc, float *k, int i, bool comp)
-{
-    if (!comp) return x + inc;
-    const float y = inc - k[i];
-    const float t = x + y;
-    k[i] = (t - x) - y;
-    return t;
-}
-
-// soc_k of thip_cone.hip for one cone by one wave, with rx <- rx - 2 x folded in (cone_soc.rs:38-65, cone_rotsoc.rs:38-65)
-__device__ __forceinline__ void sb_soc(float *x, float *rx, int beg, int end, int rotated, int lane)
-{
-    const int len = end - beg;
-    if (len <= 0) return;
-    const float fsqrt2 = sqrtf(2.0f);
-    if (rotated && len == 1) {
-        if (lane == 0) {
-            const float v = fmaxf(x[beg], 0.0f);
-            x[beg] = v;
-            rx[beg] = rx[beg] - 2.0f * v;
-        }
-        return;
-    }
-    float s0, v1 = 0.0f;
-    if (rotated) {
-        const float r = x[beg], s = x[beg + 1];
-        s0 = (r + s) / fsqrt2;
-        v1 = (r - s) / fsqrt2;
-    } else {
-        s0 = x[beg];
-    }
-    double acc = 0.0;
-    for (int i = beg + 1 + lane; i < end; i += 64) {
-        const double t = (double)((rotated && i == beg + 1) ? v1 : x[i]);
-        acc += t * t;
-    }
-    const float norm_v = (float)sqrt(wave_sum_d(acc));
-    float f, s_new;
-    if (norm_v <= -s0) { f = 0.0f; s_new = 0.0f; }
-    else if (norm_v <= s0) { f = 1.0f; s_new = s0; }
-    else { f = (1.0f + s0 / norm_v) / 2.0f; s_new = (norm_v + s0) / 2.0f; }
-    if (!rotated) {
-        if (lane == 0) {
-            x[beg] = s_new;
-            rx[beg] = rx[beg] - 2.0f * s_new;
-        }
-        for (int i = beg + 1 + lane; i < end; i += 64) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
-            x[i] = nv;
-            rx[i] = rx[i] - 2.0f * nv;
-        }
-    } else {
-        const float v1n = f * v1;
-        for (int i = beg + 2 + lane; i < end; i += 64) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
-            x[i] = nv;
-            rx[i] = rx[i] - 2.0f * nv;
-        }
-        if (lane == 0) {
-            const float a = (s_new + v1n) / fsqrt2, b = (s_new - v1n) / fsqrt2;
-            x[beg] = a;
-            x[beg + 1] = b;
-            rx[beg] = rx[beg] - 2.0f * a;
-            rx[beg + 1] = rx[beg + 1] - 2.0f * b;
-        }
-    }
 }
 
 extern __shared__ float sb_lds[];
@@ -450,17 +346,10 @@ __global__ __launch_bounds__(1024) void smallbatch_k(const SbArgs a)
     }
 }
 
-__global__ void smallbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,
-                                   size_t m, size_t n)
-{
-    for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < (size_t)n_prob; p += (size_t)gridDim.x * blockDim.x) {
-        SbSlot s;
-        s.a = a + p * m * n; s.b = b + p * m; s.c = c + p * n; s.rowabs = rowabs ? rowabs + p * m : nullptr;
-        slots[p] = s;
-    }
-}
-
 size_t g_sb_bytes = 0;                      // device memory held by every thip_smallbatch of the process
+
+const ObText SB_TEXT = { "small batch not initialised", "null small batch", "a small batch holds 1 .. 1048576 problems",
+                         "a small batch takes no PSD segment" };
 
 int sb_threads_for(size_t n, size_t m)
 {
@@ -475,52 +364,14 @@ int sb_check(size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const in
     if (m < 1 || m > SB_MAX_DIM || n < 1 || n > SB_MAX_DIM)
         return fail(THIP_E_INVALID, "a small batch takes 1 <= m <= 1024 and 1 <= n <= 1024", __FILE__, __LINE__);
     if (m * n > SB_MAX_AREA) return fail(THIP_E_INVALID, "a small batch takes m * n <= 24576 (96 KiB of A on chip)", __FILE__, __LINE__);
-    if (n_seg && (!seg_type || !seg_len)) return fail(THIP_E_INVALID, "null cone segments", __FILE__, __LINE__);
-    int64_t off = 0;
-    if (cls) cls->assign(m, 2);
-    for (size_t i = 0; i < n_seg; ++i) {
-        const int64_t l = seg_len[i];
-        if (l < 0 || seg_type[i] < 0 || seg_type[i] > THIP_CONE_PSD) return fail(THIP_E_INVALID, "bad cone segment", __FILE__, __LINE__);
-        if (seg_type[i] == THIP_CONE_PSD) return fail(THIP_E_INVALID, "a small batch takes no PSD segment", __FILE__, __LINE__);
-        if (off + l > (int64_t)m) return fail(THIP_E_INVALID, "cone segments do not cover m rows", __FILE__, __LINE__);
-        if (seg_type[i] == THIP_CONE_ZERO || seg_type[i] == THIP_CONE_RPOS) {
-            if (cls) for (int64_t r = 0; r < l; ++r) (*cls)[(size_t)(off + r)] = seg_type[i] == THIP_CONE_ZERO ? 0 : 1;
-        } else if (cones) {
-            cones->push_back((int)off); cones->push_back((int)(off + l)); cones->push_back(seg_type[i] == THIP_CONE_ROTSOC ? 1 : 0);
-        }
-        off += l;
-    }
-    if ((size_t)off != m) return fail(THIP_E_INVALID, "cone segments do not cover m rows", __FILE__, __LINE__);
-    return 0;
+    return ob_segments(SB_TEXT, m, n_seg, seg_type, seg_len, cones, cls);
 }
 
 }  // namespace
 
-struct thip_smallbatch {
-    size_t n = 0, m = 0, n_prob = 0;
-    thip_param par{};
-    std::vector<int> cones;
-    std::vector<unsigned char> cls;
-    int threads = 0, forced = 0;
-    size_t lds = 0, stride = 0, bytes = 0;
-    float *arena = nullptr;
-    SbStatus *dst = nullptr, *hst = nullptr;
-    SbSlot *slots = nullptr;
-    int *live_dev = nullptr, *cones_dev = nullptr;
-    unsigned char *cls_dev = nullptr;
-    std::vector<int> live;
-    bool inited = false;
-    int64_t launches = 0, workgroups = 0;
-};
+struct thip_smallbatch : OwnBatch {};
 
 namespace {
-
-int sb_alloc(thip_smallbatch *h, void **p, size_t bytes)
-{
-    THIP_TRY(hipMalloc(p, bytes));
-    h->bytes += bytes; g_sb_bytes += bytes;
-    return 0;
-}
 
 int sb_attr()
 {
@@ -536,13 +387,13 @@ int sb_attr()
     return 0;
 }
 
-void sb_plan(thip_smallbatch *h)
+void sb_plan(OwnBatch *h)
 {
     h->threads = h->forced ? h->forced : sb_threads_for(h->n, h->m);
     h->lds = SbMap((int)h->n, (int)h->m, sb_lda((int)h->m), h->threads).bytes((int)h->m);
 }
 
-SbArgs sb_args(const thip_smallbatch *h)
+SbArgs sb_args(const OwnBatch *h)
 {
     SbArgs a{};
     a.n = (int)h->n; a.m = (int)h->m; a.lda = sb_lda((int)h->m); a.n_cones = (int)(h->cones.size() / 3);
@@ -552,88 +403,23 @@ SbArgs sb_args(const thip_smallbatch *h)
     return a;
 }
 
-void sb_status_out(const SbStatus &s, thip_status *o)
+int sb_launch_init(OwnBatch *h, int first, int count)
 {
-    o->state = s.state; o->iter = s.iter; o->kind = s.kind;
-    o->cri[0] = s.cri[0]; o->cri[1] = s.cri[1]; o->cri[2] = s.cri[2];
-    o->tau = s.tau; o->kappa = s.kappa; o->norm_b = s.norm_b; o->norm_c = s.norm_c;
-}
-
-// every status block in one transfer; the live set from it
-int sb_poll(thip_smallbatch *h, thip_status *host_status)
-{
-    hipStream_t st = ctx().stream;
-    THIP_TRY(hipMemcpyAsync(h->hst, h->dst, h->n_prob * sizeof(SbStatus), hipMemcpyDeviceToHost, st));
-    THIP_TRY(hipStreamSynchronize(st));
-    h->live.clear();
-    for (size_t p = 0; p < h->n_prob; ++p) {
-        if (h->hst[p].state == THIP_ST_RUNNING) h->live.push_back((int)p);
-        if (host_status) sb_status_out(h->hst[p], host_status + p);
-    }
-    return 0;
-}
-
-int sb_init_range(thip_smallbatch *h, int first, int count)
-{
-    hipStream_t st = ctx().stream;
     SbArgs a = sb_args(h);
     a.first = first;
-    hipLaunchKernelGGL(smallbatch_init_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, st, a);
+    hipLaunchKernelGGL(smallbatch_init_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
 
-int sb_run_impl(thip_smallbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status, bool until_any)
+int sb_launch_run(OwnBatch *h, int count, int steps, const int *live)
 {
-    THIP_NEED_INIT();
-    if (!h || !h->inited) return fail(THIP_E_INVALID, "small batch not initialised", __FILE__, __LINE__);
-    if (poll_every <= 0) poll_every = 16;
-    hipStream_t st = ctx().stream;
-    THIP_RC(sb_poll(h, host_status));
-    const size_t live0 = h->live.size();
-    int64_t done = 0;
-    while (!h->live.empty() && (max_steps < 0 || done < max_steps) && !(until_any && h->live.size() < live0)) {
-        int64_t batch = poll_every;
-        if (max_steps >= 0 && done + batch > max_steps) batch = max_steps - done;
-        if (batch > 1 << 20) batch = 1 << 20;
-        const bool all = h->live.size() == h->n_prob;          // (then workgroup k serves problem k: no list)
-        if (!all) THIP_TRY(hipMemcpyAsync(h->live_dev, h->live.data(), h->live.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        SbArgs a = sb_args(h);
-        a.steps = (int)batch;
-        a.live = all ? nullptr : h->live_dev;
-        hipLaunchKernelGGL(smallbatch_k, dim3((unsigned)h->live.size()), dim3((unsigned)h->threads), h->lds, st, a);
-        THIP_LAUNCH_CHECK();
-        h->launches += 1;
-        h->workgroups += (int64_t)h->live.size();
-        done += batch;
-        THIP_RC(sb_poll(h, host_status));       // (synchronises: the list the launch read is the host's to rewrite)
-    }
+    SbArgs a = sb_args(h);
+    a.steps = steps;
+    a.live = live;
+    hipLaunchKernelGGL(smallbatch_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
+    THIP_LAUNCH_CHECK();
     return 0;
-}
-
-int sb_member(thip_smallbatch *h, int i)
-{
-    if (!h || !h->inited) return fail(THIP_E_INVALID, "small batch not initialised", __FILE__, __LINE__);
-    if (i < 0 || (size_t)i >= h->n_prob) return fail(THIP_E_INVALID, "no such problem", __FILE__, __LINE__);
-    return 0;
-}
-
-// problem i's status block, fresh from the device
-int sb_status_one(thip_smallbatch *h, int i)
-{
-    hipStream_t st = ctx().stream;
-    THIP_TRY(hipMemcpyAsync(h->hst + i, h->dst + i, sizeof(SbStatus), hipMemcpyDeviceToHost, st));
-    THIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// the final 1/tau scaling of a terminated iterate (solver.rs:397-400; finalize_k), applied to the copy that is read
-void sb_finalize(const SbStatus &s, float *x, size_t n)
-{
-    const bool scale = (s.kind == 0) && (s.state == THIP_ST_OK || s.state == THIP_ST_EXCESS_ITER);
-    if (!scale || !x) return;
-    const float rt = 1.0f / s.tau;
-    for (size_t i = 0; i < n; ++i) x[i] = rt * x[i];
 }
 
 }  // namespace
@@ -656,10 +442,7 @@ int thip_smallbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_s
 int thip_smallbatch_destroy(thip_smallbatch *h)
 {
     if (!h) return 0;
-    if (ctx().inited) hipStreamSynchronize(ctx().stream);
-    hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
-    if (h->hst) hipHostFree(h->hst);
-    g_sb_bytes -= h->bytes;
+    ob_destroy(h);
     delete h;
     return 0;
 }
@@ -671,13 +454,9 @@ int thip_smallbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_m
     if (!out) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
     *out = nullptr;
     THIP_NEED_INIT();
-    if (!par || !dev_mats_a || !dev_vecs_b || !dev_vecs_c) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    if (n_prob < 1 || n_prob > SB_MAX_PROB) return fail(THIP_E_INVALID, "a small batch holds 1 .. 1048576 problems", __FILE__, __LINE__);
-    if (par->state_arith != THIP_STATE_COMPENSATED && par->state_arith != THIP_STATE_PLAIN)
-        return fail(THIP_E_INVALID, "bad thip_param.state_arith", __FILE__, __LINE__);
-    if (((uintptr_t)dev_mats_a | (uintptr_t)dev_vecs_b | (uintptr_t)dev_vecs_c | (uintptr_t)dev_vecs_b_rowabs) & 3u)
-        return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
+    THIP_RC(ob_create_args(SB_TEXT, n_prob, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs, par));
     thip_smallbatch *h = new thip_smallbatch();
+    h->text = &SB_TEXT; h->total = &g_sb_bytes; h->launch_init = sb_launch_init; h->launch_run = sb_launch_run;
     // every refusal comes before the first allocation
     int rc = sb_check(n, m, n_seg, host_seg_type, host_seg_len, &h->cones, &h->cls);
     if (rc == 0) rc = thip_smallbatch_fits(n, m, n_seg, host_seg_type, host_seg_len, nullptr, nullptr);
@@ -686,137 +465,58 @@ int thip_smallbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_m
     h->par = *par;
     h->stride = sb_stride(n, m);
     sb_plan(h);
-    auto build = [&]() -> int {
-        hipStream_t st = ctx().stream;
-        THIP_RC(sb_attr());
-        THIP_RC(sb_alloc(h, (void **)&h->arena, h->stride * n_prob * sizeof(float)));
-        THIP_RC(sb_alloc(h, (void **)&h->dst, n_prob * sizeof(SbStatus)));
-        THIP_RC(sb_alloc(h, (void **)&h->slots, n_prob * sizeof(SbSlot)));
-        THIP_RC(sb_alloc(h, (void **)&h->live_dev, n_prob * sizeof(int)));
-        THIP_RC(sb_alloc(h, (void **)&h->cls_dev, (m + 3) & ~(size_t)3));
-        THIP_RC(sb_alloc(h, (void **)&h->cones_dev, std::max<size_t>(h->cones.size(), 3) * sizeof(int)));
-        THIP_TRY(hipHostMalloc((void **)&h->hst, n_prob * sizeof(SbStatus), hipHostMallocDefault));
-        THIP_TRY(hipMemcpy(h->cls_dev, h->cls.data(), m, hipMemcpyHostToDevice));
-        if (!h->cones.empty()) THIP_TRY(hipMemcpy(h->cones_dev, h->cones.data(), h->cones.size() * sizeof(int), hipMemcpyHostToDevice));
-        THIP_TRY(hipMemsetAsync(h->dst, 0, n_prob * sizeof(SbStatus), st));
-        hipLaunchKernelGGL(smallbatch_slots_k, dim3(grid_for(n_prob, 256, 1024)), dim3(256), 0, st, h->slots, (int)n_prob, dev_mats_a,
-                           dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs, m, n);
-        THIP_LAUNCH_CHECK();
-        return 0;
-    };
-    rc = build();
+    rc = sb_attr();
+    if (rc == 0) rc = ob_build(h, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs);
     if (rc != 0) { thip_smallbatch_destroy(h); return rc; }
     *out = h;
     return 0;
 }
 
-int thip_smallbatch_set_param(thip_smallbatch *h, const thip_param *par)
-{
-    if (!h || !par) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    if (par->state_arith != THIP_STATE_COMPENSATED && par->state_arith != THIP_STATE_PLAIN)
-        return fail(THIP_E_INVALID, "bad thip_param.state_arith", __FILE__, __LINE__);
-    h->par = *par;
-    return 0;
-}
+int thip_smallbatch_set_param(thip_smallbatch *h, const thip_param *par) { return ob_set_param(h, par); }
 
-int thip_smallbatch_init(thip_smallbatch *h)
-{
-    THIP_NEED_INIT();
-    if (!h) return fail(THIP_E_INVALID, "null small batch", __FILE__, __LINE__);
-    THIP_RC(sb_init_range(h, 0, (int)h->n_prob));
-    h->launches = 0; h->workgroups = 0;
-    h->inited = true;
-    return sb_poll(h, nullptr);
-}
+int thip_smallbatch_init(thip_smallbatch *h) { return ob_init(h, SB_TEXT); }
 
 int thip_smallbatch_run(thip_smallbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
 {
-    return sb_run_impl(h, max_steps, poll_every, host_status, false);
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_run(h, max_steps, poll_every, host_status, false);
 }
 
 int thip_smallbatch_run_until_any(thip_smallbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
 {
-    return sb_run_impl(h, max_steps, poll_every, host_status, true);
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_run(h, max_steps, poll_every, host_status, true);
 }
 
 int thip_smallbatch_status(thip_smallbatch *h, int i, thip_status *host_status)
 {
-    THIP_NEED_INIT();
-    THIP_RC(sb_member(h, i));
-    if (!host_status) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    THIP_RC(sb_status_one(h, i));
-    sb_status_out(h->hst[i], host_status);
-    return 0;
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_status(h, i, host_status);
 }
 
 int thip_smallbatch_solution(thip_smallbatch *h, int i, float *host_x, float *host_y)
 {
-    THIP_NEED_INIT();
-    THIP_RC(sb_member(h, i));
-    THIP_RC(sb_status_one(h, i));
-    const float *ar = h->arena + (size_t)i * h->stride;
-    if (host_x) THIP_RC(thip_d2h(host_x, ar, h->n));
-    if (host_y) THIP_RC(thip_d2h(host_y, ar + 4 * h->n, h->m));
-    sb_finalize(h->hst[i], host_x, h->n);
-    sb_finalize(h->hst[i], host_y, h->m);
-    return 0;
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_solution(h, i, host_x, host_y);
 }
 
 int thip_smallbatch_iterate(thip_smallbatch *h, int i, float *host_x, float *host_y)
 {
-    THIP_NEED_INIT();
-    THIP_RC(sb_member(h, i));
-    THIP_RC(sb_status_one(h, i));
-    const size_t n = h->n, m = h->m;
-    const float *ar = h->arena + (size_t)i * h->stride;      // xx u kx ku | xy xs v ..
-    if (host_x) {
-        THIP_RC(thip_d2h(host_x, ar, n));
-        THIP_RC(thip_d2h(host_x + n, ar + 4 * n, 2 * m));
-        host_x[n + m + m] = h->hst[i].tau;
-        sb_finalize(h->hst[i], host_x, n + m);              // (x_x and x_y are adjacent in the copy)
-    }
-    if (host_y) {
-        THIP_RC(thip_d2h(host_y, ar + n, n));
-        THIP_RC(thip_d2h(host_y + n, ar + 4 * n + 2 * m, m));
-        host_y[n + m] = h->hst[i].kappa;
-    }
-    return 0;
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_iterate(h, i, host_x, host_y);
 }
 
 int thip_smallbatch_precond(thip_smallbatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
 {
-    THIP_NEED_INIT();
-    THIP_RC(sb_member(h, i));
-    THIP_RC(sb_status_one(h, i));
-    const size_t n = h->n, m = h->m;
-    const float *k = h->arena + (size_t)i * h->stride + 4 * n + 6 * m;      // Tx Ty Ts Sv
-    if (host_dp_tau) {
-        THIP_RC(thip_d2h(host_dp_tau, k, n + 2 * m));
-        host_dp_tau[n + 2 * m] = h->hst[i].t_tau;
-    }
-    if (host_dp_sigma) {
-        THIP_RC(thip_d2h(host_dp_sigma, k, n));                             // sigma_n = tau_x
-        THIP_RC(thip_d2h(host_dp_sigma + n, k + n + 2 * m, m));
-        host_dp_sigma[n + m] = h->hst[i].s_kappa;
-    }
-    return 0;
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_precond(h, i, host_dp_tau, host_dp_sigma);
 }
 
 int thip_smallbatch_replace(thip_smallbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                             const float *dev_vec_b_rowabs)
 {
-    THIP_NEED_INIT();
-    THIP_RC(sb_member(h, i));
-    if (!dev_mat_a || !dev_vec_b || !dev_vec_c) return fail(THIP_E_INVALID, "null A, b or c", __FILE__, __LINE__);
-    if (((uintptr_t)dev_mat_a | (uintptr_t)dev_vec_b | (uintptr_t)dev_vec_c | (uintptr_t)dev_vec_b_rowabs) & 3u)
-        return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
-    const SbSlot s{ dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs };
-    THIP_TRY(hipMemcpyAsync(h->slots + i, &s, sizeof(SbSlot), hipMemcpyHostToDevice, ctx().stream));
-    THIP_TRY(hipStreamSynchronize(ctx().stream));           // (s is a local)
-    THIP_RC(sb_init_range(h, i, 1));
-    const auto at = std::lower_bound(h->live.begin(), h->live.end(), i);
-    if (at == h->live.end() || *at != i) h->live.insert(at, i);
-    return sb_status_one(h, i);
+    if (!h) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SB_TEXT.uninit, __FILE__, __LINE__); }
+    return ob_replace(h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs);
 }
 
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info)

@@ -17,8 +17,7 @@ from .fused import DeviceBuffer, FusedResult, _c_param
 from .solver import SolverError, SolverParam
 
 
-def fits(n, m, seg_type, seg_len):
-    """the shape rules alone (thip_smallbatch_fits; needs no GPU): (lds_bytes, threads) of one workgroup, or ValueError"""
+def _fits(prefix, n, m, seg_type, seg_len):
     st = np.ascontiguousarray(seg_type, dtype=np.int32)
     sl = np.ascontiguousarray(seg_len, dtype=np.int64)
     if st.size != sl.size:
@@ -27,8 +26,8 @@ def fits(n, m, seg_type, seg_len):
         raise ValueError("negative shape (n = %r, m = %r)" % (n, m))
     lds, thr = C.c_size_t(), C.c_int()
     try:
-        lib.thip_smallbatch_fits(int(n), int(m), st.size, st.ctypes.data_as(C.POINTER(C.c_int32)), sl.ctypes.data_as(C.POINTER(C.c_int64)),
-                                 C.byref(lds), C.byref(thr))
+        getattr(lib, prefix + "fits")(int(n), int(m), st.size, st.ctypes.data_as(C.POINTER(C.c_int32)), sl.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      C.byref(lds), C.byref(thr))
     except _lib.ThipError as e:
         if e.code == _lib.E_INVALID:
             raise ValueError(str(e)) from None
@@ -36,7 +35,18 @@ def fits(n, m, seg_type, seg_len):
     return lds.value, thr.value
 
 
+def fits(n, m, seg_type, seg_len):
+    """the shape rules alone (thip_smallbatch_fits; needs no GPU): (lds_bytes, threads) of one workgroup, or ValueError"""
+    return _fits("thip_smallbatch_", n, m, seg_type, seg_len)
+
+
 class SmallBatchSolver:
+    # what a family of own-A batches differs in (MidBatchSolver overrides these)
+    _prefix, _force_hook, _what, _Info = "thip_smallbatch_", "thip_test_smallbatch_force_threads", "small", _lib.SmallBatchInfo
+
+    def _c(self, name):
+        return getattr(lib, self._prefix + name)
+
     def __init__(self, n, m, mats_a, vecs_b, vecs_c, seg_type, seg_len, param=None, vecs_b_rowabs=None, force_threads=None):
         """mats_a: (P, m * n) -- every A column-major; vecs_b: (P, m); vecs_c: (P, n); vecs_b_rowabs: (P, m) or None (|b|) -- host
         arrays (uploaded) or DeviceBuffers holding the same, problem after problem.  force_threads: test hook (64, 256, 1024)."""
@@ -44,10 +54,10 @@ class SmallBatchSolver:
         self._owned = []
         self._slot_owned = {}
         self.n, self.m = int(n), int(m)
-        fits(self.n, self.m, seg_type, seg_len)               # every shape refusal, before anything is uploaded
+        _fits(self._prefix, self.n, self.m, seg_type, seg_len)      # every shape refusal, before anything is uploaded
         self.n_prob = self._count(vecs_b, self.m, "vecs_b")
         if not 1 <= self.n_prob <= _lib.SMALLBATCH_MAX_PROB:
-            raise ValueError("a small batch holds 1 .. %d problems, not %d" % (_lib.SMALLBATCH_MAX_PROB, self.n_prob))
+            raise ValueError("a %s batch holds 1 .. %d problems, not %d" % (self._what, _lib.SMALLBATCH_MAX_PROB, self.n_prob))
         for name, arr, per in (("mats_a", mats_a, self.m * self.n), ("vecs_b", vecs_b, self.m), ("vecs_c", vecs_c, self.n),
                                ("vecs_b_rowabs", vecs_b_rowabs, self.m)):
             if arr is None and name == "vecs_b_rowabs":
@@ -65,14 +75,14 @@ class SmallBatchSolver:
             self.vecs_b_rowabs = None if vecs_b_rowabs is None else self._dev(vecs_b_rowabs)
             par = _c_param(self.param)
             h = C.c_void_p()
-            lib.thip_smallbatch_create(self.n, self.m, self.n_prob, self.mats_a.ptr, self.vecs_b.ptr, self.vecs_c.ptr,
-                                       None if self.vecs_b_rowabs is None else self.vecs_b_rowabs.ptr, len(self._st),
-                                       self._st.ctypes.data_as(C.POINTER(C.c_int32)), self._sl.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       C.byref(par), C.byref(h))
+            self._c("create")(self.n, self.m, self.n_prob, self.mats_a.ptr, self.vecs_b.ptr, self.vecs_c.ptr,
+                              None if self.vecs_b_rowabs is None else self.vecs_b_rowabs.ptr, len(self._st),
+                              self._st.ctypes.data_as(C.POINTER(C.c_int32)), self._sl.ctypes.data_as(C.POINTER(C.c_int64)),
+                              C.byref(par), C.byref(h))
             self.h = h
             if force_threads is not None:
-                lib.thip_test_smallbatch_force_threads(self.h, int(force_threads))
-            lib.thip_smallbatch_init(self.h)
+                getattr(lib, self._force_hook)(self.h, int(force_threads))
+            self._c("init")(self.h)
         except Exception:
             self.destroy()
             raise
@@ -105,17 +115,17 @@ class SmallBatchSolver:
                 raise ValueError("problem %d: mat_a holds %d entries where m * n = %d are needed" % (k, np.asarray(d.mat_a).size, d0.n * d0.m))
         return denses
 
-    @staticmethod
-    def from_dense(denses, param=None, **kw):
+    @classmethod
+    def from_dense(cls, denses, param=None, **kw):
         """one problem per Prob*.dense() of the list; ValueError when their shapes or cone layouts differ"""
-        denses = SmallBatchSolver.check_same_layout(denses)
+        denses = cls.check_same_layout(denses)
         d0 = denses[0]
         f = np.float32
         a = np.stack([np.asarray(d.mat_a, f).ravel() for d in denses])
         b = np.stack([np.asarray(d.vec_b, f).ravel() for d in denses]).reshape(len(denses), d0.m)
         c = np.stack([np.asarray(d.vec_c, f).ravel() for d in denses]).reshape(len(denses), d0.n)
         r = None if d0.vec_b_rowabs is None else np.stack([np.asarray(d.vec_b_rowabs, f).ravel() for d in denses])
-        return SmallBatchSolver(d0.n, d0.m, a, b, c, d0.seg_type, d0.seg_len, param, vecs_b_rowabs=r, **kw)
+        return cls(d0.n, d0.m, a, b, c, d0.seg_type, d0.seg_len, param, vecs_b_rowabs=r, **kw)
 
     def _dev(self, a, owned=None):
         if isinstance(a, DeviceBuffer):
@@ -142,7 +152,7 @@ class SmallBatchSolver:
         try:
             da, db, dc = self._dev(mat_a, own), self._dev(vec_b, own), self._dev(vec_c, own)
             dr = None if vec_b_rowabs is None else self._dev(vec_b_rowabs, own)
-            lib.thip_smallbatch_replace(self.h, i, da.ptr, db.ptr, dc.ptr, None if dr is None else dr.ptr)
+            self._c("replace")(self.h, i, da.ptr, db.ptr, dc.ptr, None if dr is None else dr.ptr)
         except Exception:
             for d in own:
                 d.free()
@@ -153,12 +163,12 @@ class SmallBatchSolver:
 
     def reinit(self):
         """thip_smallbatch_init again: a fresh solve of every problem"""
-        lib.thip_smallbatch_init(self.h)
+        self._c("init")(self.h)
 
     def set_param(self, param):
         self.param = param
         par = _c_param(param)
-        lib.thip_smallbatch_set_param(self.h, C.byref(par))
+        self._c("set_param")(self.h, C.byref(par))
 
     def _run(self, fn, max_steps, poll_every):
         st = (_lib.Status * self.n_prob)()
@@ -167,39 +177,39 @@ class SmallBatchSolver:
 
     def run(self, max_steps=-1, poll_every=16):
         """every running problem advances by up to max_steps iterations; returns the list of the problems' FusedResult"""
-        return self._run(lib.thip_smallbatch_run, max_steps, poll_every)
+        return self._run(self._c("run"), max_steps, poll_every)
 
     def run_until_any(self, max_steps=-1, poll_every=16):
         """run(), but back at the first poll that finds stopped a problem that was running when the call began"""
-        return self._run(lib.thip_smallbatch_run_until_any, max_steps, poll_every)
+        return self._run(self._c("run_until_any"), max_steps, poll_every)
 
     def status(self, i):
         st = _lib.Status()
-        lib.thip_smallbatch_status(self.h, int(i), C.byref(st))
+        self._c("status")(self.h, int(i), C.byref(st))
         return FusedResult(st)
 
     def solution(self, i):
         x = np.empty(self.n, dtype=np.float32)
         y = np.empty(self.m, dtype=np.float32)
-        lib.thip_smallbatch_solution(self.h, int(i), x.ctypes.data, y.ctypes.data)
+        self._c("solution")(self.h, int(i), x.ctypes.data, y.ctypes.data)
         return x, y
 
     def iterate(self, i):
         x = np.empty(self.n + 2 * self.m + 1, dtype=np.float32)
         y = np.empty(self.n + self.m + 1, dtype=np.float32)
-        lib.thip_smallbatch_iterate(self.h, int(i), x.ctypes.data, y.ctypes.data)
+        self._c("iterate")(self.h, int(i), x.ctypes.data, y.ctypes.data)
         return x, y
 
     def precond(self, i):
         t = np.empty(self.n + 2 * self.m + 1, dtype=np.float32)
         s = np.empty(self.n + self.m + 1, dtype=np.float32)
-        lib.thip_smallbatch_precond(self.h, int(i), t.ctypes.data, s.ctypes.data)
+        self._c("precond")(self.h, int(i), t.ctypes.data, s.ctypes.data)
         return t, s
 
     def info(self):
-        o = _lib.SmallBatchInfo()
-        lib.thip_smallbatch_info(self.h, C.byref(o))
-        return {k: getattr(o, k) for k, _ in _lib.SmallBatchInfo._fields_}
+        o = self._Info()
+        self._c("info")(self.h, C.byref(o))
+        return {k: getattr(o, k) for k, _ in self._Info._fields_ if k != "reserved"}
 
     def solve(self, poll_every=16):
         """Solver::solve semantics per problem: the list of (x, y), or a SolverError for a problem that did not converge"""
@@ -216,7 +226,7 @@ class SmallBatchSolver:
 
     def destroy(self):
         if getattr(self, "h", None) is not None:
-            lib.thip_smallbatch_destroy(self.h)
+            self._c("destroy")(self.h)
             self.h = None
         for d in getattr(self, "_owned", []) + [d for own in getattr(self, "_slot_owned", {}).values() for d in own]:
             d.free()
