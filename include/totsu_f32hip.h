@@ -636,6 +636,47 @@ int thip_midbatch_replace(thip_midbatch *h, int i, const float *dev_mat_a, const
 int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Many small SDPs (or mixed programs with PSD blocks), each with its own A: the mid batch's iteration with every PSD cone projected
+ * on chip by the problem's own workgroup, between the two passes over A (thip_sdpbatch.hip).  The interface is
+ * thip_midbatch's, one for one, and a layout without PSD segments gives thip_midbatch's iterates bit for bit.
+ * Accepted: 1 <= m, n <= 4096, segments of all five cones that cover m, every PSD segment of k (k + 1) / 2 rows with 1 <= k <= 64
+ * (packed upper triangle by columns, off-diagonals times sqrt 2: what ProbSDP produces), an LDS map of at most 163 840 bytes --
+ * 4 (6208 + 8 n + 13 m) + roundup4(m), plus 49 920 when the largest PSD order exceeds 32 --, 1 <= n_prob <= 1 048 576.
+ * Everything else is THIP_E_INVALID before anything is allocated.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_sdpbatch thip_sdpbatch;
+typedef struct thip_sdpbatch_info_t {
+    int32_t n_prob, threads;          /* as thip_midbatch_info_t ... */
+    int32_t lds_bytes, live;
+    size_t  arena_bytes;
+    size_t  device_bytes;
+    size_t  device_bytes_all;         /* summed over every thip_sdpbatch alive in the process */
+    int64_t launches, workgroups;
+    int32_t load_bytes, reserved;
+    size_t  a_bytes_per_iter;
+    int32_t max_psd_order, n_psd;     /* ... and: the largest PSD order of the layout (0: none), the number of PSD segments */
+    size_t  psd_lds_bytes;            /* LDS the projection adds beyond the vectors: 0 (orders <= 32 overlay the pass scratch) or 49 920 */
+} thip_sdpbatch_info_t;
+/* the shape rules alone (needs no device): 0 and the LDS bytes / threads of one workgroup, or THIP_E_INVALID */
+int thip_sdpbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                       size_t *host_lds_bytes, int *host_threads);
+int thip_sdpbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                         const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                         const int64_t *host_seg_len, const thip_param *par, thip_sdpbatch **out);
+int thip_sdpbatch_set_param(thip_sdpbatch *h, const thip_param *par);
+int thip_sdpbatch_init(thip_sdpbatch *h);
+int thip_sdpbatch_run(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_sdpbatch_run_until_any(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_sdpbatch_status(thip_sdpbatch *h, int i, thip_status *host_status);
+int thip_sdpbatch_solution(thip_sdpbatch *h, int i, float *host_x, float *host_y);
+int thip_sdpbatch_iterate(thip_sdpbatch *h, int i, float *host_x, float *host_y);
+int thip_sdpbatch_precond(thip_sdpbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                          const float *dev_vec_b_rowabs);
+int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
+int thip_sdpbatch_destroy(thip_sdpbatch *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

@@ -120,6 +120,15 @@ int thip_test_smallbatch_force_threads(thip_smallbatch *h, int threads);
  * thip_midbatch_init. */
 int thip_test_midbatch_force_threads(thip_midbatch *h, int threads);
 
+/* TEST HOOK: the workgroup size of an SDP batch (thip_sdpbatch.hip): 256 or 1024 threads, 0 = by shape.  Before
+ * thip_sdpbatch_init. */
+int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads);
+
+/* TEST HOOK: the SDP batch kernel's own PSD projection alone: `count` packed matrices of order k (1 .. 64; k (k + 1) / 2 floats each,
+ * one after another at dev_packed, off-diagonals times sqrt 2) are projected in place, one workgroup each, in ONE launch;
+ * dev_rx_or_null != NULL: rx <- rx - 2 x of the same layout rides in the pack. */
+int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_rx_or_null);
+
 #ifdef __cplusplus
 }
 #endif

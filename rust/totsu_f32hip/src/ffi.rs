@@ -51,6 +51,17 @@ pub struct thip_midbatch_info_t {
     pub load_bytes: i32, pub reserved: i32,
     pub a_bytes_per_iter: usize,
 }
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_sdpbatch_info_t {
+    pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub load_bytes: i32, pub reserved: i32,
+    pub a_bytes_per_iter: usize,
+    pub max_psd_order: i32, pub n_psd: i32,
+    pub psd_lds_bytes: usize,
+}
 pub const THIP_BATCH_MAX: c_int = 64;
 pub const THIP_BATCH_GROUP_DEFAULT: c_int = 8;
 
@@ -71,6 +82,7 @@ pub enum thip_solver {}
 pub enum thip_batch {}
 pub enum thip_smallbatch {}
 pub enum thip_midbatch {}
+pub enum thip_sdpbatch {}
 pub enum thip_sptile {}
 pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
@@ -278,6 +290,27 @@ extern "C" {
     pub fn thip_midbatch_info(h: *const thip_midbatch, host_info: *mut thip_midbatch_info_t) -> c_int;
     pub fn thip_midbatch_destroy(h: *mut thip_midbatch) -> c_int;
     pub fn thip_test_midbatch_force_threads(h: *mut thip_midbatch, threads: c_int) -> c_int;
+
+    // many small SDPs, each with its own A: the mid batch's iteration with the PSD cones projected on chip (thip_sdpbatch.hip)
+    pub fn thip_sdpbatch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                              host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;
+    pub fn thip_sdpbatch_create(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                host_seg_len: *const i64, par: *const thip_param, out: *mut *mut thip_sdpbatch) -> c_int;
+    pub fn thip_sdpbatch_set_param(h: *mut thip_sdpbatch, par: *const thip_param) -> c_int;
+    pub fn thip_sdpbatch_init(h: *mut thip_sdpbatch) -> c_int;
+    pub fn thip_sdpbatch_run(h: *mut thip_sdpbatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sdpbatch_run_until_any(h: *mut thip_sdpbatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sdpbatch_status(h: *mut thip_sdpbatch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sdpbatch_solution(h: *mut thip_sdpbatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_sdpbatch_iterate(h: *mut thip_sdpbatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_sdpbatch_precond(h: *mut thip_sdpbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_sdpbatch_replace(h: *mut thip_sdpbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
+                                 dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_sdpbatch_info(h: *const thip_sdpbatch, host_info: *mut thip_sdpbatch_info_t) -> c_int;
+    pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
+    pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
+    pub fn thip_test_sdpbatch_project(k: c_int, count: c_int, dev_packed: *mut f32, dev_rx_or_null: *mut f32) -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

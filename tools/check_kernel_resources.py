@@ -25,7 +25,12 @@ in flight per lane, with up to 1024 threads:
 
     midbatch_k and midbatch_init_k: the same -- no scratch at all, and >= 4 waves per SIMD.
 
-usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch]"""
+The SDP batch (thip_sdpbatch.hip, --family sdpbatch) is the mid batch's iteration with the PSD cones projected between the two passes
+by the workgroup itself (f32 MFMAs on operands in LDS), with up to 1024 threads:
+
+    sdpbatch_k, sdpbatch_init_k (and the test hook's sdpbatch_project_k): no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
+
+usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch]"""
 import re
 import sys
 
@@ -123,9 +128,34 @@ def check_midbatch(res):
     return 0
 
 
+def check_sdpbatch(res):
+    bad, seen = [], set()
+    for name, r in sorted(res.items()):
+        m = re.search(r"sdpbatch(_init|_project)?_k", name)
+        if not m or "scratch" not in r:
+            continue
+        seen.add(m.group(0))
+        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4 and r.get("vgprs", 999) <= 128
+        if "--report" in sys.argv or not ok:
+            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
+                                                                                 r["scratch"], r.get("occupancy", -1)))
+        if not ok:
+            bad.append(name)
+    if not {"sdpbatch_k", "sdpbatch_init_k"} <= seen:
+        print("check_kernel_resources: sdpbatch_k / sdpbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
+        return 2
+    if bad:
+        print("check_kernel_resources: FAILED for %s: scratch in use, > 128 VGPRs or < 4 waves/SIMD -- a 1024-thread workgroup of the SDP "
+              "batch kernel no longer fits a CU (thip_sdpbatch.hip)" % bad)
+        return 1
+    return 0
+
+
 def main():
     txt = open(sys.argv[1]).read()
     res = parse(txt)
+    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "sdpbatch":
+        return check_sdpbatch(res)
     if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "smallbatch":
         return check_smallbatch(res)
     if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "midbatch":

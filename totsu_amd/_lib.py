@@ -73,6 +73,10 @@ class MidBatchInfo(C.Structure):
     _fields_ = SmallBatchInfo._fields_ + [("load_bytes", C.c_int32), ("reserved", C.c_int32), ("a_bytes_per_iter", C.c_size_t)]
 
 
+class SdpBatchInfo(C.Structure):
+    _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
+
+
 BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
 SMALLBATCH_MAX_DIM, SMALLBATCH_MAX_AREA, SMALLBATCH_MAX_PROB, SMALLBATCH_LDS_MAX = 1024, 24576, 1048576, 163840
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -252,6 +256,22 @@ PROTOTYPES = {
     "thip_midbatch_info": (_i, [_vp, C.POINTER(MidBatchInfo)]),
     "thip_midbatch_destroy": (_i, [_vp]),
     "thip_test_midbatch_force_threads": (_i, [_vp, _i]),
+    "thip_sdpbatch_fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
+    "thip_sdpbatch_create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                  C.POINTER(Param), C.POINTER(_vp)]),
+    "thip_sdpbatch_set_param": (_i, [_vp, C.POINTER(Param)]),
+    "thip_sdpbatch_init": (_i, [_vp]),
+    "thip_sdpbatch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_sdpbatch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+    "thip_sdpbatch_status": (_i, [_vp, _i, C.POINTER(Status)]),
+    "thip_sdpbatch_solution": (_i, [_vp, _i, _vp, _vp]),
+    "thip_sdpbatch_iterate": (_i, [_vp, _i, _vp, _vp]),
+    "thip_sdpbatch_precond": (_i, [_vp, _i, _vp, _vp]),
+    "thip_sdpbatch_replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "thip_sdpbatch_info": (_i, [_vp, C.POINTER(SdpBatchInfo)]),
+    "thip_sdpbatch_destroy": (_i, [_vp]),
+    "thip_test_sdpbatch_force_threads": (_i, [_vp, _i]),
+    "thip_test_sdpbatch_project": (_i, [_i, _i, _vp, _vp]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "thip_prof_read_psd": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

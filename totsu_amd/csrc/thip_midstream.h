@@ -1,0 +1,444 @@
+// thip_midstream.h -- what the two batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
+// second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip): the LDS map of a problem's vectors, the pass over A
+// (mb_pass), the init kernel's body and the iteration's body -- the carried recurrence, two passes per iteration, every vector in
+// LDS -- with one hook in the block-cone phase between the two passes, and the host pieces that do not depend on the cones.
+// Included once by each of the two translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// includes it.
+//
+// A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when
+// m % 4 == 0 and the problem's base is 16-byte aligned, four 4-byte loads of the same entries otherwise -- the same lanes hold the
+// same entries, so both paths add in the same order), the columns into chunks of MB_CK = 8.  With R row tiles and nw waves the
+// workgroup is R x S units, S = max(1, nw / R) column slices (slice s takes the chunks s, s + S, ..); wave w serves the units
+// w, w + nw, ...  A unit loads the 8 columns of a chunk at once (8 independent loads in flight per lane), and every loaded entry
+// feeds both h += A[:, j] xn[j] (row sums in registers across the unit's chunks) and g[j] = A[:, j] . xt (a DPP wave sum per column).
+// The R partial g of a column meet in LDS (gp) per batch of CB = max(8, 2048 / R rounded down to 8) columns and are added in tile
+// order; the S partial h of a row meet in LDS (hp) and are added in slice order.  No atomics: a problem's iterates are a function of
+// (its data, the workgroup size, these constants) alone -- not of its index, its neighbours or the launch.
+//
+// LDS, in floats: [sh 64][hp 4096][gp 2048], then xx u kx ku | xy xs v ky ks kv | Tx Ty Ts Sv | hx gx (the arena's order), then
+// b c rxs g h: 8 n + 13 m floats of vectors, and the class bytes.
+#pragma once
+
+#include "thip_ownbatch.h"
+
+namespace {
+
+constexpr int MB_ROWS = 256, MB_CK = 8, MB_SCRH = 4096, MB_SCRG = 2048;
+constexpr size_t MB_MAX_DIM = 4096, MB_LDS_MAX = OB_LDS_MAX;
+
+struct MbArgs {
+    int n, m, n_cones, comp, steps;
+    int first;                              // live == NULL: workgroup k serves problem first + k
+    const int *live;                        // else problem live[k]
+    const SbSlot *slots;
+    float *arena; size_t stride;            // problem p's state: arena + p * stride
+    SbStatus *st;
+    const unsigned char *cls;               // 0 zero cone, 1 nonnegative, 2 member of a block cone
+    const int *cones;                       // (beg, end, kind) per block cone: 0 second-order, 1 rotated, 1 + k a PSD cone of order k
+    float eps_acc, eps_inf, eps_zero; long long max_iter;
+};
+
+struct MbMap {
+    int sh, hp, gp, xx, u, kx, ku, xy, xs, v, ky, ks, kv, Tx, Ty, Ts, Sv, hx, gx, b, c, rxs, g, h, cls, floats;
+    __host__ __device__ MbMap(int n, int m)
+    {
+        int o = 0;
+        auto take = [&](int k) { const int r = o; o += k; return r; };
+        sh = take(64); hp = take(MB_SCRH); gp = take(MB_SCRG);
+        xx = take(n); u = take(n); kx = take(n); ku = take(n);                                   // the arena's order: mutable part
+        xy = take(m); xs = take(m); v = take(m); ky = take(m); ks = take(m); kv = take(m);
+        Tx = take(n); Ty = take(m); Ts = take(m); Sv = take(m);                                  // constant after init
+        hx = take(m); gx = take(n);                                                              // carried: A x_x, A^T x_y
+        b = take(m); c = take(n); rxs = take(m); g = take(n); h = take(m);
+        cls = o; floats = o;
+    }
+    __host__ __device__ size_t bytes(int m) const { return (size_t)floats * 4 + (size_t)((m + 3) & ~3); }
+};
+__host__ __device__ inline size_t mb_stride(size_t n, size_t m) { return 6 * n + 10 * m; }
+
+// h = A xn (m), g = A^T xt (n) from ONE read of A (ABS: the row and column sums of |A|).  A: global, column-major, lda = m.
+// Begins and ends with a barrier: the inputs written before the call are seen, the results are visible on return.
+template <bool ABS, bool VEC>
+__device__ __forceinline__ void mb_pass_t(const float *__restrict__ A, int m, int n, const float *xn, const float *xt, float *h, float *g,
+                                          float *hp, float *gp)
+{
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6, nw = T >> 6;
+    const int R = (m + MB_ROWS - 1) / MB_ROWS;
+    const int S = R >= nw ? 1 : nw / R;
+    const int CB = max(MB_CK, (MB_SCRG / R) & ~(MB_CK - 1));
+    __syncthreads();
+    for (int cb0 = 0; cb0 < n; cb0 += CB) {
+        const int cbn = min(CB, n - cb0);
+        const int nch = (cbn + MB_CK - 1) / MB_CK;
+        for (int unit = w; unit < R * S; unit += nw) {
+            const int r = unit % R, s = unit / R;
+            const int row = r * MB_ROWS + lane * 4;
+            const bool in0 = row < m, in1 = row + 1 < m, in2 = row + 2 < m, in3 = row + 3 < m;
+            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f;
+            if (ABS) {
+                t0 = t1 = t2 = t3 = 1.0f;
+            } else {
+                if (in0) t0 = xt[row];
+                if (in1) t1 = xt[row + 1];
+                if (in2) t2 = xt[row + 2];
+                if (in3) t3 = xt[row + 3];
+            }
+            auto ld = [&](int j) {
+                float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float *p = A + (size_t)j * (size_t)m + row;
+                if (VEC) {
+                    if (in0) q = *reinterpret_cast<const float4 *>(p);      // (m % 4 == 0: all four rows or none)
+                } else {
+                    if (in0) q.x = p[0];
+                    if (in1) q.y = p[1];
+                    if (in2) q.z = p[2];
+                    if (in3) q.w = p[3];
+                }
+                if (ABS) { q.x = fabsf(q.x); q.y = fabsf(q.y); q.z = fabsf(q.z); q.w = fabsf(q.w); }
+                return q;
+            };
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+            for (int ch = s; ch < nch; ch += S) {
+                const int j0 = cb0 + ch * MB_CK;
+                const int nj = min(MB_CK, cb0 + cbn - j0);
+                float4 q[MB_CK];
+                float xj[MB_CK];
+                if (nj == MB_CK) {
+#pragma unroll
+                    for (int k = 0; k < MB_CK; ++k) q[k] = ld(j0 + k);
+#pragma unroll
+                    for (int k = 0; k < MB_CK; ++k) xj[k] = ABS ? 1.0f : xn[j0 + k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < MB_CK; ++k) {
+                        q[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        xj[k] = 0.0f;
+                        if (k < nj) { q[k] = ld(j0 + k); xj[k] = ABS ? 1.0f : xn[j0 + k]; }
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < MB_CK; ++k) {
+                    a0 = fmaf(q[k].x, xj[k], a0); a1 = fmaf(q[k].y, xj[k], a1);
+                    a2 = fmaf(q[k].z, xj[k], a2); a3 = fmaf(q[k].w, xj[k], a3);
+                    float d = q[k].x * t0;
+                    d = fmaf(q[k].y, t1, d); d = fmaf(q[k].z, t2, d); d = fmaf(q[k].w, t3, d);
+                    d = wave_sum_dpp(d);
+                    if (lane == 0 && k < nj) gp[r * CB + (j0 + k - cb0)] = d;
+                }
+            }
+            // the unit's row sums: (s, row) is this lane's alone
+            float *hs = hp + s * m + row;
+            if (cb0 == 0) {
+                if (in0) hs[0] = a0;
+                if (in1) hs[1] = a1;
+                if (in2) hs[2] = a2;
+                if (in3) hs[3] = a3;
+            } else {
+                if (in0) hs[0] += a0;
+                if (in1) hs[1] += a1;
+                if (in2) hs[2] += a2;
+                if (in3) hs[3] += a3;
+            }
+        }
+        __syncthreads();
+        for (int t = tid; t < cbn; t += T) {
+            float acc = gp[t];
+            for (int r = 1; r < R; ++r) acc += gp[r * CB + t];
+            g[cb0 + t] = acc;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < m; i += T) {
+        float acc = hp[i];
+        for (int s = 1; s < S; ++s) acc += hp[s * m + i];
+        h[i] = acc;
+    }
+    __syncthreads();
+}
+
+template <bool ABS>
+__device__ __forceinline__ void mb_pass(const float *A, bool vec, int m, int n, const float *xn, const float *xt, float *h, float *g,
+                                        float *hp, float *gp)
+{
+    if (vec) mb_pass_t<ABS, true>(A, m, n, xn, xt, h, g, hp, gp);
+    else mb_pass_t<ABS, false>(A, m, n, xn, xt, h, g, hp, gp);
+}
+
+__device__ __forceinline__ bool mb_vec(const float *a, int m) { return (m & 3) == 0 && ((uintptr_t)a & 15u) == 0; }
+
+extern __shared__ float mb_lds[];
+
+// the block-cone phase of a family without PSD cones: nothing beside the second-order cones
+struct MbNoPsd {
+    static constexpr bool psd = false;
+    __device__ __forceinline__ void operator()(float *, const MbMap &, const MbArgs &) const {}
+};
+
+// calc_norms, calc_precond and init_vecs (solver.rs:460-524) of one problem per workgroup, as smallbatch_init_k, with the |A| sums
+// from one streamed pass.  product_group takes the minimum over every block cone, second-order or PSD
+__device__ __forceinline__ void mb_init_body(const MbArgs &a)
+{
+    const int p = a.live ? a.live[blockIdx.x] : a.first + (int)blockIdx.x;
+    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const MbMap L(n, m);
+    float *S = mb_lds;
+    const SbSlot sl = a.slots[p];
+    for (int i = tid; i < m; i += T) S[L.b + i] = sl.b[i];
+    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
+    __syncthreads();
+    float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };              // sum b^2, sum |b|, sum c^2, sum |c|
+    for (int i = tid; i < m; i += T) { const float t = S[L.b + i]; q[0] = fmaf(t, t, q[0]); q[1] += fabsf(t); }
+    for (int i = tid; i < n; i += T) { const float t = S[L.c + i]; q[2] = fmaf(t, t, q[2]); q[3] += fabsf(t); }
+    block_sums<4>(q, S + L.sh);
+    mb_pass<true>(sl.a, mb_vec(sl.a, m), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);      // |A| row / column sums
+    float *ar = a.arena + (size_t)p * a.stride;
+    float *gTx = ar + 4 * n + 6 * m, *gTy = gTx + n, *gTs = gTy + m, *gSv = gTs + m, *gcar = gSv + m;
+    for (int i = tid; i < n; i += T) {
+        const float t = S[L.g + i] + fabsf(S[L.c + i]);
+        gTx[i] = 1.0f / fmaxf(t, a.eps_zero);
+    }
+    for (int i = tid; i < m; i += T) {
+        const float t = S[L.h + i] + (sl.rowabs ? sl.rowabs[i] : fabsf(S[L.b + i]));
+        S[L.Ty + i] = 1.0f / fmaxf(t, a.eps_zero);
+        S[L.Ts + i] = 1.0f / fmaxf(1.0f, a.eps_zero);
+        gSv[i] = 1.0f / fmaxf(t + 1.0f, a.eps_zero);
+    }
+    __syncthreads();
+    {   // product_group (solver.rs:509-523): the minimum over each block cone, one wave per cone
+        const int lane = tid & 63, w = tid >> 6, nw = T >> 6;
+        for (int k = w; k < a.n_cones; k += nw) {
+            const int beg = a.cones[3 * k], end = a.cones[3 * k + 1];
+            for (int which = 0; which < 2; ++which) {
+                float *t = S + (which ? L.Ts : L.Ty);
+                float mn = __builtin_inff();
+                for (int i = beg + lane; i < end; i += 64) mn = fminf(mn, t[i]);
+                mn = wave_min(mn);
+                for (int i = beg + lane; i < end; i += 64) t[i] = mn;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += T) { gTy[i] = S[L.Ty + i]; gTs[i] = S[L.Ts + i]; }
+    for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
+    for (int i = tid; i < m + n; i += T) gcar[i] = 0.0f;            // A 0, A^T 0
+    if (tid == 0) {
+        SbStatus s;
+        s.stop = 0; s.state = THIP_ST_RUNNING; s.kind = 0; s.pad = 0; s.iter = 0;
+        s.cri[0] = s.cri[1] = s.cri[2] = 0.0f;
+        s.tau = 1.0f; s.kappa = 0.0f; s.r_tau = 0.0f;
+        const float nb = sqrtf(q[0]), nc = sqrtf(q[2]);      // fr_norm (solver.rs:85-107)
+        s.norm_b = sqrtf(nb * nb);
+        s.norm_c = sqrtf(nc * nc);
+        const float tau_tau = q[3] + q[1];
+        s.t_tau = 1.0f / fmaxf(tau_tau, a.eps_zero);
+        s.s_kappa = 1.0f / fmaxf(tau_tau, a.eps_zero);
+        a.st[p] = s;
+    }
+}
+
+// `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
+// (called by every thread, after the second-order cones; hp, gp and g are dead there)
+template <class PSD>
+__device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_cones)
+{
+    const int p = a.live ? a.live[blockIdx.x] : a.first + (int)blockIdx.x;
+    SbStatus *const gst = a.st + p;
+    if (gst->stop != 0) return;
+    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6, nw = T >> 6;
+    const bool comp = a.comp != 0;
+    const MbMap L(n, m);
+    float *S = mb_lds;
+    float *const sh = S + L.sh, *const hp = S + L.hp, *const gp = S + L.gp;
+    float *const xx = S + L.xx, *const u = S + L.u, *const kx = S + L.kx, *const ku = S + L.ku;
+    float *const xy = S + L.xy, *const xs = S + L.xs, *const v = S + L.v, *const ky = S + L.ky, *const ks = S + L.ks, *const kv = S + L.kv;
+    const float *const Tx = S + L.Tx, *const Ty = S + L.Ty, *const Ts = S + L.Ts, *const Sv = S + L.Sv;
+    float *const hx = S + L.hx, *const gx = S + L.gx;
+    const float *const b = S + L.b, *const c = S + L.c;
+    float *const rxs = S + L.rxs, *const g = S + L.g, *const h = S + L.h;
+    unsigned char *const cls = reinterpret_cast<unsigned char *>(S + L.cls);
+
+    // ---- load ----
+    const SbSlot sl = a.slots[p];
+    const float *const A = sl.a;
+    const bool vec = mb_vec(A, m);
+    float *const ar = a.arena + (size_t)p * a.stride;
+    {
+        const int nstate = 6 * n + 10 * m;                 // the arena's order is the LDS order from xx on
+        for (int i = tid; i < nstate; i += T) xx[i] = ar[i];
+    }
+    for (int i = tid; i < m; i += T) { S[L.b + i] = sl.b[i]; cls[i] = a.cls[i]; }
+    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
+    float tau = gst->tau, kappa = gst->kappa, rtau = gst->r_tau;
+    const float norm_b = gst->norm_b, norm_c = gst->norm_c, t_tau = gst->t_tau, s_kappa = gst->s_kappa;
+    long long iter = gst->iter;
+    int state = THIP_ST_RUNNING, kind = gst->kind;
+    float cri0 = gst->cri[0], cri1 = gst->cri[1], cri2 = gst->cri[2];
+    __syncthreads();
+
+    for (int step = 0; step < a.steps; ++step) {
+        // ---- x += T o (-K^T y): h = A u, g = A^T v; c.u, b.v, and c.x_x, b.x_y of the iterate that is about to move ----
+        float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+        for (int i = tid; i < n; i += T) { q[0] = fmaf(c[i], u[i], q[0]); q[2] = fmaf(c[i], xx[i], q[2]); }
+        for (int i = tid; i < m; i += T) { q[1] = fmaf(b[i], v[i], q[1]); q[3] = fmaf(b[i], xy[i], q[3]); }
+        mb_pass<false>(A, vec, m, n, u, v, h, g, hp, gp);
+        block_sums<4>(q, sh);
+        const float cx_old = q[2], by_old = q[3];
+        for (int i = tid; i < n; i += T) xx[i] = sb_comp_add(xx[i], Tx[i] * (g[i] + c[i] * kappa), kx, i, comp);
+        for (int i = tid; i < m; i += T) {
+            const unsigned char k = cls[i];
+            const float oy = xy[i], os = xs[i];
+            float ny = sb_comp_add(oy, Ty[i] * (b[i] * kappa - h[i]), ky, i, comp);
+            float ns = sb_comp_add(os, Ts[i] * v[i], ks, i, comp);
+            if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
+            else if (k == 0) { ns = 0.0f; }
+            xy[i] = ny;
+            xs[i] = ns;
+            h[i] = oy;                                             // (rx_y is not needed: what sb_soc writes there is dropped)
+            rxs[i] = (k < 2) ? os - 2.0f * ns : os;
+        }
+        {
+            const float old = tau;
+            tau = fmaxf(old + t_tau * (-q[0] - q[1]), 0.0f);      // solver.rs:551-552
+            rtau = old - 2.0f * tau;
+        }
+        __syncthreads();
+        // ---- the block cones: one wave per second-order cone, x_y then x_s; then the family's PSD cones ----
+        if (a.n_cones > 0) {
+            for (int k = wv; k < a.n_cones; k += nw) {
+                const int beg = a.cones[3 * k], end = a.cones[3 * k + 1], rot = a.cones[3 * k + 2];
+                if (PSD::psd && rot >= 2) continue;
+                sb_soc(xy, h, beg, end, rot, lane);
+                sb_soc(xs, rxs, beg, end, rot, lane);
+            }
+        }
+        psd_cones(S, L, a);
+        // ---- h = A x_x, g = A^T x_y of the new iterate: the criteria, and K rx = K x_k - 2 K x_{k+1} ----
+        mb_pass<false>(A, vec, m, n, xx, xy, h, g, hp, gp);
+        const bool conv = tau > a.eps_zero;
+        const float rt = conv ? 1.0f / tau : 1.0f;
+        q[0] = q[1] = q[2] = q[3] = 0.0f;                          // ||p||^2, b.x_y, ||d||^2, c.x_x
+        for (int i = tid; i < m; i += T) {
+            const float bi = b[i];
+            float pr;
+            if (conv) { pr = xs[i] * rt - bi; pr = fmaf(rt, h[i], pr); }
+            else pr = xs[i] + h[i];
+            q[0] = fmaf(pr, pr, q[0]);
+            q[1] = fmaf(bi, xy[i], q[1]);
+        }
+        for (int i = tid; i < n; i += T) {
+            const float ci = c[i];
+            const float d = conv ? fmaf(rt, g[i], ci) : g[i];
+            q[2] = fmaf(d, d, q[2]);
+            q[3] = fmaf(ci, xx[i], q[3]);
+        }
+        block_sums<4>(q, sh);
+        const float pp = q[0], by = q[1], dd = q[2], cx = q[3];
+        // ---- y += S o (-K rx) (ycrit_k), the pair carried on ----
+        for (int i = tid; i < n; i += T) {
+            const float gn = g[i];
+            u[i] = sb_comp_add(u[i], Tx[i] * (-(gx[i] - 2.0f * gn) - c[i] * rtau), ku, i, comp);
+            gx[i] = gn;
+        }
+        for (int i = tid; i < m; i += T) {
+            const float hn = h[i];
+            v[i] = sb_comp_add(v[i], Sv[i] * ((hx[i] - 2.0f * hn) + rxs[i] - b[i] * rtau), kv, i, comp);
+            hx[i] = hn;
+        }
+        kappa = fminf(kappa + s_kappa * ((cx_old - 2.0f * cx) + (by_old - 2.0f * by)), 0.0f);     // solver.rs:566-567
+        // ---- status_eval ----
+        const bool excess_iter = (a.max_iter >= 0) ? (iter + 1 >= a.max_iter) : false;
+        const float norm_p = sqrtf(pp), norm_d = sqrtf(dd);
+        if (conv) {
+            const float g_x = rt * cx;
+            const float g_y = rt * by;
+            const float gg = g_x + g_y;
+            kind = 0;
+            cri0 = norm_p / (1.0f + norm_b);
+            cri1 = norm_d / (1.0f + norm_c);
+            cri2 = fabsf(gg) / (1.0f + fabsf(g_x) + fabsf(g_y));
+            const bool term_conv = (cri0 <= a.eps_acc) && (cri1 <= a.eps_acc) && (cri2 <= a.eps_acc);
+            if (term_conv) state = THIP_ST_OK;
+            else if (excess_iter) state = THIP_ST_EXCESS_ITER;
+        } else {
+            const float m_cx = -cx;
+            const float m_by = -by;
+            kind = 1;
+            cri0 = (m_cx > a.eps_zero) ? norm_p * norm_c / m_cx : __builtin_inff();
+            cri1 = (m_by > a.eps_zero) ? norm_d * norm_b / m_by : __builtin_inff();
+            cri2 = 0.0f;
+            if (cri0 <= a.eps_inf) state = THIP_ST_UNBOUNDED;
+            else if (cri1 <= a.eps_inf) state = THIP_ST_INFEASIBLE;
+            else if (excess_iter) state = THIP_ST_EXCESS_ITER;
+        }
+        if (state != THIP_ST_RUNNING) break;                       // (uniform: every thread holds the same sums)
+        iter += 1;
+    }
+
+    // ---- store ----
+    __syncthreads();
+    {
+        const int nmut = 4 * n + 6 * m;
+        for (int i = tid; i < nmut; i += T) ar[i] = xx[i];
+        float *const gcar = ar + 5 * n + 9 * m;
+        for (int i = tid; i < m + n; i += T) gcar[i] = hx[i];      // (gx follows hx)
+    }
+    if (tid == 0) {
+        gst->tau = tau; gst->kappa = kappa; gst->r_tau = rtau; gst->iter = iter;
+        gst->kind = kind; gst->cri[0] = cri0; gst->cri[1] = cri1; gst->cri[2] = cri2;
+        gst->state = state;
+        gst->stop = state != THIP_ST_RUNNING ? 1 : 0;
+    }
+}
+
+// ---- the host side ------------------------------------------------------------------------------------------------------------
+
+int mb_threads_for(size_t n, size_t m) { return n * m <= 8192 ? 256 : 1024; }
+
+// a handle of either family: which slots hold an A that is not 16-byte aligned decides the load path info() reports
+struct MbHandle : OwnBatch {
+    std::vector<unsigned char> unaligned;   // per slot: the problem's A is not 16-byte aligned
+    size_t n_unaligned = 0;
+};
+
+void mb_note_alignment(MbHandle *h, const float *dev_mats_a)
+{
+    h->unaligned.assign(h->n_prob, 0);
+    for (size_t p = 0; p < h->n_prob; ++p) {
+        h->unaligned[p] = (((uintptr_t)(dev_mats_a + p * h->m * h->n)) & 15u) != 0;
+        h->n_unaligned += h->unaligned[p];
+    }
+}
+
+void mb_note_replaced(MbHandle *h, int i, const float *dev_mat_a)
+{
+    const unsigned char un = ((uintptr_t)dev_mat_a & 15u) != 0;
+    h->n_unaligned += un;
+    h->n_unaligned -= h->unaligned[(size_t)i];
+    h->unaligned[(size_t)i] = un;
+}
+
+MbArgs mb_args(const OwnBatch *h)
+{
+    MbArgs a{};
+    a.n = (int)h->n; a.m = (int)h->m; a.n_cones = (int)(h->cones.size() / 3);
+    a.comp = h->par.state_arith == THIP_STATE_COMPENSATED; a.steps = 0; a.first = 0; a.live = nullptr;
+    a.slots = h->slots; a.arena = h->arena; a.stride = h->stride; a.st = h->dst; a.cls = h->cls_dev; a.cones = h->cones_dev;
+    a.eps_acc = h->par.eps_acc; a.eps_inf = h->par.eps_inf; a.eps_zero = h->par.eps_zero; a.max_iter = h->par.max_iter;
+    return a;
+}
+
+// the fields of thip_midbatch_info_t, which both families' records begin with
+template <class INFO>
+void mb_info(const MbHandle *h, size_t total, INFO &o)
+{
+    o.n_prob = (int32_t)h->n_prob; o.threads = h->threads; o.lds_bytes = (int32_t)h->lds; o.live = (int32_t)h->live.size();
+    o.arena_bytes = h->stride * h->n_prob * sizeof(float);
+    o.device_bytes = h->bytes;
+    o.device_bytes_all = total;
+    o.launches = h->launches; o.workgroups = h->workgroups;
+    o.load_bytes = ((h->m & 3) == 0 && h->n_unaligned == 0) ? 16 : 4;
+    o.a_bytes_per_iter = 2 * h->m * h->n * sizeof(float);
+}
+
+}  // namespace

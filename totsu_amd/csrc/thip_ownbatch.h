@@ -1,8 +1,9 @@
-// thip_ownbatch.h -- what the two "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip: A
-// streamed from memory): the status block and the slot of a problem, the device functions of the iteration that do not touch A
-// (block_sums, sb_comp_add, sb_soc), and the host machinery -- slots, arena, all 64-byte status blocks in one copy, the live list,
-// replace as the init kernel on one slot.  A family supplies its two launches, its shape rule and its words for the refusals.
-// Included once by each of the two translation units: everything here is internal to the one that includes it.
+// thip_ownbatch.h -- what the "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip and
+// thip_sdpbatch.hip: A streamed from memory, thip_midstream.h): the status block and the slot of a problem, the device functions of
+// the iteration that do not touch A (block_sums, sb_comp_add, sb_soc), and the host machinery -- slots, arena, all 64-byte status
+// blocks in one copy, the live list, replace as the init kernel on one slot.  A family supplies its two launches, its shape rule
+// and its words for the refusals.
+// Included once by each of the translation units: everything here is internal to the one that includes it.
 #pragma once
 
 #include "thip_common.h"
@@ -159,9 +160,11 @@ struct OwnBatch {
     int64_t launches = 0, workgroups = 0;
 };
 
-// the cone segments (no device needed).  On success *cones holds (beg, end, rotated) per block cone and *cls the class bytes
+// the cone segments (no device needed).  On success *cones holds (beg, end, kind) per block cone -- kind 0: second-order, 1: rotated,
+// 1 + k: a PSD cone of order k -- and *cls the class bytes.  psd_max: the largest PSD order the family takes (0: it takes no PSD
+// segment and refuses one in its own words, tx.no_psd)
 int ob_segments(const ObText &tx, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, std::vector<int> *cones,
-                std::vector<unsigned char> *cls)
+                std::vector<unsigned char> *cls, int psd_max = 0)
 {
     if (n_seg && (!seg_type || !seg_len)) return fail(THIP_E_INVALID, "null cone segments", __FILE__, __LINE__);
     int64_t off = 0;
@@ -169,12 +172,22 @@ int ob_segments(const ObText &tx, size_t m, size_t n_seg, const int32_t *seg_typ
     for (size_t i = 0; i < n_seg; ++i) {
         const int64_t l = seg_len[i];
         if (l < 0 || seg_type[i] < 0 || seg_type[i] > THIP_CONE_PSD) return fail(THIP_E_INVALID, "bad cone segment", __FILE__, __LINE__);
-        if (seg_type[i] == THIP_CONE_PSD) return fail(THIP_E_INVALID, tx.no_psd, __FILE__, __LINE__);
+        int kind = seg_type[i] == THIP_CONE_ROTSOC ? 1 : 0;
+        if (seg_type[i] == THIP_CONE_PSD) {
+            if (psd_max == 0) return fail(THIP_E_INVALID, tx.no_psd, __FILE__, __LINE__);
+            int64_t k = 0;
+            while (k <= psd_max && k * (k + 1) / 2 < l) ++k;
+            if (k > psd_max) return fail(THIP_E_INVALID, "a PSD segment of an order above 64: the batch projects orders 1 .. 64", __FILE__, __LINE__);
+            if (l == 0 || k * (k + 1) / 2 != l)
+                return fail(THIP_E_INVALID, "a PSD segment of order k holds k (k + 1) / 2 rows, k >= 1: not a triangular number", __FILE__,
+                            __LINE__);
+            kind = 1 + (int)k;
+        }
         if (off + l > (int64_t)m) return fail(THIP_E_INVALID, "cone segments do not cover m rows", __FILE__, __LINE__);
         if (seg_type[i] == THIP_CONE_ZERO || seg_type[i] == THIP_CONE_RPOS) {
             if (cls) for (int64_t r = 0; r < l; ++r) (*cls)[(size_t)(off + r)] = seg_type[i] == THIP_CONE_ZERO ? 0 : 1;
         } else if (cones) {
-            cones->push_back((int)off); cones->push_back((int)(off + l)); cones->push_back(seg_type[i] == THIP_CONE_ROTSOC ? 1 : 0);
+            cones->push_back((int)off); cones->push_back((int)(off + l)); cones->push_back(kind);
         }
         off += l;
     }

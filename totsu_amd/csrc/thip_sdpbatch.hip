@@ -1,0 +1,406 @@
+// thip_sdpbatch.hip -- thip_sdpbatch: many small SDPs (and mixed conic programs with PSD blocks), each with its OWN dense f32 A, one
+// shape n, m and one cone layout.  The third own-A family: the mid batch's iteration unchanged (thip_midstream.h: one workgroup per
+// problem, every vector in LDS, A streamed twice per iteration, the carried pair in the arena) with one more cone class in the
+// block-cone phase between the two passes -- every PSD cone of order k <= 64 is projected by the workgroup itself, on x_y and then on
+// x_s, so an iteration of a small SDP has no launch boundary inside it.
+//
+// The projection (sdp_project) is polar_small_k's (thip_eig_gemm.inc): Pi(M) = (M + M sign(M)) / 2 with sign(M) from the 45-product
+// quintic polar chain on M / ||M||_F (11 lifting quintics, the first on 1.7 x; 3 minimax quintics; 1 Newton-Schulz step -- the same
+// coefficients, so the same (0, 1.85] band), operands row-major in LDS at an odd pitch, __builtin_amdgcn_mfma_f32_32x32x2f32 with
+// one 32 x 32 quadrant of the result per wave, a DIVISION by the norm per element (the exact zero matrix stays zero, a subnormal
+// norm does not overflow), the packing of cone_psd.rs (off-diagonals carry sqrt 2 in the vector: the diagonal is multiplied by
+// sqrt 2 on the way in and divided on the way out) and the symmetrised pack with rx <- rx - 2 x riding in it.  What differs:
+//   * FOUR operands, not five: M is needed only by the last product M sign(M), and is unpacked again from the packed vector (which
+//     is not written before the pack) into an operand that is dead by then;
+//   * the operand extent follows the order: k <= 32 takes 32 x 33 operands and one wave, above that 64 x 65 and four;
+//   * K is walked in chunks of 4 MFMA steps with a run-time count (ceil(k / 2) rounded up to 4, the padding is zero) instead of a
+//     compile-time unroll of up to 32: a 1024-thread workgroup has 128 VGPRs per lane, and one instance serves every order.
+// Cones are projected one after another, x_y then x_s, by waves 0 .. 3 (the simple form; the other waves of a 1024-thread workgroup
+// wait at the barriers).
+//
+// LDS: the mid batch's map, and the operands.  During the cone phase the pass scratch hp, gp (6144 floats) is dead:
+//   largest order <= 32: four 32 x 33 operands (4224 floats) lie in it -- the projection adds nothing;
+//   largest order  > 32: one 64 x 65 operand (4160 floats) lies in it, three more follow the class bytes: 3 * 64 * 65 * 4 = 49 920 bytes.
+// sp_check is the single source of the rule.  No atomics: a problem's iterates are a function of (its data, the workgroup size, the
+// constants) alone.
+#include "thip_midstream.h"
+
+#include <mutex>
+
+using namespace thip;
+
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int SP_MAX_ORDER = 64, SP_OP32 = 32 * 33, SP_OP64 = 64 * 65;
+static_assert(4 * SP_OP32 <= MB_SCRH + MB_SCRG && SP_OP64 <= MB_SCRH + MB_SCRG, "the operands that overlay the pass scratch fit it");
+
+// floats the projection adds behind the class bytes for a layout whose largest PSD order is max_k (0: no PSD cone)
+__host__ __device__ inline size_t sp_tail_floats(int max_k) { return max_k > 32 ? 3 * (size_t)SP_OP64 : 0; }
+
+// C = alpha * (FORM 0: A B^T, FORM 1: A B) + beta * D + gamma * I_k on this wave's quadrant (ps_gemm of thip_eig_gemm.inc with
+// a run-time number of MFMA steps nk, a multiple of 4; the columns k .. 2 nk - 1 are zero padding inside the operands).
+// Operands: row-major, pitch P.  Ends with a barrier
+template <int FORM, int P>
+__device__ __forceinline__ void sp_gemm(float *C, const float *A, const float *B, const float *D, float alpha, float beta, float gamma,
+                                        int k, int nk, int qi, int qj, int h, int li, bool live)
+{
+    if (live) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        const float *pa = A + (32 * qi + li) * P + h;
+        const float *pb = FORM == 0 ? B + (32 * qj + li) * P + h : B + h * P + 32 * qj + li;
+        constexpr int SB = FORM == 0 ? 2 : 2 * P;
+        for (int u0 = 0; u0 < nk; u0 += 4) {
+            float av[4], bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { av[u] = pa[2 * (u0 + u)]; bv[u] = pb[SB * (u0 + u)]; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = 32 * qi + (r & 3) + 8 * (r >> 2) + 4 * h, j = 32 * qj + li;
+            float v = alpha * acc[r];
+            if (D != nullptr) v = fmaf(beta, D[i * P + j], v);
+            if (i == j && i < k) v += gamma;
+            C[i * P + j] = v;
+        }
+    }
+    __syncthreads();
+}
+
+// x (packed, k (k + 1) / 2 entries) <- its projection onto the PSD cone, by the whole workgroup (every thread calls; blockDim.x a
+// multiple of 64, >= 256 when E == 64); rx != nullptr: rx <- rx - 2 x rides in the pack.  E: the operands' extent (32: k <= 32, 64),
+// o0 .. o3: four operands of E * (E + 1) floats, shd: 16 doubles.  Begins with the caller's barrier behind it (x is visible), ends
+// with a barrier (x, rx are visible, the operands are free)
+template <int E>
+__device__ __forceinline__ void sp_project(float *x, float *rx, int k, float *o0, float *o1, float *o2, float *o3, double *shd)
+{
+    constexpr int P = E + 1;
+    // (the thread index is made opaque here: every per-lane address below is then computed inside the projection instead of being
+    // hoisted out of the iteration loop, where it would be live across the passes over A and push the kernel into scratch)
+    int tid = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int T = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int qi = wave >> 1, qj = wave & 1, h = lane >> 5, li = lane & 31;
+    // a quadrant that is all padding is neither computed nor read (the operands' padding is zero from the unpack on)
+    const bool live = wave < (E == 32 ? 1 : 4) && 32 * qi < k && 32 * qj < k;
+    const int nk = ((k + 7) / 8) * 4;
+    const float scale = sqrtf(2.0f);
+    auto entry = [&](int r, int c) {
+        float v = 0.0f;
+        if (r < k && c < k) {
+            const int lo = r < c ? r : c, hi = r < c ? c : r;
+            v = x[hi * (hi + 1) / 2 + lo];
+            if (r == c) v *= scale;
+        }
+        return v;
+    };
+    double acc = 0.0;
+    for (int e = tid; e < E * E; e += T) {
+        const int r = e % E, c = e / E;
+        const float v = entry(r, c);
+        acc += (double)v * (double)v;
+        o0[r * P + c] = v;
+        o1[r * P + c] = 0.0f; o2[r * P + c] = 0.0f; o3[r * P + c] = 0.0f;
+    }
+    acc = block_sum_d(acc, shd);
+    const float fro = (float)sqrt(acc);
+    // a DIVISION per element, not a multiplication by 1 / fro: the reciprocal of a subnormal norm is infinite (a slack block on its
+    // way to zero gets there), and 0 * inf poisons the iterate.  The exact zero matrix stays zero.
+    for (int e = tid; e < E * E; e += T) {
+        const int o = (e % E) * P + e / E;
+        o0[o] = fro > 0.0f ? o0[o] / fro : 0.0f;
+    }
+    __syncthreads();
+    float *S = o0, *Z = o1, *const Y = o2, *const Tm = o3;
+#pragma unroll 1
+    for (int it = 0; it < 14; ++it) {
+        // 11 lifting quintics (the first on 1.7 x; band [0.3, 1.7], gain 3.94), 3 minimax quintics
+        float a, b, c;
+        if (it == 0) { a = 4.02942496f * 1.7f; b = -3.82532605f * 4.913f; c = 0.95951948f * 14.19857f; }
+        else if (it < 11) { a = 4.02942496f; b = -3.82532605f; c = 0.95951948f; }
+        else if (it == 11) { a = 2.647997920f; b = -1.945904487f; c = 0.440483961f; }
+        else if (it == 12) { a = 1.967564378f; b = -1.351306898f; c = 0.386705679f; }
+        else { a = 1.884943743f; b = -1.269148602f; c = 0.384197480f; }
+        sp_gemm<0, P>(Y, S, S, nullptr, 1.0f, 0.0f, 0.0f, k, nk, qi, qj, h, li, live);          // Y = S S^T
+        sp_gemm<1, P>(Tm, Y, Y, Y, c, b, a, k, nk, qi, qj, h, li, live);                        // T = c Y Y + b Y + a I
+        sp_gemm<1, P>(Z, Tm, S, nullptr, 1.0f, 0.0f, 0.0f, k, nk, qi, qj, h, li, live);         // Z = T S
+        float *t = S; S = Z; Z = t;
+    }
+    sp_gemm<0, P>(Tm, S, S, nullptr, -0.5f, 0.0f, 1.5f, k, nk, qi, qj, h, li, live);            // one Newton-Schulz step
+    sp_gemm<1, P>(Z, Tm, S, nullptr, 1.0f, 0.0f, 0.0f, k, nk, qi, qj, h, li, live);
+    { float *t = S; S = Z; Z = t; }
+    for (int e = tid; e < E * E; e += T) Y[(e % E) * P + e / E] = entry(e % E, e / E);           // M again: Y is dead, x is unwritten
+    __syncthreads();
+    sp_gemm<1, P>(Z, Y, S, nullptr, 1.0f, 0.0f, 0.0f, k, nk, qi, qj, h, li, live);              // M sign(M)
+    for (int e = tid; e < E * E; e += T) {
+        const int r = e % E, c = e / E;
+        if (r <= c && c < k) {
+            float v = 0.5f * (Y[r * P + c] + 0.5f * (Z[r * P + c] + Z[c * P + r]));
+            if (r == c) v = v / scale;
+            const int o = c * (c + 1) / 2 + r;
+            x[o] = v;
+            if (rx != nullptr) rx[o] = rx[o] - 2.0f * v;
+        }
+    }
+    __syncthreads();
+}
+
+// scr: SP_OP64 (4 * SP_OP32 fits) floats; tail: 3 * SP_OP64 floats, touched only when k > 32
+__device__ __forceinline__ void sp_project_any(float *x, float *rx, int k, float *scr, float *tail, double *shd)
+{
+    if (k <= 32) sp_project<32>(x, rx, k, scr, scr + SP_OP32, scr + 2 * SP_OP32, scr + 3 * SP_OP32, shd);
+    else sp_project<64>(x, rx, k, scr, tail, tail + SP_OP64, tail + 2 * SP_OP64, shd);
+}
+
+// the PSD cones of the block-cone phase: one after another, x_y (whose reflection is not needed) then x_s
+struct SpCones {
+    static constexpr bool psd = true;
+    int tail;                               // where the operands behind the class bytes begin, in floats
+    __device__ __forceinline__ void operator()(float *S, const MbMap &L, const MbArgs &a) const
+    {
+        for (int c = 0; c < a.n_cones; ++c) {
+            const int kind = a.cones[3 * c + 2];
+            if (kind < 2) continue;
+            const int beg = a.cones[3 * c];
+#pragma unroll 1
+            for (int which = 0; which < 2; ++which)
+                sp_project_any(S + (which ? L.xs : L.xy) + beg, which ? S + L.rxs + beg : nullptr, kind - 1, S + L.hp, S + tail,
+                               reinterpret_cast<double *>(S + L.sh));
+        }
+    }
+};
+
+struct SpArgs { MbArgs mb; int tail; };
+
+__global__ __launch_bounds__(1024) void sdpbatch_init_k(const MbArgs a) { mb_init_body(a); }
+
+__global__ __launch_bounds__(1024) void sdpbatch_k(const SpArgs a) { mb_iterate_body(a.mb, SpCones{ a.tail }); }
+
+// thip_test_sdpbatch_project: the projection alone, one workgroup per packed matrix.  LDS: [shd 64][operands]
+__global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, float *rx)
+{
+    const size_t len = (size_t)k * (size_t)(k + 1) / 2;
+    float *S = mb_lds;
+    sp_project_any(packed + blockIdx.x * len, rx != nullptr ? rx + blockIdx.x * len : nullptr, k, S + 64, S + 64 + SP_OP64,
+                   reinterpret_cast<double *>(S));
+}
+
+size_t g_sp_bytes = 0;                      // device memory held by every thip_sdpbatch of the process
+
+const ObText SP_TEXT = { "SDP batch not initialised", "null SDP batch", "an SDP batch holds 1 .. 1048576 problems", nullptr };
+
+struct SpShape { int max_k = 0, n_psd = 0; size_t lds = 0, tail_bytes = 0; };
+
+// the shape rules (no device needed): the single source of the limit
+int sp_check(size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, std::vector<int> *cones,
+             std::vector<unsigned char> *cls, SpShape *shape)
+{
+    if (m < 1 || m > MB_MAX_DIM || n < 1 || n > MB_MAX_DIM)
+        return fail(THIP_E_INVALID, "an SDP batch takes 1 <= m <= 4096 and 1 <= n <= 4096", __FILE__, __LINE__);
+    std::vector<int> local;
+    if (!cones) cones = &local;
+    THIP_RC(ob_segments(SP_TEXT, m, n_seg, seg_type, seg_len, cones, cls, SP_MAX_ORDER));
+    SpShape s;
+    for (size_t i = 0; i + 2 < cones->size(); i += 3)
+        if ((*cones)[i + 2] >= 2) { s.n_psd += 1; s.max_k = std::max(s.max_k, (*cones)[i + 2] - 1); }
+    s.tail_bytes = sp_tail_floats(s.max_k) * sizeof(float);
+    s.lds = MbMap((int)n, (int)m).bytes((int)m) + s.tail_bytes;
+    if (s.lds > MB_LDS_MAX)
+        return fail(THIP_E_INVALID, "the vectors of the problem (8 n + 13 m floats and 24 832 bytes) and the three operands a PSD order "
+                                    "above 32 adds (49 920 bytes) do not fit the LDS of one CU", __FILE__, __LINE__);
+    if (shape) *shape = s;
+    return 0;
+}
+
+}  // namespace
+
+struct thip_sdpbatch : MbHandle {
+    SpShape shape;
+};
+
+namespace {
+
+int sp_attr()
+{
+    static std::once_flag once;
+    static hipError_t err = hipSuccess;
+    std::call_once(once, [&]() {
+        err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MB_LDS_MAX);
+        if (err == hipSuccess)
+            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_init_k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)MB_LDS_MAX);
+        if (err == hipSuccess)
+            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_project_k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)MB_LDS_MAX);
+    });
+    THIP_TRY(err);
+    return 0;
+}
+
+void sp_plan(thip_sdpbatch *h)
+{
+    h->threads = h->forced ? h->forced : mb_threads_for(h->n, h->m);
+    h->lds = h->shape.lds;
+}
+
+int sp_launch_init(OwnBatch *h, int first, int count)
+{
+    MbArgs a = mb_args(h);
+    a.first = first;
+    hipLaunchKernelGGL(sdpbatch_init_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int sp_launch_run(OwnBatch *h, int count, int steps, const int *live)
+{
+    SpArgs a{};
+    a.mb = mb_args(h);
+    a.mb.steps = steps;
+    a.mb.live = live;
+    a.tail = (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float));
+    hipLaunchKernelGGL(sdpbatch_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+#define SP_NEED(h)                                                                  \
+    do {                                                                            \
+        if (!(h)) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SP_TEXT.uninit, __FILE__, __LINE__); } \
+    } while (0)
+
+extern "C" {
+
+int thip_sdpbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                       size_t *host_lds_bytes, int *host_threads)
+{
+    SpShape s;
+    THIP_RC(sp_check(n, m, n_seg, host_seg_type, host_seg_len, nullptr, nullptr, &s));
+    if (host_threads) *host_threads = mb_threads_for(n, m);
+    if (host_lds_bytes) *host_lds_bytes = s.lds;                                    // (the same for every workgroup size)
+    return 0;
+}
+
+int thip_sdpbatch_destroy(thip_sdpbatch *h)
+{
+    if (!h) return 0;
+    ob_destroy(h);
+    delete h;
+    return 0;
+}
+
+int thip_sdpbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b, const float *dev_vecs_c,
+                         const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                         const thip_param *par, thip_sdpbatch **out)
+{
+    if (!out) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    *out = nullptr;
+    THIP_NEED_INIT();
+    THIP_RC(ob_create_args(SP_TEXT, n_prob, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs, par));
+    thip_sdpbatch *h = new thip_sdpbatch();
+    h->text = &SP_TEXT; h->total = &g_sp_bytes; h->launch_init = sp_launch_init; h->launch_run = sp_launch_run;
+    // every refusal comes before the first allocation
+    int rc = sp_check(n, m, n_seg, host_seg_type, host_seg_len, &h->cones, &h->cls, &h->shape);
+    if (rc != 0) { delete h; return rc; }
+    h->n = n; h->m = m; h->n_prob = n_prob;
+    h->par = *par;
+    h->stride = mb_stride(n, m);
+    sp_plan(h);
+    mb_note_alignment(h, dev_mats_a);
+    rc = sp_attr();
+    if (rc == 0) rc = ob_build(h, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs);
+    if (rc != 0) { thip_sdpbatch_destroy(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+int thip_sdpbatch_set_param(thip_sdpbatch *h, const thip_param *par) { return ob_set_param(h, par); }
+
+int thip_sdpbatch_init(thip_sdpbatch *h) { return ob_init(h, SP_TEXT); }
+
+int thip_sdpbatch_run(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
+{
+    SP_NEED(h);
+    return ob_run(h, max_steps, poll_every, host_status, false);
+}
+
+int thip_sdpbatch_run_until_any(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
+{
+    SP_NEED(h);
+    return ob_run(h, max_steps, poll_every, host_status, true);
+}
+
+int thip_sdpbatch_status(thip_sdpbatch *h, int i, thip_status *host_status)
+{
+    SP_NEED(h);
+    return ob_status(h, i, host_status);
+}
+
+int thip_sdpbatch_solution(thip_sdpbatch *h, int i, float *host_x, float *host_y)
+{
+    SP_NEED(h);
+    return ob_solution(h, i, host_x, host_y);
+}
+
+int thip_sdpbatch_iterate(thip_sdpbatch *h, int i, float *host_x, float *host_y)
+{
+    SP_NEED(h);
+    return ob_iterate(h, i, host_x, host_y);
+}
+
+int thip_sdpbatch_precond(thip_sdpbatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
+{
+    SP_NEED(h);
+    return ob_precond(h, i, host_dp_tau, host_dp_sigma);
+}
+
+int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                          const float *dev_vec_b_rowabs)
+{
+    SP_NEED(h);
+    THIP_RC(ob_replace(h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs));
+    mb_note_replaced(h, i, dev_mat_a);
+    return 0;
+}
+
+int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info)
+{
+    if (!h || !host_info) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    memset(host_info, 0, sizeof(*host_info));
+    mb_info(h, g_sp_bytes, *host_info);
+    host_info->max_psd_order = h->shape.max_k; host_info->n_psd = h->shape.n_psd;
+    host_info->psd_lds_bytes = h->shape.tail_bytes;
+    return 0;
+}
+
+int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads)
+{
+    if (!h) return fail(THIP_E_INVALID, "null SDP batch", __FILE__, __LINE__);
+    if (threads != 0 && threads != 256 && threads != 1024)
+        return fail(THIP_E_INVALID, "the workgroup size is 256 or 1024 (0: by shape)", __FILE__, __LINE__);
+    if (h->inited) return fail(THIP_E_INVALID, "thip_test_sdpbatch_force_threads comes before thip_sdpbatch_init", __FILE__, __LINE__);
+    h->forced = threads;
+    sp_plan(h);
+    return 0;
+}
+
+int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_rx_or_null)
+{
+    THIP_NEED_INIT();
+    if (k < 1 || k > SP_MAX_ORDER) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project: 1 <= k <= 64", __FILE__, __LINE__);
+    if (count < 1 || !dev_packed) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project: no matrix", __FILE__, __LINE__);
+    THIP_RC(sp_attr());
+    const size_t lds = (64 + (k <= 32 ? 4 * (size_t)SP_OP32 : 4 * (size_t)SP_OP64)) * sizeof(float);
+    hipLaunchKernelGGL(sdpbatch_project_k, dim3((unsigned)count), dim3(256), lds, ctx().stream, k, dev_packed, dev_rx_or_null);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
