@@ -1,8 +1,8 @@
 """GPU: many mid-size problems, each with its OWN A streamed from memory (totsu_amd.MidBatchSolver / thip_midbatch_*): every problem's
 iterates against the f64 oracle, edge shapes around every tiling constant of the kernel, independent termination, isolation from the
 neighbours and from the launch boundaries (bitwise), steps and limits, replace, the tau -> 0 branch, the refusals.  Every oracle
-state a test relies on is asserted first.  The families, the oracle runs and the helpers of tests/test_gpu_smallbatch.py are
-shared (computed once per session).
+state a test relies on is asserted first.  The families, the oracle runs and the helpers are those of
+tests/ownbatch_cases.py (computed once per session).
 
 The kernel's tiling constants (thip_midbatch.hip):
     ROWS   = 256   rows per wave step (a lane holds 4 consecutive rows)
@@ -18,97 +18,21 @@ import pytest
 
 import oracle as O
 import tau_zero_problems as Z
-import test_gpu_smallbatch as SBT
-from problems import benchmark_lp, random_socp
-from test_gpu_smallbatch import _D, _edge, _mb, _oracle
+from ownbatch_cases import (F, ITERS, TOLS, T, _D, _compare_snap, _dense_of, _edge, _lp_arrays, _oracle, _term_problem,  # noqa: F401
+                            _View, check_against_oracle)
+from ownbatch_cases import family as _family
 
 pytestmark = pytest.mark.gpu
 
-TOLS, ITERS, F = SBT.TOLS, SBT.ITERS, np.float32
 ROWS, CK, WAVES = 256, 8, (4, 16)
 
 
-@pytest.fixture(scope="module")
-def T():
-    import totsu_amd
-    from totsu_amd import _lib
-    _lib.init()
-    return totsu_amd
-
-
-_FAMILIES = {}
-
-
-def _family(T, name):
-    """(list of dense problems, list of oracle results at ITERS), computed once"""
-    if name in ("lp20", "socp", "qp"):
-        return SBT._family(T, name)
-    if name in _FAMILIES:
-        return _FAMILIES[name]
-    ds, ros = [], []
-    if name in ("lp80", "lp260"):
-        sz = int(name[2:])
-        for i in range(5):
-            c, G, h = benchmark_lp(sz, seed=i)
-            ds.append(_D(G, h, c, [1], [2 * sz]))
-            ros.append(_oracle(ds[-1], ITERS))
-    elif name == "socp60":
-        n, cones = 60, [5, 1, 0, 17, 140, 250, 3]
-        for i in range(3):
-            f, Gs, hs, cs, d = random_socp(n, cones, seed=i)
-            socp = T.ProbSOCP(_mb(T, T.MatType.General(n, 1)).set_array(f.reshape(-1, 1)),
-                              [_mb(T, T.MatType.General(G.shape[0], n)).set_array(G) for G in Gs],
-                              [_mb(T, T.MatType.General(len(h_), 1)).set_array(h_.reshape(-1, 1)) for h_ in hs],
-                              [_mb(T, T.MatType.General(n, 1)).set_array(c_.reshape(-1, 1)) for c_ in cs], d,
-                              _mb(T, T.MatType.General(0, n)), _mb(T, T.MatType.General(0, 1)))
-            ds.append(socp.dense())
-            assert (ds[-1].m, ds[-1].n) == (423, 60) and ds[-1].m * ds[-1].n > 24576 and ds[-1].vec_b_rowabs is not None
-            ros.append(_oracle(ds[-1], ITERS, socp=(f, Gs, hs, cs, d)))
-    for ro in ros:
-        assert ro.status == O.EXCESS_ITER and len(ro.trace) > max(ITERS)
-    _FAMILIES[name] = (ds, ros)
-    return _FAMILIES[name]
-
-
-def _check(T, label, ds, ros, iters, tols, state_arith=None, **kw):
-    p = T.SolverParam()
-    p.eps_acc = 1e-30
-    if state_arith:
-        p.state_arith = state_arith
-    sb = T.MidBatchSolver.from_dense(ds, p, **kw)
-    try:
-        n, m = ds[0].n, ds[0].m
-        N = n + 2 * m + 1
-        for i, ro in enumerate(ros):
-            t, s = sb.precond(i)
-            et, es = np.abs(t / ro.precond[:N] - 1).max(), np.abs(s / ro.precond[N:] - 1).max()
-            print("%s problem %d preconditioner: rel err tau %.2e sigma %.2e" % (label, i, et, es))
-            assert np.allclose(t, ro.precond[:N], rtol=2e-5, atol=0), (i, et)
-            assert np.allclose(s, ro.precond[N:], rtol=2e-5, atol=0), (i, es)
-        done = 0
-        for q, (it, tol) in enumerate(zip(iters, tols)):
-            sb.run(it + 1 - done, poll_every=64)
-            done = it + 1
-            for i, ro in enumerate(ros):
-                x, y = sb.iterate(i)
-                rx, ry = ro.snaps[q][:N], ro.snaps[q][N:]
-                sx, sy = max(np.abs(rx).max(), 1e-6), max(np.abs(ry).max(), 1e-6)
-                print("%s problem %d iterate %d: err x %.2e y %.2e (tol %.0e)" % (label, i, it, np.abs(x - rx).max() / sx,
-                                                                                 np.abs(y - ry).max() / sy, tol))
-                assert np.abs(x - rx).max() <= tol * sx, (i, it, np.abs(x - rx).max() / sx)
-                assert np.abs(y - ry).max() <= tol * sy, (i, it, np.abs(y - ry).max() / sy)
-                st = sb.status(i)
-                assert st.state == -1 and st.iters == it + 1
-                tr = ro.trace[it]
-                assert st.kind == tr[1]
-                assert np.allclose(st.cri, tr[2:], rtol=max(50 * tol, 1e-3), atol=1e-5), (i, it, st.cri, tr)
-        info = sb.info()
-        assert info["threads"] == (kw.get("force_threads") or info["threads"]) and info["lds_bytes"] <= 163840
-        assert info["a_bytes_per_iter"] == 8 * m * n
-        assert info["load_bytes"] == (16 if m % 4 == 0 else 4)
-        return info
-    finally:
-        sb.destroy()
+def _check(T, label, ds, ros, iters, tols, **kw):
+    info = check_against_oracle(T, T.MidBatchSolver, label, ds, ros, iters, tols, **kw)
+    n, m = ds[0].n, ds[0].m
+    assert info["a_bytes_per_iter"] == 8 * m * n
+    assert info["load_bytes"] == (16 if m % 4 == 0 else 4)
+    return info
 
 
 # ---- 1. iterates against the oracle, every problem with its own A -----------------------------------------------------------
@@ -158,17 +82,6 @@ def test_floor_edge_shape(T):
     _check(T, "edge 2000x1000", [d], [_oracle(d, ITERS[:2])], ITERS[:2], TOLS[:2])
 
 
-def _View(T, base, offset, n):
-    """a DeviceBuffer that is a window into a buffer someone else owns"""
-    class V(T.DeviceBuffer):
-        def __init__(self):                    # (no allocation)
-            self.n, self.ptr = n, base.ptr + 4 * offset
-
-        def free(self):
-            self.ptr = None
-    return V()
-
-
 def test_unaligned_a_takes_the_4_byte_path_with_the_same_bits(T):
     """m % 4 == 0 with every A one float off a 16-byte boundary: info() reports the 4-byte path, the iterates are those of the
     aligned batch bit for bit (the same lanes hold the same entries on both paths)"""
@@ -203,7 +116,7 @@ def test_unaligned_a_takes_the_4_byte_path_with_the_same_bits(T):
 def test_independent_termination(T):
     from totsu_amd import _lib
     P = 18
-    ds = [SBT._term_problem(i) for i in range(P)]
+    ds = [_term_problem(i) for i in range(P)]
     ros = [O.solve_matop_cones(O.param(max_iter=100000, eps_acc=1e-5, eps_inf=1e-5), d.vec_c, d.mat_a, d.vec_b, d.seg_type, d.seg_len,
                                trace_cap=400) for d in ds]
     want = [O.INFEASIBLE, O.OK, O.UNBOUNDED]
@@ -287,7 +200,7 @@ def test_isolation_and_reproducibility(T):
     P = 300                                            # more workgroups than the device has CUs
     seeds = list(range(P))
     seeds[P - 1] = 0                                   # the same LP at index 0 and at index 299
-    a, b, c = SBT._lp_arrays(seeds)
+    a, b, c = _lp_arrays(seeds)
     p = T.SolverParam()
     p.max_iter, p.eps_acc = 1500, 1e-3
     seg = ([_lib.CONE_RPOS], [40])
@@ -428,35 +341,6 @@ def test_replace(T):
 
 
 # ---- 7. the tau -> 0 branch ----------------------------------------------------------------------------------------------------
-
-def _dense_of(fam):
-    from totsu_amd.problem import _Dense
-    return _Dense(*fam.args())
-
-
-def _compare_snap(tag, fam, pl, it, x, y, st):
-    """the iterate after iteration `it` against the oracle's; at a decisive snap also kind, criteria and tau == 0
-    (tests/test_gpu_tau_zero.py)"""
-    N = pl.N
-    tol = fam.tol(it)
-    rx, ry = pl.snaps[it][:N], pl.snaps[it][N:]
-    sx, sy = max(np.abs(rx).max(), 1e-6), max(np.abs(ry).max(), 1e-6)
-    ex, ey = np.abs(x - rx).max() / sx, np.abs(y - ry).max() / sy
-    print("tau_zero %-22s it %2d kind %d %s err x %.2e y %.2e (tol %.0e) tau %.3e cri %s"
-          % (tag, it, pl.kinds[it], "decisive" if pl.decisive[it] else "--------", ex, ey, tol, x[N - 1], tuple("%.3e" % c for c in st.cri)))
-    assert ex <= tol and ey <= tol, (tag, it, ex, ey, tol)
-    assert st.iters == it + 1, (tag, it, st.iters)
-    if not pl.decisive[it]:
-        return
-    assert st.kind == pl.kinds[it], (tag, it, st.kind, pl.kinds[it])
-    ncri = 3 if pl.kinds[it] == 0 else 2
-    want, got = np.array(pl.cri[it][:ncri]), np.array(st.cri[:ncri])
-    assert np.array_equal(np.isinf(want), np.isinf(got)), (tag, it, got, want)
-    assert np.allclose(got, want, rtol=max(50 * tol, 1e-3), atol=1e-5), (tag, it, got, want)
-    assert (x[N - 1] == 0.0) == (rx[N - 1] == 0.0), (tag, it, x[N - 1], rx[N - 1])
-    if pl.kinds[it] == 1:
-        assert x[N - 1] == 0.0 and y[-1] <= 0.0
-
 
 def _tau_zero_batch(name):
     fams, pls = Z.family(name), Z.plan(name)

@@ -1,8 +1,8 @@
 """GPU: many small SDPs, each with its OWN A, the PSD cones projected on chip by the problem's workgroup (totsu_amd.SdpBatchSolver /
 thip_sdpbatch_*): the projection alone against the f64 oracle, every problem's iterates against the oracle, isolation from the
 neighbours, the launch boundaries and the alignment of A (bitwise), the mid batch's bits on layouts without PSD cones, independent
-termination, the tau -> 0 branch, the refusals.  Every oracle state a test relies on is asserted first.  The helpers and the LP /
-SOCP families of tests/test_gpu_smallbatch.py and tests/test_gpu_midbatch.py are shared.
+termination, the tau -> 0 branch, the refusals.  Every oracle state a test relies on is asserted first.  The families, the
+oracle runs and the helpers are those of tests/ownbatch_cases.py.
 
 The kernel's constants (thip_sdpbatch.hip): operands of extent 32 (one wave) up to order 32 and 64 (four waves) above; K walked in
 chunks of 4 MFMA steps, ceil(k / 8) of them; workgroups of 256 or 1024 threads."""
@@ -13,28 +13,15 @@ import pytest
 
 import oracle as O
 import tau_zero_problems as Z
-import test_gpu_midbatch as MBT
-from problems import partitioning_sdp, random_sdp
-from test_gpu_midbatch import _compare_snap, _dense_of
-from test_gpu_smallbatch import _D, _mb, _oracle
+from ownbatch_cases import SDP_ITERS as ITERS
+from ownbatch_cases import SDP_TOLS as TOLS
+from ownbatch_cases import (F, T, _compare_snap, _dense_of, _same, _sdp_dense, _snap, _View, check_against_oracle,  # noqa: F401
+                            tri)
+from ownbatch_cases import family as _family
 
 pytestmark = pytest.mark.gpu
 
-F = np.float32
-ITERS, TOLS = [0, 1, 9, 49], [5e-5, 5e-5, 3e-4, 3e-3]          # tests/test_gpu_solver.py::test_iterates_sdp
 LARGEST = 57                                                   # the largest order a layout can hold (tests/test_sdpbatch_cpu.py)
-
-
-@pytest.fixture(scope="module")
-def T():
-    import totsu_amd
-    from totsu_amd import _lib
-    _lib.init()
-    return totsu_amd
-
-
-def tri(k):
-    return k * (k + 1) // 2
 
 
 # ---- 1. the projection alone ---------------------------------------------------------------------------------------------------
@@ -125,125 +112,10 @@ def test_a_batch_of_projections_is_each_one_alone(T, k):
 
 # ---- 2. iterates against the oracle, every problem with its own A --------------------------------------------------------------
 
-def _sdp_dense(T, n, k, seed):
-    c, syms = random_sdp(n, k, seed=seed)
-    sdp = T.ProbSDP(_mb(T, T.MatType.General(n, 1)).set_array(c.reshape(-1, 1)),
-                    [_mb(T, T.MatType.SymPack(k)).set_array(s) for s in syms],
-                    _mb(T, T.MatType.General(0, n)), _mb(T, T.MatType.General(0, 1)), 1e-12)
-    d = sdp.dense()
-    sdp.drop()
-    return d
-
-
-def _part_dense(T, grid, seed):
-    w, syms_f, mat_a, vec_b = partitioning_sdp(*grid, seed=seed)
-    l, n = grid[0] * grid[1], w.size
-    sdp = T.ProbSDP(_mb(T, T.MatType.General(n, 1)).set_array(w.reshape(-1, 1)),
-                    [_mb(T, T.MatType.SymPack(l)).set_array(s_) for s_ in syms_f],
-                    _mb(T, T.MatType.General(l, n)).set_array(mat_a), _mb(T, T.MatType.General(l, 1)).set_array(vec_b.reshape(-1, 1)),
-                    1e-12)
-    d = sdp.dense()
-    sdp.drop()
-    assert d.seg_type == [O.CONE_PSD, O.CONE_ZERO] and d.seg_len == [n, l]
-    return d
-
-
-MIXED_ORDERS = [3, 6, 6, 12, 6, 33, 12, 1]
-
-
-def _mixed_dense(T, seed):
-    """in the manner of tests/test_gpu_solver.py::test_iterates_many_psd_cones: 3 nonnegative rows in front (no PSD block starts on a
-    multiple of 4), PSD cones of eight orders, then a second-order cone of 17 rows and a rotated one of 5"""
-    from totsu_amd import _lib
-    n = 5
-    rng = np.random.default_rng(99 + seed)
-    blocks = [rng.standard_normal((3, n)).astype(F)]
-    bs, st, sl = [np.abs(rng.standard_normal(3)).astype(F) + 1.0], [_lib.CONE_RPOS], [3]
-    c0 = np.zeros(n, F)
-    for q, k in enumerate(MIXED_ORDERS):
-        d = _sdp_dense(T, n, k, 10 + q + 100 * seed)
-        sk = tri(k)
-        blocks.append(np.asarray(d.mat_a, dtype=F).reshape((n, d.m)).T[:sk])
-        bs.append(np.asarray(d.vec_b, dtype=F)[:sk])
-        st.append(_lib.CONE_PSD)
-        sl.append(sk)
-        c0 = c0 + np.asarray(d.vec_c, dtype=F)
-    for t, rows in ((_lib.CONE_SOC, 17), (_lib.CONE_ROTSOC, 5)):   # s = b - A x with large leading entries: inside the cone at x = 0
-        blocks.append((rng.standard_normal((rows, n)) / 4).astype(F))
-        b = (rng.standard_normal(rows) / 4).astype(F)
-        b[0] = 3.0
-        if t == _lib.CONE_ROTSOC:
-            b[1] = 3.0
-        bs.append(b)
-        st.append(t)
-        sl.append(rows)
-    a = np.vstack(blocks)
-    beg = np.cumsum([0] + sl)[:-1]
-    assert all(b_ % 4 != 0 for b_, t in zip(beg, st) if t == _lib.CONE_PSD)
-    return _D(a, np.concatenate(bs), c0 / len(MIXED_ORDERS), st, sl)
-
-
-_FAMILIES = {}
-
-
-def _family(T, name):
-    """(list of dense problems, list of oracle results at ITERS), computed once"""
-    if name in _FAMILIES:
-        return _FAMILIES[name]
-    if name.startswith("sdp"):
-        ds = [_sdp_dense(T, 6, int(name[3:]), seed) for seed in range(3)]
-    elif name.startswith("part"):
-        ds = [_part_dense(T, (int(name[4]), int(name[5])), seed) for seed in range(2)]
-    else:
-        ds = [_mixed_dense(T, seed) for seed in range(2)]
-    ros = [_oracle(d, ITERS) for d in ds]
-    for ro in ros:
-        assert ro.status == O.EXCESS_ITER and len(ro.trace) > max(ITERS)
-    _FAMILIES[name] = (ds, ros)
-    return _FAMILIES[name]
-
-
-def _check(T, label, ds, ros, state_arith=None, **kw):
-    p = T.SolverParam()
-    p.eps_acc = 1e-30
-    if state_arith:
-        p.state_arith = state_arith
-    sb = T.SdpBatchSolver.from_dense(ds, p, **kw)
-    try:
-        n, m = ds[0].n, ds[0].m
-        N = n + 2 * m + 1
-        worst = [0.0] * len(ITERS)
-        for i, ro in enumerate(ros):
-            t, s = sb.precond(i)
-            et, es = np.abs(t / ro.precond[:N] - 1).max(), np.abs(s / ro.precond[N:] - 1).max()
-            print("%s problem %d preconditioner: rel err tau %.2e sigma %.2e" % (label, i, et, es))
-            assert np.allclose(t, ro.precond[:N], rtol=2e-5, atol=0), (i, et)
-            assert np.allclose(s, ro.precond[N:], rtol=2e-5, atol=0), (i, es)
-        done = 0
-        for q, (it, tol) in enumerate(zip(ITERS, TOLS)):
-            sb.run(it + 1 - done, poll_every=64)
-            done = it + 1
-            for i, ro in enumerate(ros):
-                x, y = sb.iterate(i)
-                rx, ry = ro.snaps[q][:N], ro.snaps[q][N:]
-                sx, sy = max(np.abs(rx).max(), 1e-6), max(np.abs(ry).max(), 1e-6)
-                ex, ey = np.abs(x - rx).max() / sx, np.abs(y - ry).max() / sy
-                worst[q] = max(worst[q], ex, ey)
-                print("%s problem %d iterate %d: err x %.2e y %.2e (tol %.0e)" % (label, i, it, ex, ey, tol))
-                assert ex <= tol, (i, it, ex)
-                assert ey <= tol, (i, it, ey)
-                st = sb.status(i)
-                assert st.state == -1 and st.iters == it + 1
-                tr = ro.trace[it]
-                assert st.kind == tr[1]
-                assert np.allclose(st.cri, tr[2:], rtol=max(50 * tol, 1e-3), atol=1e-5), (i, it, st.cri, tr)
-        print("%s worst iterate errors at %s: %s" % (label, ITERS, " ".join("%.2e" % w for w in worst)))
-        info = sb.info()
-        assert info["threads"] == (kw.get("force_threads") or info["threads"]) and info["lds_bytes"] <= 163840
-        assert info["a_bytes_per_iter"] == 8 * m * n
-        return info
-    finally:
-        sb.destroy()
+def _check(T, label, ds, ros, **kw):
+    info = check_against_oracle(T, T.SdpBatchSolver, label, ds, ros, ITERS, TOLS, **kw)
+    assert info["a_bytes_per_iter"] == 8 * ds[0].m * ds[0].n
+    return info
 
 
 @pytest.mark.parametrize("name", ["sdp9", "sdp24", "sdp33", "sdp48", "part23", "part44", "mixed"])
@@ -269,15 +141,6 @@ def test_iterates_plain_state(T, name):
 
 
 # ---- 3. bitwise properties -----------------------------------------------------------------------------------------------------
-
-def _snap(sb, i):
-    st = sb.status(i)
-    return sb.iterate(i) + ((st.state, st.iters, st.kind, tuple(st.cri)),)
-
-
-def _same(g, w):
-    assert np.array_equal(g[0], w[0]) and np.array_equal(g[1], w[1]) and g[2] == w[2], (g[2], w[2])
-
 
 def test_a_problem_does_not_depend_on_its_index_or_its_neighbours(T):
     ds = [_sdp_dense(T, 6, 9, seed) for seed in range(39)]
@@ -367,7 +230,7 @@ def test_unaligned_a_takes_the_4_byte_path_with_the_same_bits(T):
     i16, want = run(a)
     base = T.DeviceBuffer.from_host(np.concatenate([np.zeros(1, F), a.ravel()]))
     assert base.ptr % 16 == 0
-    i4, got = run(MBT._View(T, base, 1, a.size))
+    i4, got = run(_View(T, base, 1, a.size))
     base.free()
     assert (i16["load_bytes"], i4["load_bytes"]) == (16, 4)
     for g, w in zip(got, want):
@@ -379,7 +242,7 @@ def test_unaligned_a_takes_the_4_byte_path_with_the_same_bits(T):
 
 @pytest.mark.parametrize("name", ["lp80", "socp60"])
 def test_without_psd_cones_the_bits_are_the_mid_batch_s(T, name):
-    ds, _ = MBT._family(T, name)
+    ds, _ = _family(T, name)
     p = T.SolverParam()
     p.eps_acc = 1e-30
     out = []
@@ -547,8 +410,8 @@ def test_refusals_leave_nothing_allocated(T):
 
 
 def test_conic_batch_returns_the_batch_the_layout_needs(T):
-    lp20, _ = MBT._family(T, "lp20")
-    lp260, _ = MBT._family(T, "lp260")
+    lp20, _ = _family(T, "lp20")
+    lp260, _ = _family(T, "lp260")
     sdp9, _ = _family(T, "sdp9")
     small, mid, sdp = T.conic_batch(lp20), T.conic_batch(lp260[:2]), T.conic_batch(sdp9)
     assert (type(small), type(mid), type(sdp)) == (T.SmallBatchSolver, T.MidBatchSolver, T.SdpBatchSolver)

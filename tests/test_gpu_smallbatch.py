@@ -1,136 +1,19 @@
 """GPU: many small problems, each with its OWN A, iterated on chip (totsu_amd.SmallBatchSolver / thip_smallbatch_*): every problem's
 iterates against the f64 oracle, edge shapes, independent termination, isolation from the neighbours, steps and limits, replace,
-the refusals.  Every oracle state a test relies on is asserted first (confirmed on the CPU)."""
+the refusals.  Every oracle state a test relies on is asserted first (confirmed on the CPU).  The families, the oracle runs and the
+helpers are those of tests/ownbatch_cases.py."""
 import numpy as np
 import pytest
 
 import oracle as O
-from problems import benchmark_lp, random_socp, svm_qp
+from ownbatch_cases import F, ITERS, TOLS, T, _D, _edge, _lp_arrays, _oracle, _term_problem, check_against_oracle  # noqa: F401
+from ownbatch_cases import family as _family
 
 pytestmark = pytest.mark.gpu
 
-TOLS = [2e-5, 2e-5, 1e-4, 2e-3]      # iterates 0, 1, 9, 99 relative to the iterate's max norm (tests/test_gpu_solver.py)
-ITERS = [0, 1, 9, 99]
-F = np.float32
 
-
-@pytest.fixture(scope="module")
-def T():
-    import totsu_amd
-    from totsu_amd import _lib
-    _lib.init()
-    return totsu_amd
-
-
-def _mb(T, typ):
-    return T.MatBuild(T.F32HIP, typ)
-
-
-class _D:
-    """the fields of Prob*.dense() for problems built from arrays"""
-
-    def __init__(self, a, b, c, seg_type, seg_len):
-        a = np.asarray(a, F)
-        self.m, self.n = a.shape
-        self.mat_a, self.vec_b, self.vec_c = np.asfortranarray(a).ravel(order="F"), np.asarray(b, F), np.asarray(c, F)
-        self.seg_type, self.seg_len, self.vec_b_rowabs = list(seg_type), list(seg_len), None
-
-
-def _oracle(d, iters, socp=None):
-    """the oracle's snapshots, trace and preconditioner of one problem.  socp: the ProbSOCP pieces -- its op_b adds scl_d, not
-    |scl_d|, to the row sums (what dense().vec_b_rowabs carries), so the SOCP oracle is the SOCP one"""
-    par = O.param(max_iter=max(iters) + 2, eps_acc=1e-30)
-    if socp is not None:
-        f, Gs, hs, cs, dd = socp
-        return O.solve_socp(par, f, Gs, hs, cs, dd, np.zeros((0, f.size)), [], trace_cap=max(iters) + 3, snap_iters=iters)
-    return O.solve_matop_cones(par, d.vec_c, d.mat_a, d.vec_b, d.seg_type, d.seg_len, snap_iters=iters, trace_cap=max(iters) + 3,
-                               use_ql=True)
-
-
-_FAMILIES = {}
-
-
-def _family(T, name):
-    """(list of dense problems, list of oracle results at ITERS): computed once, shared by every test that uses the family"""
-    if name in _FAMILIES:
-        return _FAMILIES[name]
-    ds, ros = [], []
-    if name in ("lp20", "lp40"):
-        sz = int(name[2:])
-        for i in range(5):
-            c, G, h = benchmark_lp(sz, seed=i)
-            lp = T.ProbLP(_mb(T, T.MatType.General(sz, 1)).set_array(c.reshape(-1, 1)), _mb(T, T.MatType.General(2 * sz, sz)).set_array(G),
-                          _mb(T, T.MatType.General(2 * sz, 1)).set_array(h.reshape(-1, 1)), _mb(T, T.MatType.General(0, sz)),
-                          _mb(T, T.MatType.General(0, 1)))
-            ds.append(lp.dense())
-            ros.append(_oracle(ds[-1], ITERS))
-    elif name == "socp":
-        n, cones = 12, [5, 1, 0, 17, 70, 3]
-        for i in range(4):
-            f, Gs, hs, cs, d = random_socp(n, cones, seed=i)
-            socp = T.ProbSOCP(_mb(T, T.MatType.General(n, 1)).set_array(f.reshape(-1, 1)),
-                              [_mb(T, T.MatType.General(G.shape[0], n)).set_array(G) for G in Gs],
-                              [_mb(T, T.MatType.General(len(h_), 1)).set_array(h_.reshape(-1, 1)) for h_ in hs],
-                              [_mb(T, T.MatType.General(n, 1)).set_array(c_.reshape(-1, 1)) for c_ in cs], d,
-                              _mb(T, T.MatType.General(0, n)), _mb(T, T.MatType.General(0, 1)))
-            ds.append(socp.dense())
-            assert (ds[-1].m, ds[-1].n) == (102, 12) and ds[-1].vec_b_rowabs is not None
-            ros.append(_oracle(ds[-1], ITERS, socp=(f, Gs, hs, cs, d)))
-    elif name == "qp":
-        l = 12
-        for i in range(3):
-            q = svm_qp(l, seed=i)
-            qp = T.ProbQP(_mb(T, T.MatType.SymPack(l)).set_by_fn(lambda r, c: q["sym_p"][r, c]),
-                          _mb(T, T.MatType.General(l, 1)).set_array(q["vec_q"].reshape(-1, 1)),
-                          _mb(T, T.MatType.General(l, l)).set_array(q["mat_g"]),
-                          _mb(T, T.MatType.General(l, 1)).set_array(q["vec_h"].reshape(-1, 1)),
-                          _mb(T, T.MatType.General(1, l)).set_array(q["mat_a"]),
-                          _mb(T, T.MatType.General(1, 1)).set_array(q["vec_b"].reshape(-1, 1)), 1e-12)
-            ds.append(qp.dense())
-            assert (ds[-1].m, ds[-1].n) == (27, 13) and ds[-1].seg_type == [3, 1, 0]
-            ros.append(_oracle(ds[-1], ITERS))          # (on the dense A itself: its P^(1/2) is the device's f32 one)
-    for ro in ros:
-        assert ro.status == O.EXCESS_ITER and len(ro.trace) > max(ITERS)
-    _FAMILIES[name] = (ds, ros)
-    return _FAMILIES[name]
-
-
-def _check(T, label, ds, ros, iters, tols, state_arith=None, **kw):
-    p = T.SolverParam()
-    p.eps_acc = 1e-30
-    if state_arith:
-        p.state_arith = state_arith
-    sb = T.SmallBatchSolver.from_dense(ds, p, **kw)
-    try:
-        n, m = ds[0].n, ds[0].m
-        N = n + 2 * m + 1
-        for i, ro in enumerate(ros):
-            t, s = sb.precond(i)
-            et, es = np.abs(t / ro.precond[:N] - 1).max(), np.abs(s / ro.precond[N:] - 1).max()
-            print("%s problem %d preconditioner: rel err tau %.2e sigma %.2e" % (label, i, et, es))
-            assert np.allclose(t, ro.precond[:N], rtol=2e-5, atol=0), (i, et)
-            assert np.allclose(s, ro.precond[N:], rtol=2e-5, atol=0), (i, es)
-        done = 0
-        for q, (it, tol) in enumerate(zip(iters, tols)):
-            sb.run(it + 1 - done, poll_every=64)
-            done = it + 1
-            for i, ro in enumerate(ros):
-                x, y = sb.iterate(i)
-                rx, ry = ro.snaps[q][:N], ro.snaps[q][N:]
-                sx, sy = max(np.abs(rx).max(), 1e-6), max(np.abs(ry).max(), 1e-6)
-                print("%s problem %d iterate %d: err x %.2e y %.2e (tol %.0e)" % (label, i, it, np.abs(x - rx).max() / sx,
-                                                                                 np.abs(y - ry).max() / sy, tol))
-                assert np.abs(x - rx).max() <= tol * sx, (i, it, np.abs(x - rx).max() / sx)
-                assert np.abs(y - ry).max() <= tol * sy, (i, it, np.abs(y - ry).max() / sy)
-                st = sb.status(i)
-                assert st.state == -1 and st.iters == it + 1
-                tr = ro.trace[it]
-                assert st.kind == tr[1]
-                assert np.allclose(st.cri, tr[2:], rtol=max(50 * tol, 1e-3), atol=1e-5), (i, it, st.cri, tr)
-        info = sb.info()
-        assert info["threads"] == (kw.get("force_threads") or info["threads"]) and info["lds_bytes"] <= 163840
-    finally:
-        sb.destroy()
+def _check(T, label, ds, ros, iters, tols, **kw):
+    check_against_oracle(T, T.SmallBatchSolver, label, ds, ros, iters, tols, **kw)
 
 
 # ---- 1. iterates against the oracle, every problem with its own A -----------------------------------------------------------
@@ -154,14 +37,6 @@ def test_iterates_plain_state(T):
 
 
 # ---- 2. edge shapes ----------------------------------------------------------------------------------------------------------
-
-def _edge(m, n, seed):
-    """a primal- and dual-feasible LP over the nonnegative cone: b = A x0 + s0, c = -A^T y0, s0, y0 ~ U(0.1, 1.1)"""
-    rng = np.random.default_rng(1000 * m + n + 7919 * seed)
-    A = (rng.standard_normal((m, n)) / np.sqrt(n)).astype(F)
-    x0, s0, y0 = rng.standard_normal(n), rng.uniform(0.1, 1.1, m), rng.uniform(0.1, 1.1, m)
-    return _D(A, A.astype(np.float64) @ x0 + s0, -A.astype(np.float64).T @ y0, [1], [m])
-
 
 EDGE_SHAPES = [(1, 1), (2, 1), (3, 2), (65, 33), (129, 190), (192, 128), (1024, 24), (24, 1024)]
 
@@ -198,16 +73,6 @@ def test_edge_shapes_converge(T, m, n):
 
 
 # ---- 3. independent termination ------------------------------------------------------------------------------------------------
-
-def _term_problem(i):
-    """three kinds over A = [D; -D], D = diag(U(0.5, 1.5)), two unknowns: 0 an infeasible box (b = -1), 1 a feasible box (b = 1),
-    2 the upper bounds alone (the rows of -D are zero) with c = (1, 1): unbounded"""
-    rng = np.random.default_rng(100 + i)
-    D = np.diag(rng.uniform(0.5, 1.5, 2))
-    k = i % 3
-    A = np.vstack([D, -D if k < 2 else 0.0 * D])
-    return _D(A, -np.ones(4) if k == 0 else np.ones(4), np.ones(2), [1], [4])
-
 
 def test_independent_termination(T):
     from totsu_amd import _lib
@@ -255,16 +120,6 @@ def test_independent_termination(T):
 
 
 # ---- 4. isolation and reproducibility ------------------------------------------------------------------------------------------
-
-def _lp_arrays(seeds):
-    a, b, c = [], [], []
-    for s in seeds:
-        cc, G, h = benchmark_lp(20, seed=s)
-        a.append(np.asfortranarray(G).ravel(order="F"))
-        b.append(h)
-        c.append(cc)
-    return np.stack(a), np.stack(b), np.stack(c)
-
 
 def test_isolation_and_reproducibility(T):
     from totsu_amd import _lib

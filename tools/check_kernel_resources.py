@@ -84,69 +84,36 @@ def check_gemv_multi(res):
     return 0
 
 
-def check_smallbatch(res):
-    bad, seen = [], 0
-    for name, r in sorted(res.items()):
-        if not re.search(r"smallbatch(_init)?_k", name) or "scratch" not in r:
-            continue
-        seen += 1
-        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4
-        if "--report" in sys.argv or not ok:
-            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
-                                                                                 r["scratch"], r.get("occupancy", -1)))
-        if not ok:
-            bad.append(name)
-    if seen < 2:
-        print("check_kernel_resources: smallbatch_k / smallbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
-        return 2
-    if bad:
-        print("check_kernel_resources: FAILED for %s: scratch in use or < 4 waves/SIMD -- a 1024-thread workgroup of the on-chip "
-              "small-batch kernel no longer fits a CU (thip_smallbatch.hip)" % bad)
-        return 1
-    return 0
+# the own-A batch families: kernel-name regex, the kernels that must be present, the VGPR cap (None: the occupancy bound alone),
+# the kernel's description and its source file for the message
+OWNBATCH = {
+    "smallbatch": (r"smallbatch(_init)?_k", ("smallbatch_k", "smallbatch_init_k"), None, "on-chip small-batch", "thip_smallbatch.hip"),
+    "midbatch": (r"midbatch(_init)?_k", ("midbatch_k", "midbatch_init_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
+    "sdpbatch": (r"sdpbatch(_init|_project)?_k", ("sdpbatch_k", "sdpbatch_init_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
+}
 
 
-def check_midbatch(res):
-    bad, seen = [], 0
-    for name, r in sorted(res.items()):
-        if not re.search(r"midbatch(_init)?_k", name) or "scratch" not in r:
-            continue
-        seen += 1
-        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4
-        if "--report" in sys.argv or not ok:
-            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
-                                                                                 r["scratch"], r.get("occupancy", -1)))
-        if not ok:
-            bad.append(name)
-    if seen < 2:
-        print("check_kernel_resources: midbatch_k / midbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
-        return 2
-    if bad:
-        print("check_kernel_resources: FAILED for %s: scratch in use or < 4 waves/SIMD -- a 1024-thread workgroup of the streamed "
-              "mid-size batch kernel no longer fits a CU (thip_midbatch.hip)" % bad)
-        return 1
-    return 0
-
-
-def check_sdpbatch(res):
+def check_ownbatch(res, family):
+    pat, need, max_vgprs, what, src = OWNBATCH[family]
     bad, seen = [], set()
     for name, r in sorted(res.items()):
-        m = re.search(r"sdpbatch(_init|_project)?_k", name)
+        m = re.search(pat, name)
         if not m or "scratch" not in r:
             continue
         seen.add(m.group(0))
-        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4 and r.get("vgprs", 999) <= 128
+        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4 and (max_vgprs is None or r.get("vgprs", 999) <= max_vgprs)
         if "--report" in sys.argv or not ok:
             print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
                                                                                  r["scratch"], r.get("occupancy", -1)))
         if not ok:
             bad.append(name)
-    if not {"sdpbatch_k", "sdpbatch_init_k"} <= seen:
-        print("check_kernel_resources: sdpbatch_k / sdpbatch_init_k not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?")
+    if not set(need) <= seen:
+        print("check_kernel_resources: %s not in the remarks -- was -Rpass-analysis=kernel-resource-usage passed?" % " / ".join(need))
         return 2
     if bad:
-        print("check_kernel_resources: FAILED for %s: scratch in use, > 128 VGPRs or < 4 waves/SIMD -- a 1024-thread workgroup of the SDP "
-              "batch kernel no longer fits a CU (thip_sdpbatch.hip)" % bad)
+        bounds = "scratch in use or < 4 waves/SIMD" if max_vgprs is None else "scratch in use, > %d VGPRs or < 4 waves/SIMD" % max_vgprs
+        print("check_kernel_resources: FAILED for %s: %s -- a 1024-thread workgroup of the %s kernel no longer fits a CU (%s)"
+              % (bad, bounds, what, src))
         return 1
     return 0
 
@@ -154,13 +121,10 @@ def check_sdpbatch(res):
 def main():
     txt = open(sys.argv[1]).read()
     res = parse(txt)
-    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "sdpbatch":
-        return check_sdpbatch(res)
-    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "smallbatch":
-        return check_smallbatch(res)
-    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "midbatch":
-        return check_midbatch(res)
-    if "--family" in sys.argv and sys.argv[sys.argv.index("--family") + 1] == "gemv_multi":
+    family = sys.argv[sys.argv.index("--family") + 1] if "--family" in sys.argv else "sweep"
+    if family in OWNBATCH:
+        return check_ownbatch(res, family)
+    if family == "gemv_multi":
         return check_gemv_multi(res)
     bad, seen = [], 0
     for name, r in sorted(res.items()):

@@ -226,51 +226,6 @@ PROTOTYPES = {
     "thip_batch_counters": (_i, [_vp, C.POINTER(BatchCounters)]),
     "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
-    "thip_smallbatch_fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
-    "thip_smallbatch_create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                    C.POINTER(Param), C.POINTER(_vp)]),
-    "thip_smallbatch_set_param": (_i, [_vp, C.POINTER(Param)]),
-    "thip_smallbatch_init": (_i, [_vp]),
-    "thip_smallbatch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_smallbatch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_smallbatch_status": (_i, [_vp, _i, C.POINTER(Status)]),
-    "thip_smallbatch_solution": (_i, [_vp, _i, _vp, _vp]),
-    "thip_smallbatch_iterate": (_i, [_vp, _i, _vp, _vp]),
-    "thip_smallbatch_precond": (_i, [_vp, _i, _vp, _vp]),
-    "thip_smallbatch_replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "thip_smallbatch_info": (_i, [_vp, C.POINTER(SmallBatchInfo)]),
-    "thip_smallbatch_destroy": (_i, [_vp]),
-    "thip_test_smallbatch_force_threads": (_i, [_vp, _i]),
-    "thip_midbatch_fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
-    "thip_midbatch_create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                  C.POINTER(Param), C.POINTER(_vp)]),
-    "thip_midbatch_set_param": (_i, [_vp, C.POINTER(Param)]),
-    "thip_midbatch_init": (_i, [_vp]),
-    "thip_midbatch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_midbatch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_midbatch_status": (_i, [_vp, _i, C.POINTER(Status)]),
-    "thip_midbatch_solution": (_i, [_vp, _i, _vp, _vp]),
-    "thip_midbatch_iterate": (_i, [_vp, _i, _vp, _vp]),
-    "thip_midbatch_precond": (_i, [_vp, _i, _vp, _vp]),
-    "thip_midbatch_replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "thip_midbatch_info": (_i, [_vp, C.POINTER(MidBatchInfo)]),
-    "thip_midbatch_destroy": (_i, [_vp]),
-    "thip_test_midbatch_force_threads": (_i, [_vp, _i]),
-    "thip_sdpbatch_fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
-    "thip_sdpbatch_create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                  C.POINTER(Param), C.POINTER(_vp)]),
-    "thip_sdpbatch_set_param": (_i, [_vp, C.POINTER(Param)]),
-    "thip_sdpbatch_init": (_i, [_vp]),
-    "thip_sdpbatch_run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_sdpbatch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
-    "thip_sdpbatch_status": (_i, [_vp, _i, C.POINTER(Status)]),
-    "thip_sdpbatch_solution": (_i, [_vp, _i, _vp, _vp]),
-    "thip_sdpbatch_iterate": (_i, [_vp, _i, _vp, _vp]),
-    "thip_sdpbatch_precond": (_i, [_vp, _i, _vp, _vp]),
-    "thip_sdpbatch_replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "thip_sdpbatch_info": (_i, [_vp, C.POINTER(SdpBatchInfo)]),
-    "thip_sdpbatch_destroy": (_i, [_vp]),
-    "thip_test_sdpbatch_force_threads": (_i, [_vp, _i]),
     "thip_test_sdpbatch_project": (_i, [_i, _i, _vp, _vp]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -279,6 +234,27 @@ PROTOTYPES = {
     "thip_gen_identity": (_i, [_vp, _sz, _sz, _sz, _u64, _f]),
     "thip_gen_matrix": (_i, [_vp, _sz, _sz, _sz, _u64, _u64, _u64, _u64, _u64, _i, _f, _f]),
 }
+
+# the own-A batch families share one C API (totsu_amd/csrc/thip_ownbatch.h): the same signatures under each prefix
+for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo), ("sdpbatch", SdpBatchInfo)):
+    _p = "thip_%s_" % _name
+    PROTOTYPES.update({
+        _p + "fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
+        _p + "create": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(Param),
+                             C.POINTER(_vp)]),
+        _p + "set_param": (_i, [_vp, C.POINTER(Param)]),
+        _p + "init": (_i, [_vp]),
+        _p + "run": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+        _p + "run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
+        _p + "status": (_i, [_vp, _i, C.POINTER(Status)]),
+        _p + "solution": (_i, [_vp, _i, _vp, _vp]),
+        _p + "iterate": (_i, [_vp, _i, _vp, _vp]),
+        _p + "precond": (_i, [_vp, _i, _vp, _vp]),
+        _p + "replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+        _p + "info": (_i, [_vp, C.POINTER(_info)]),
+        _p + "destroy": (_i, [_vp]),
+        "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
+    })
 
 _NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen"}
 

@@ -1,7 +1,8 @@
 // thip_midstream.h -- what the two batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
 // second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip): the LDS map of a problem's vectors, the pass over A
-// (mb_pass), the init kernel's body and the iteration's body -- the carried recurrence, two passes per iteration, every vector in
-// LDS -- with one hook in the block-cone phase between the two passes, and the host pieces that do not depend on the cones.
+// (mb_pass), the iteration's body -- the carried recurrence, two passes per iteration, every vector in LDS -- with one hook in the
+// block-cone phase between the two passes, the thread choice and what both add to the info record.  The init kernel's body, the
+// criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
 // Included once by each of the two translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
@@ -24,19 +25,7 @@
 namespace {
 
 constexpr int MB_ROWS = 256, MB_CK = 8, MB_SCRH = 4096, MB_SCRG = 2048;
-constexpr size_t MB_MAX_DIM = 4096, MB_LDS_MAX = OB_LDS_MAX;
-
-struct MbArgs {
-    int n, m, n_cones, comp, steps;
-    int first;                              // live == NULL: workgroup k serves problem first + k
-    const int *live;                        // else problem live[k]
-    const SbSlot *slots;
-    float *arena; size_t stride;            // problem p's state: arena + p * stride
-    SbStatus *st;
-    const unsigned char *cls;               // 0 zero cone, 1 nonnegative, 2 member of a block cone
-    const int *cones;                       // (beg, end, kind) per block cone: 0 second-order, 1 rotated, 1 + k a PSD cone of order k
-    float eps_acc, eps_inf, eps_zero; long long max_iter;
-};
+constexpr size_t MB_MAX_DIM = 4096;
 
 struct MbMap {
     int sh, hp, gp, xx, u, kx, ku, xy, xs, v, ky, ks, kv, Tx, Ty, Ts, Sv, hx, gx, b, c, rxs, g, h, cls, floats;
@@ -171,77 +160,26 @@ extern __shared__ float mb_lds[];
 // the block-cone phase of a family without PSD cones: nothing beside the second-order cones
 struct MbNoPsd {
     static constexpr bool psd = false;
-    __device__ __forceinline__ void operator()(float *, const MbMap &, const MbArgs &) const {}
+    __device__ __forceinline__ void operator()(float *, const MbMap &, const ObArgs &) const {}
 };
 
-// calc_norms, calc_precond and init_vecs (solver.rs:460-524) of one problem per workgroup, as smallbatch_init_k, with the |A| sums
-// from one streamed pass.  product_group takes the minimum over every block cone, second-order or PSD
-__device__ __forceinline__ void mb_init_body(const MbArgs &a)
+// ob_init_body with the |A| sums from one streamed pass
+__device__ __forceinline__ void mb_init_body(const ObArgs &a)
 {
-    const int p = a.live ? a.live[blockIdx.x] : a.first + (int)blockIdx.x;
-    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const int n = a.n, m = a.m;
     const MbMap L(n, m);
     float *S = mb_lds;
-    const SbSlot sl = a.slots[p];
-    for (int i = tid; i < m; i += T) S[L.b + i] = sl.b[i];
-    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
-    __syncthreads();
-    float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };              // sum b^2, sum |b|, sum c^2, sum |c|
-    for (int i = tid; i < m; i += T) { const float t = S[L.b + i]; q[0] = fmaf(t, t, q[0]); q[1] += fabsf(t); }
-    for (int i = tid; i < n; i += T) { const float t = S[L.c + i]; q[2] = fmaf(t, t, q[2]); q[3] += fabsf(t); }
-    block_sums<4>(q, S + L.sh);
-    mb_pass<true>(sl.a, mb_vec(sl.a, m), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);      // |A| row / column sums
-    float *ar = a.arena + (size_t)p * a.stride;
-    float *gTx = ar + 4 * n + 6 * m, *gTy = gTx + n, *gTs = gTy + m, *gSv = gTs + m, *gcar = gSv + m;
-    for (int i = tid; i < n; i += T) {
-        const float t = S[L.g + i] + fabsf(S[L.c + i]);
-        gTx[i] = 1.0f / fmaxf(t, a.eps_zero);
-    }
-    for (int i = tid; i < m; i += T) {
-        const float t = S[L.h + i] + (sl.rowabs ? sl.rowabs[i] : fabsf(S[L.b + i]));
-        S[L.Ty + i] = 1.0f / fmaxf(t, a.eps_zero);
-        S[L.Ts + i] = 1.0f / fmaxf(1.0f, a.eps_zero);
-        gSv[i] = 1.0f / fmaxf(t + 1.0f, a.eps_zero);
-    }
-    __syncthreads();
-    {   // product_group (solver.rs:509-523): the minimum over each block cone, one wave per cone
-        const int lane = tid & 63, w = tid >> 6, nw = T >> 6;
-        for (int k = w; k < a.n_cones; k += nw) {
-            const int beg = a.cones[3 * k], end = a.cones[3 * k + 1];
-            for (int which = 0; which < 2; ++which) {
-                float *t = S + (which ? L.Ts : L.Ty);
-                float mn = __builtin_inff();
-                for (int i = beg + lane; i < end; i += 64) mn = fminf(mn, t[i]);
-                mn = wave_min(mn);
-                for (int i = beg + lane; i < end; i += 64) t[i] = mn;
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < m; i += T) { gTy[i] = S[L.Ty + i]; gTs[i] = S[L.Ts + i]; }
-    for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
-    for (int i = tid; i < m + n; i += T) gcar[i] = 0.0f;            // A 0, A^T 0
-    if (tid == 0) {
-        SbStatus s;
-        s.stop = 0; s.state = THIP_ST_RUNNING; s.kind = 0; s.pad = 0; s.iter = 0;
-        s.cri[0] = s.cri[1] = s.cri[2] = 0.0f;
-        s.tau = 1.0f; s.kappa = 0.0f; s.r_tau = 0.0f;
-        const float nb = sqrtf(q[0]), nc = sqrtf(q[2]);      // fr_norm (solver.rs:85-107)
-        s.norm_b = sqrtf(nb * nb);
-        s.norm_c = sqrtf(nc * nc);
-        const float tau_tau = q[3] + q[1];
-        s.t_tau = 1.0f / fmaxf(tau_tau, a.eps_zero);
-        s.s_kappa = 1.0f / fmaxf(tau_tau, a.eps_zero);
-        a.st[p] = s;
-    }
+    ob_init_body(a, ob_problem(a.live, a.first), L, S, [&](const float *A) {
+        mb_pass<true>(A, mb_vec(A, m), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
+    });
 }
 
 // `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
 // (called by every thread, after the second-order cones; hp, gp and g are dead there)
 template <class PSD>
-__device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_cones)
+__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones)
 {
-    const int p = a.live ? a.live[blockIdx.x] : a.first + (int)blockIdx.x;
+    const int p = ob_problem(a.live, a.first);
     SbStatus *const gst = a.st + p;
     if (gst->stop != 0) return;
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -269,11 +207,8 @@ __device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_
     }
     for (int i = tid; i < m; i += T) { S[L.b + i] = sl.b[i]; cls[i] = a.cls[i]; }
     for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
-    float tau = gst->tau, kappa = gst->kappa, rtau = gst->r_tau;
-    const float norm_b = gst->norm_b, norm_c = gst->norm_c, t_tau = gst->t_tau, s_kappa = gst->s_kappa;
-    long long iter = gst->iter;
-    int state = THIP_ST_RUNNING, kind = gst->kind;
-    float cri0 = gst->cri[0], cri1 = gst->cri[1], cri2 = gst->cri[2];
+    ObScalars s;
+    s.load(gst);
     __syncthreads();
 
     for (int step = 0; step < a.steps; ++step) {
@@ -284,11 +219,11 @@ __device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_
         mb_pass<false>(A, vec, m, n, u, v, h, g, hp, gp);
         block_sums<4>(q, sh);
         const float cx_old = q[2], by_old = q[3];
-        for (int i = tid; i < n; i += T) xx[i] = sb_comp_add(xx[i], Tx[i] * (g[i] + c[i] * kappa), kx, i, comp);
+        for (int i = tid; i < n; i += T) xx[i] = sb_comp_add(xx[i], Tx[i] * (g[i] + c[i] * s.kappa), kx, i, comp);
         for (int i = tid; i < m; i += T) {
             const unsigned char k = cls[i];
             const float oy = xy[i], os = xs[i];
-            float ny = sb_comp_add(oy, Ty[i] * (b[i] * kappa - h[i]), ky, i, comp);
+            float ny = sb_comp_add(oy, Ty[i] * (b[i] * s.kappa - h[i]), ky, i, comp);
             float ns = sb_comp_add(os, Ts[i] * v[i], ks, i, comp);
             if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
             else if (k == 0) { ns = 0.0f; }
@@ -298,9 +233,9 @@ __device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_
             rxs[i] = (k < 2) ? os - 2.0f * ns : os;
         }
         {
-            const float old = tau;
-            tau = fmaxf(old + t_tau * (-q[0] - q[1]), 0.0f);      // solver.rs:551-552
-            rtau = old - 2.0f * tau;
+            const float old = s.tau;
+            s.tau = fmaxf(old + s.t_tau * (-q[0] - q[1]), 0.0f);      // solver.rs:551-552
+            s.rtau = old - 2.0f * s.tau;
         }
         __syncthreads();
         // ---- the block cones: one wave per second-order cone, x_y then x_s; then the family's PSD cones ----
@@ -315,64 +250,23 @@ __device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_
         psd_cones(S, L, a);
         // ---- h = A x_x, g = A^T x_y of the new iterate: the criteria, and K rx = K x_k - 2 K x_{k+1} ----
         mb_pass<false>(A, vec, m, n, xx, xy, h, g, hp, gp);
-        const bool conv = tau > a.eps_zero;
-        const float rt = conv ? 1.0f / tau : 1.0f;
-        q[0] = q[1] = q[2] = q[3] = 0.0f;                          // ||p||^2, b.x_y, ||d||^2, c.x_x
-        for (int i = tid; i < m; i += T) {
-            const float bi = b[i];
-            float pr;
-            if (conv) { pr = xs[i] * rt - bi; pr = fmaf(rt, h[i], pr); }
-            else pr = xs[i] + h[i];
-            q[0] = fmaf(pr, pr, q[0]);
-            q[1] = fmaf(bi, xy[i], q[1]);
-        }
-        for (int i = tid; i < n; i += T) {
-            const float ci = c[i];
-            const float d = conv ? fmaf(rt, g[i], ci) : g[i];
-            q[2] = fmaf(d, d, q[2]);
-            q[3] = fmaf(ci, xx[i], q[3]);
-        }
-        block_sums<4>(q, sh);
+        ob_criteria_sums(q, n, m, s.tau, a.eps_zero, b, c, xx, xy, xs, h, g, sh);
         const float pp = q[0], by = q[1], dd = q[2], cx = q[3];
         // ---- y += S o (-K rx) (ycrit_k), the pair carried on ----
         for (int i = tid; i < n; i += T) {
             const float gn = g[i];
-            u[i] = sb_comp_add(u[i], Tx[i] * (-(gx[i] - 2.0f * gn) - c[i] * rtau), ku, i, comp);
+            u[i] = sb_comp_add(u[i], Tx[i] * (-(gx[i] - 2.0f * gn) - c[i] * s.rtau), ku, i, comp);
             gx[i] = gn;
         }
         for (int i = tid; i < m; i += T) {
             const float hn = h[i];
-            v[i] = sb_comp_add(v[i], Sv[i] * ((hx[i] - 2.0f * hn) + rxs[i] - b[i] * rtau), kv, i, comp);
+            v[i] = sb_comp_add(v[i], Sv[i] * ((hx[i] - 2.0f * hn) + rxs[i] - b[i] * s.rtau), kv, i, comp);
             hx[i] = hn;
         }
-        kappa = fminf(kappa + s_kappa * ((cx_old - 2.0f * cx) + (by_old - 2.0f * by)), 0.0f);     // solver.rs:566-567
-        // ---- status_eval ----
-        const bool excess_iter = (a.max_iter >= 0) ? (iter + 1 >= a.max_iter) : false;
-        const float norm_p = sqrtf(pp), norm_d = sqrtf(dd);
-        if (conv) {
-            const float g_x = rt * cx;
-            const float g_y = rt * by;
-            const float gg = g_x + g_y;
-            kind = 0;
-            cri0 = norm_p / (1.0f + norm_b);
-            cri1 = norm_d / (1.0f + norm_c);
-            cri2 = fabsf(gg) / (1.0f + fabsf(g_x) + fabsf(g_y));
-            const bool term_conv = (cri0 <= a.eps_acc) && (cri1 <= a.eps_acc) && (cri2 <= a.eps_acc);
-            if (term_conv) state = THIP_ST_OK;
-            else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-        } else {
-            const float m_cx = -cx;
-            const float m_by = -by;
-            kind = 1;
-            cri0 = (m_cx > a.eps_zero) ? norm_p * norm_c / m_cx : __builtin_inff();
-            cri1 = (m_by > a.eps_zero) ? norm_d * norm_b / m_by : __builtin_inff();
-            cri2 = 0.0f;
-            if (cri0 <= a.eps_inf) state = THIP_ST_UNBOUNDED;
-            else if (cri1 <= a.eps_inf) state = THIP_ST_INFEASIBLE;
-            else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-        }
-        if (state != THIP_ST_RUNNING) break;                       // (uniform: every thread holds the same sums)
-        iter += 1;
+        s.kappa = fminf(s.kappa + s.s_kappa * ((cx_old - 2.0f * cx) + (by_old - 2.0f * by)), 0.0f);     // solver.rs:566-567
+        ob_status_eval(s, ObLimits{ a.eps_acc, a.eps_inf, a.eps_zero, a.max_iter }, pp, by, dd, cx);
+        if (s.state != THIP_ST_RUNNING) break;                     // (uniform: every thread holds the same sums)
+        s.iter += 1;
     }
 
     // ---- store ----
@@ -383,62 +277,22 @@ __device__ __forceinline__ void mb_iterate_body(const MbArgs &a, const PSD &psd_
         float *const gcar = ar + 5 * n + 9 * m;
         for (int i = tid; i < m + n; i += T) gcar[i] = hx[i];      // (gx follows hx)
     }
-    if (tid == 0) {
-        gst->tau = tau; gst->kappa = kappa; gst->r_tau = rtau; gst->iter = iter;
-        gst->kind = kind; gst->cri[0] = cri0; gst->cri[1] = cri1; gst->cri[2] = cri2;
-        gst->state = state;
-        gst->stop = state != THIP_ST_RUNNING ? 1 : 0;
-    }
+    if (tid == 0) s.store(gst);
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 int mb_threads_for(size_t n, size_t m) { return n * m <= 8192 ? 256 : 1024; }
 
-// a handle of either family: which slots hold an A that is not 16-byte aligned decides the load path info() reports
-struct MbHandle : OwnBatch {
-    std::vector<unsigned char> unaligned;   // per slot: the problem's A is not 16-byte aligned
-    size_t n_unaligned = 0;
-};
-
-void mb_note_alignment(MbHandle *h, const float *dev_mats_a)
-{
-    h->unaligned.assign(h->n_prob, 0);
-    for (size_t p = 0; p < h->n_prob; ++p) {
-        h->unaligned[p] = (((uintptr_t)(dev_mats_a + p * h->m * h->n)) & 15u) != 0;
-        h->n_unaligned += h->unaligned[p];
-    }
-}
-
-void mb_note_replaced(MbHandle *h, int i, const float *dev_mat_a)
-{
-    const unsigned char un = ((uintptr_t)dev_mat_a & 15u) != 0;
-    h->n_unaligned += un;
-    h->n_unaligned -= h->unaligned[(size_t)i];
-    h->unaligned[(size_t)i] = un;
-}
-
-MbArgs mb_args(const OwnBatch *h)
-{
-    MbArgs a{};
-    a.n = (int)h->n; a.m = (int)h->m; a.n_cones = (int)(h->cones.size() / 3);
-    a.comp = h->par.state_arith == THIP_STATE_COMPENSATED; a.steps = 0; a.first = 0; a.live = nullptr;
-    a.slots = h->slots; a.arena = h->arena; a.stride = h->stride; a.st = h->dst; a.cls = h->cls_dev; a.cones = h->cones_dev;
-    a.eps_acc = h->par.eps_acc; a.eps_inf = h->par.eps_inf; a.eps_zero = h->par.eps_zero; a.max_iter = h->par.max_iter;
-    return a;
-}
-
 // the fields of thip_midbatch_info_t, which both families' records begin with
-template <class INFO>
-void mb_info(const MbHandle *h, size_t total, INFO &o)
-{
-    o.n_prob = (int32_t)h->n_prob; o.threads = h->threads; o.lds_bytes = (int32_t)h->lds; o.live = (int32_t)h->live.size();
-    o.arena_bytes = h->stride * h->n_prob * sizeof(float);
-    o.device_bytes = h->bytes;
-    o.device_bytes_all = total;
-    o.launches = h->launches; o.workgroups = h->workgroups;
-    o.load_bytes = ((h->m & 3) == 0 && h->n_unaligned == 0) ? 16 : 4;
-    o.a_bytes_per_iter = 2 * h->m * h->n * sizeof(float);
-}
+struct MbInfo {
+    template <class INFO>
+    void operator()(const OwnBatch *h, INFO &o) const
+    {
+        ObInfo()(h, o);
+        o.load_bytes = ((h->m & 3) == 0 && h->n_unaligned == 0) ? 16 : 4;
+        o.a_bytes_per_iter = 2 * h->m * h->n * sizeof(float);
+    }
+};
 
 }  // namespace

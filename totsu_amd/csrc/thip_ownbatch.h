@@ -1,14 +1,19 @@
 // thip_ownbatch.h -- what the "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip and
-// thip_sdpbatch.hip: A streamed from memory, thip_midstream.h): the status block and the slot of a problem, the device functions of
-// the iteration that do not touch A (block_sums, sb_comp_add, sb_soc), and the host machinery -- slots, arena, all 64-byte status
-// blocks in one copy, the live list, replace as the init kernel on one slot.  A family supplies its two launches, its shape rule
-// and its words for the refusals.
+// thip_sdpbatch.hip: A streamed from memory, thip_midstream.h).
+//   device: the launch arguments (ObArgs), the status block and the slot of a problem, the problem's scalars (ObScalars), the
+//           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
+//           functions of the iteration that do not touch A (block_sums, sb_comp_add, sb_soc).  The two recurrences -- three passes
+//           from LDS, two carried passes from memory -- stay with their families.
+//   host:   slots, arena, all 64-byte status blocks in one copy, the live list, replace as the init kernel on one slot, and the C
+//           API itself: a family is a table (ObFamily: its words, its shape rule, its thread choice, its LDS map's size, its
+//           kernels) and one OB_DEFINE_API line that emits its extern "C" entry points over the generic bodies below.
 // Included once by each of the translation units: everything here is internal to the one that includes it.
 #pragma once
 
 #include "thip_common.h"
 
 #include <algorithm>
+#include <mutex>
 #include <string.h>
 #include <vector>
 
@@ -31,6 +36,33 @@ struct SbStatus {                // 64 bytes, one per problem; the host copies a
 static_assert(sizeof(SbStatus) == 64, "SbStatus is copied as an array");
 
 struct SbSlot { const float *a, *b, *c, *rowabs; };      // where problem p's data lives (rowabs may be NULL: |b|)
+
+// what every kernel of every family is launched with: the family's shape words (ObShape: n, m; the small batch adds lda), then
+// ObCounts and ObRest.  One text, two layouts: each family keeps the argument block its iteration kernel had before the families
+// were merged, because the compiler allocates the kernel's scalar registers differently for another block.  smallbatch_k without
+// its lda word behind m (computed in the kernel, or placed elsewhere) reloads 8 more spilled SGPRs in its product loops;
+// midbatch_k and sdpbatch_k with an lda word they do not use reload 6 more.  Either costs 0.6 to 1.0 % (NOTEBOOK 19)
+struct ObShape { int n, m; };
+struct ObCounts {
+    int n_cones, comp, steps;
+    int first;                              // live == NULL: workgroup k serves problem first + k
+};
+struct ObRest {
+    const int *live;                        // else problem live[k]
+    const SbSlot *slots;
+    float *arena; size_t stride;            // problem p's state: arena + p * stride
+    SbStatus *st;
+    const unsigned char *cls;               // 0 zero cone, 1 nonnegative, 2 member of a block cone
+    const int *cones;                       // (beg, end, kind) per block cone: 0 second-order, 1 rotated, 1 + k a PSD cone of order k
+    float eps_acc, eps_inf, eps_zero; long long max_iter;
+};
+template <class SHAPE> struct ObArgsT : SHAPE, ObCounts, ObRest {};
+using ObArgs = ObArgsT<ObShape>;
+
+// the problem this workgroup serves.  The fields by value, here and in ObLimits: smallbatch_k never hands out the address of its
+// argument block, and the compiler then knows that the pointers it loads through it (the slot's A, b, c) are global -- with the
+// address taken they become flat loads
+__device__ __forceinline__ int ob_problem(const int *live, int first) { return live ? live[blockIdx.x] : first + (int)blockIdx.x; }
 
 // Q sums over the workgroup; every thread gets every result.  sh: 64 floats of LDS
 template <int Q>
@@ -122,6 +154,158 @@ __device__ __forceinline__ void sb_soc(float *x, float *rx, int beg, int end, in
     }
 }
 
+// the scalars of a problem, held in registers across a launch: from its status block and back
+struct ObScalars {
+    float tau, kappa, rtau, norm_b, norm_c, t_tau, s_kappa;
+    long long iter;
+    int state, kind;
+    float cri0, cri1, cri2;
+    __device__ __forceinline__ void load(const SbStatus *g)
+    {
+        tau = g->tau; kappa = g->kappa; rtau = g->r_tau;
+        norm_b = g->norm_b; norm_c = g->norm_c; t_tau = g->t_tau; s_kappa = g->s_kappa;
+        iter = g->iter;
+        state = THIP_ST_RUNNING; kind = g->kind;
+        cri0 = g->cri[0]; cri1 = g->cri[1]; cri2 = g->cri[2];
+    }
+    __device__ __forceinline__ void store(SbStatus *g) const      // (one thread)
+    {
+        g->tau = tau; g->kappa = kappa; g->r_tau = rtau; g->iter = iter;
+        g->kind = kind; g->cri[0] = cri0; g->cri[1] = cri1; g->cri[2] = cri2;
+        g->state = state;
+        g->stop = state != THIP_ST_RUNNING ? 1 : 0;
+    }
+};
+
+// calc_norms, calc_precond and init_vecs (solver.rs:460-524) of problem p by one workgroup: init_sums_k / init_scalars_k /
+// precond_k / group_min_k.  L: the family's LDS map (sh, b, c, g, h, Ty, Ts are used), S: the LDS.  abs_sums() leaves the row sums
+// of |A| in S[L.h ..] and the column sums in S[L.g ..], visible to every thread on return.  product_group takes the minimum over
+// every block cone, second-order or PSD.  What the family carries in the arena behind the preconditioner (the stride says how
+// much) starts at zero: A 0, A^T 0
+template <class ARGS, class MAP, class SUMS>
+__device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L, float *S, const SUMS &abs_sums)
+{
+    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const SbSlot sl = a.slots[p];
+    for (int i = tid; i < m; i += T) S[L.b + i] = sl.b[i];
+    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
+    __syncthreads();
+    float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };              // sum b^2, sum |b|, sum c^2, sum |c|
+    for (int i = tid; i < m; i += T) { const float t = S[L.b + i]; q[0] = fmaf(t, t, q[0]); q[1] += fabsf(t); }
+    for (int i = tid; i < n; i += T) { const float t = S[L.c + i]; q[2] = fmaf(t, t, q[2]); q[3] += fabsf(t); }
+    block_sums<4>(q, S + L.sh);
+    abs_sums(sl.a);
+    float *ar = a.arena + (size_t)p * a.stride;
+    float *gTx = ar + 4 * n + 6 * m, *gTy = gTx + n, *gTs = gTy + m, *gSv = gTs + m, *gcar = gSv + m;
+    for (int i = tid; i < n; i += T) {
+        const float t = S[L.g + i] + fabsf(S[L.c + i]);
+        gTx[i] = 1.0f / fmaxf(t, a.eps_zero);
+    }
+    for (int i = tid; i < m; i += T) {
+        const float t = S[L.h + i] + (sl.rowabs ? sl.rowabs[i] : fabsf(S[L.b + i]));
+        S[L.Ty + i] = 1.0f / fmaxf(t, a.eps_zero);
+        S[L.Ts + i] = 1.0f / fmaxf(1.0f, a.eps_zero);
+        gSv[i] = 1.0f / fmaxf(t + 1.0f, a.eps_zero);
+    }
+    __syncthreads();
+    {   // product_group (solver.rs:509-523): the minimum over each block cone, one wave per cone
+        const int lane = tid & 63, w = tid >> 6, nw = T >> 6;
+        for (int k = w; k < a.n_cones; k += nw) {
+            const int beg = a.cones[3 * k], end = a.cones[3 * k + 1];
+            for (int which = 0; which < 2; ++which) {
+                float *t = S + (which ? L.Ts : L.Ty);
+                float mn = __builtin_inff();
+                for (int i = beg + lane; i < end; i += 64) mn = fminf(mn, t[i]);
+                mn = wave_min(mn);
+                for (int i = beg + lane; i < end; i += 64) t[i] = mn;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += T) { gTy[i] = S[L.Ty + i]; gTs[i] = S[L.Ts + i]; }
+    for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
+    const int ncar = (int)a.stride - (5 * n + 9 * m);
+    for (int i = tid; i < ncar; i += T) gcar[i] = 0.0f;
+    if (tid == 0) {
+        SbStatus s;
+        s.stop = 0; s.state = THIP_ST_RUNNING; s.kind = 0; s.pad = 0; s.iter = 0;
+        s.cri[0] = s.cri[1] = s.cri[2] = 0.0f;
+        s.tau = 1.0f; s.kappa = 0.0f; s.r_tau = 0.0f;
+        const float nb = sqrtf(q[0]), nc = sqrtf(q[2]);      // fr_norm (solver.rs:85-107)
+        s.norm_b = sqrtf(nb * nb);
+        s.norm_c = sqrtf(nc * nc);
+        const float tau_tau = q[3] + q[1];
+        s.t_tau = 1.0f / fmaxf(tau_tau, a.eps_zero);
+        s.s_kappa = 1.0f / fmaxf(tau_tau, a.eps_zero);
+        a.st[p] = s;
+    }
+}
+
+// the sums of the criteria of the iterate (x_x, x_y, x_s) given h = A x_x, g = A^T x_y: q <- ||p||^2, b.x_y, ||d||^2, c.x_x
+// (post_k / ycrit_k).  conv (tau > eps_zero) and rt (1 / tau then, else 1) are formed here and again in ob_status_eval, from tau, not
+// handed in: the compiler then sees, as it did with one body per family, that rt is 1 / tau wherever conv holds
+__device__ __forceinline__ void ob_criteria_sums(float *q, int n, int m, float tau, float eps_zero, const float *b, const float *c,
+                                                 const float *xx, const float *xy, const float *xs, const float *h, const float *g,
+                                                 float *sh)
+{
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const bool conv = tau > eps_zero;
+    const float rt = conv ? 1.0f / tau : 1.0f;
+    q[0] = q[1] = q[2] = q[3] = 0.0f;
+    for (int i = tid; i < m; i += T) {
+        const float bi = b[i];
+        float pr;
+        if (conv) { pr = xs[i] * rt - bi; pr = fmaf(rt, h[i], pr); }
+        else pr = xs[i] + h[i];
+        q[0] = fmaf(pr, pr, q[0]);
+        q[1] = fmaf(bi, xy[i], q[1]);
+    }
+    for (int i = tid; i < n; i += T) {
+        const float ci = c[i];
+        const float d = conv ? fmaf(rt, g[i], ci) : g[i];
+        q[2] = fmaf(d, d, q[2]);
+        q[3] = fmaf(ci, xx[i], q[3]);
+    }
+    block_sums<4>(q, sh);
+}
+
+// where a problem stops (thip_param's fields; passed by value, see ob_problem)
+struct ObLimits { float eps_acc, eps_inf, eps_zero; long long max_iter; };
+
+// status_eval (thip_solver_kernels.inc) on those sums: kind, the criteria and the state of s, whose tau is the new iterate's.
+// Uniform: every thread holds the same sums.  The state is a local until the end, so that the chain of ifs stays a chain of branches
+__device__ __forceinline__ void ob_status_eval(ObScalars &s, const ObLimits a, float pp, float by, float dd, float cx)
+{
+    const bool conv = s.tau > a.eps_zero;
+    const float rt = conv ? 1.0f / s.tau : 1.0f;
+    int state = s.state;
+    const bool excess_iter = (a.max_iter >= 0) ? (s.iter + 1 >= a.max_iter) : false;
+    const float norm_p = sqrtf(pp), norm_d = sqrtf(dd);
+    if (conv) {
+        const float g_x = rt * cx;
+        const float g_y = rt * by;
+        const float gg = g_x + g_y;
+        s.kind = 0;
+        s.cri0 = norm_p / (1.0f + s.norm_b);
+        s.cri1 = norm_d / (1.0f + s.norm_c);
+        s.cri2 = fabsf(gg) / (1.0f + fabsf(g_x) + fabsf(g_y));
+        const bool term_conv = (s.cri0 <= a.eps_acc) && (s.cri1 <= a.eps_acc) && (s.cri2 <= a.eps_acc);
+        if (term_conv) state = THIP_ST_OK;
+        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
+    } else {
+        const float m_cx = -cx;
+        const float m_by = -by;
+        s.kind = 1;
+        s.cri0 = (m_cx > a.eps_zero) ? norm_p * s.norm_c / m_cx : __builtin_inff();
+        s.cri1 = (m_by > a.eps_zero) ? norm_d * s.norm_b / m_by : __builtin_inff();
+        s.cri2 = 0.0f;
+        if (s.cri0 <= a.eps_inf) state = THIP_ST_UNBOUNDED;
+        else if (s.cri1 <= a.eps_inf) state = THIP_ST_INFEASIBLE;
+        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
+    }
+    s.state = state;
+}
+
 __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,
                                  size_t m, size_t n)
 {
@@ -135,15 +319,36 @@ __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, cons
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 // a family's words for its refusals
-struct ObText { const char *uninit, *null_h, *count, *no_psd; };
+struct ObText { const char *uninit, *null_h, *count, *no_psd, *force_sizes, *force_late; };
 
-// what a handle of either family is.  The arena holds, per problem, `stride` floats: xx u kx ku | xy xs v ky ks kv | Tx Ty Ts Sv and
+// what the PSD cones of a layout add (all zero in a family that takes none)
+struct ObPsd { int max_k = 0, n_psd = 0; size_t tail_bytes = 0; };
+
+struct OwnBatch;
+
+// a family: everything the generic API bodies below need to know about it
+struct ObFamily {
+    ObText text;
+    int forced[3];                          // the workgroup sizes force_threads takes (0: no further one)
+    bool streams;                           // A is read in place: the handle records which slots hold an unaligned one
+    // the shape rule (no device needed), the single source of the family's limit.  On success *cones holds (beg, end, kind) per
+    // block cone, *cls the class bytes and *psd what the PSD cones add (each may be null)
+    int (*check)(size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, std::vector<int> *cones,
+                 std::vector<unsigned char> *cls, ObPsd *psd);
+    int (*threads_for)(size_t n, size_t m);
+    size_t (*lds_for)(size_t n, size_t m, int threads, const ObPsd &psd);
+    size_t (*stride_for)(size_t n, size_t m);
+    int (*launch)(const OwnBatch *h, bool run, const ObArgs &a, unsigned count);      // the init kernel or the iteration
+    const void *kernels[3];                 // every kernel that asks for more than 64 KiB of LDS
+    size_t total = 0;                       // device memory held by every handle of the family
+    std::once_flag attr_once;
+    hipError_t attr_err = hipSuccess;
+};
+
+// what a handle of any family is.  The arena holds, per problem, `stride` floats: xx u kx ku | xy xs v ky ks kv | Tx Ty Ts Sv and
 // then whatever else the family carries
 struct OwnBatch {
-    const ObText *text = nullptr;
-    size_t *total = nullptr;                // device memory held by every handle of the family
-    int (*launch_init)(OwnBatch *, int first, int count) = nullptr;
-    int (*launch_run)(OwnBatch *, int count, int steps, const int *live) = nullptr;
+    ObFamily *fam = nullptr;
     size_t n = 0, m = 0, n_prob = 0;
     thip_param par{};
     std::vector<int> cones;
@@ -158,6 +363,9 @@ struct OwnBatch {
     std::vector<int> live;
     bool inited = false;
     int64_t launches = 0, workgroups = 0;
+    ObPsd psd;
+    std::vector<unsigned char> unaligned;   // (a family that streams A) per slot: the problem's A is not 16-byte aligned
+    size_t n_unaligned = 0;                 // how many: decides the load path info() reports
 };
 
 // the cone segments (no device needed).  On success *cones holds (beg, end, kind) per block cone -- kind 0: second-order, 1: rotated,
@@ -198,7 +406,62 @@ int ob_segments(const ObText &tx, size_t m, size_t n_seg, const int32_t *seg_typ
 int ob_alloc(OwnBatch *h, void **p, size_t bytes)
 {
     THIP_TRY(hipMalloc(p, bytes));
-    h->bytes += bytes; *h->total += bytes;
+    h->bytes += bytes; h->fam->total += bytes;
+    return 0;
+}
+
+void ob_plan(OwnBatch *h)
+{
+    h->threads = h->forced ? h->forced : h->fam->threads_for(h->n, h->m);
+    h->lds = h->fam->lds_for(h->n, h->m, h->threads, h->psd);
+}
+
+ObArgs ob_args(const OwnBatch *h)
+{
+    ObArgs a{};
+    a.n = (int)h->n; a.m = (int)h->m; a.n_cones = (int)(h->cones.size() / 3);
+    a.comp = h->par.state_arith == THIP_STATE_COMPENSATED; a.steps = 0; a.first = 0; a.live = nullptr;
+    a.slots = h->slots; a.arena = h->arena; a.stride = h->stride; a.st = h->dst; a.cls = h->cls_dev; a.cones = h->cones_dev;
+    a.eps_acc = h->par.eps_acc; a.eps_inf = h->par.eps_inf; a.eps_zero = h->par.eps_zero; a.max_iter = h->par.max_iter;
+    return a;
+}
+
+// the init kernel on the problems first .. first + count - 1
+int ob_launch_init(OwnBatch *h, int first, int count)
+{
+    ObArgs a = ob_args(h);
+    a.first = first;
+    return h->fam->launch(h, false, a, (unsigned)count);
+}
+
+// `steps` iterations of `count` problems: those of the list, or (live == NULL) the first `count`
+int ob_launch_run(OwnBatch *h, int count, int steps, const int *live)
+{
+    ObArgs a = ob_args(h);
+    a.steps = steps;
+    a.live = live;
+    return h->fam->launch(h, true, a, (unsigned)count);
+}
+
+// what a family's launch hook does with the kernel it chose
+template <class ARGS>
+int ob_launch(const OwnBatch *h, void (*kernel)(ARGS), const ARGS &a, unsigned count)
+{
+    hipLaunchKernelGGL(kernel, dim3(count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// every kernel of the family may ask for the whole LDS of a CU (once per process)
+int ob_attr(ObFamily &f)
+{
+    std::call_once(f.attr_once, [&]() {
+        for (const void *k : f.kernels)
+            if (k && f.attr_err == hipSuccess)
+                f.attr_err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OB_LDS_MAX);
+    });
+    const hipError_t err = f.attr_err;
+    THIP_TRY(err);
     return 0;
 }
 
@@ -223,10 +486,10 @@ int ob_poll(OwnBatch *h, thip_status *host_status)
     return 0;
 }
 
-int ob_run(OwnBatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status, bool until_any)
+int ob_run(const ObFamily &f, OwnBatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status, bool until_any)
 {
     THIP_NEED_INIT();
-    if (!h || !h->inited) return fail(THIP_E_INVALID, h ? h->text->uninit : "null batch", __FILE__, __LINE__);
+    if (!h || !h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
     if (poll_every <= 0) poll_every = 16;
     hipStream_t st = ctx().stream;
     THIP_RC(ob_poll(h, host_status));
@@ -238,7 +501,7 @@ int ob_run(OwnBatch *h, int64_t max_steps, int64_t poll_every, thip_status *host
         if (batch > 1 << 20) batch = 1 << 20;
         const bool all = h->live.size() == h->n_prob;          // (then workgroup k serves problem k: no list)
         if (!all) THIP_TRY(hipMemcpyAsync(h->live_dev, h->live.data(), h->live.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        THIP_RC(h->launch_run(h, (int)h->live.size(), (int)batch, all ? nullptr : h->live_dev));
+        THIP_RC(ob_launch_run(h, (int)h->live.size(), (int)batch, all ? nullptr : h->live_dev));
         h->launches += 1;
         h->workgroups += (int64_t)h->live.size();
         done += batch;
@@ -247,9 +510,9 @@ int ob_run(OwnBatch *h, int64_t max_steps, int64_t poll_every, thip_status *host
     return 0;
 }
 
-int ob_member(OwnBatch *h, int i)
+int ob_member(const ObFamily &f, OwnBatch *h, int i)
 {
-    if (!h || !h->inited) return fail(THIP_E_INVALID, h ? h->text->uninit : "null batch", __FILE__, __LINE__);
+    if (!h || !h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
     if (i < 0 || (size_t)i >= h->n_prob) return fail(THIP_E_INVALID, "no such problem", __FILE__, __LINE__);
     return 0;
 }
@@ -272,25 +535,16 @@ void ob_finalize(const SbStatus &s, float *x, size_t n)
     for (size_t i = 0; i < n; ++i) x[i] = rt * x[i];
 }
 
-int ob_destroy(OwnBatch *h)
+// (H: the family's handle type, which is what is deleted)
+template <class H>
+int ob_destroy(H *h)
 {
+    if (!h) return 0;
     if (ctx().inited) hipStreamSynchronize(ctx().stream);
     hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
     if (h->hst) hipHostFree(h->hst);
-    *h->total -= h->bytes;
-    return 0;
-}
-
-// the refusals of create that do not depend on the shape
-int ob_create_args(const ObText &tx, size_t n_prob, const float *a, const float *b, const float *c, const float *rowabs,
-                   const thip_param *par)
-{
-    if (!par || !a || !b || !c) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    if (n_prob < 1 || n_prob > OB_MAX_PROB) return fail(THIP_E_INVALID, tx.count, __FILE__, __LINE__);
-    if (par->state_arith != THIP_STATE_COMPENSATED && par->state_arith != THIP_STATE_PLAIN)
-        return fail(THIP_E_INVALID, "bad thip_param.state_arith", __FILE__, __LINE__);
-    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)rowabs) & 3u)
-        return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
+    h->fam->total -= h->bytes;
+    delete h;
     return 0;
 }
 
@@ -324,30 +578,30 @@ int ob_set_param(OwnBatch *h, const thip_param *par)
     return 0;
 }
 
-int ob_init(OwnBatch *h, const ObText &tx)
+int ob_init(const ObFamily &f, OwnBatch *h)
 {
     THIP_NEED_INIT();
-    if (!h) return fail(THIP_E_INVALID, tx.null_h, __FILE__, __LINE__);
-    THIP_RC(h->launch_init(h, 0, (int)h->n_prob));
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    THIP_RC(ob_launch_init(h, 0, (int)h->n_prob));
     h->launches = 0; h->workgroups = 0;
     h->inited = true;
     return ob_poll(h, nullptr);
 }
 
-int ob_status(OwnBatch *h, int i, thip_status *host_status)
+int ob_status(const ObFamily &f, OwnBatch *h, int i, thip_status *host_status)
 {
     THIP_NEED_INIT();
-    THIP_RC(ob_member(h, i));
+    THIP_RC(ob_member(f, h, i));
     if (!host_status) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
     THIP_RC(ob_status_one(h, i));
     ob_status_out(h->hst[i], host_status);
     return 0;
 }
 
-int ob_solution(OwnBatch *h, int i, float *host_x, float *host_y)
+int ob_solution(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
 {
     THIP_NEED_INIT();
-    THIP_RC(ob_member(h, i));
+    THIP_RC(ob_member(f, h, i));
     THIP_RC(ob_status_one(h, i));
     const float *ar = h->arena + (size_t)i * h->stride;
     if (host_x) THIP_RC(thip_d2h(host_x, ar, h->n));
@@ -357,10 +611,10 @@ int ob_solution(OwnBatch *h, int i, float *host_x, float *host_y)
     return 0;
 }
 
-int ob_iterate(OwnBatch *h, int i, float *host_x, float *host_y)
+int ob_iterate(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
 {
     THIP_NEED_INIT();
-    THIP_RC(ob_member(h, i));
+    THIP_RC(ob_member(f, h, i));
     THIP_RC(ob_status_one(h, i));
     const size_t n = h->n, m = h->m;
     const float *ar = h->arena + (size_t)i * h->stride;      // xx u kx ku | xy xs v ..
@@ -378,10 +632,10 @@ int ob_iterate(OwnBatch *h, int i, float *host_x, float *host_y)
     return 0;
 }
 
-int ob_precond(OwnBatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
+int ob_precond(const ObFamily &f, OwnBatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
 {
     THIP_NEED_INIT();
-    THIP_RC(ob_member(h, i));
+    THIP_RC(ob_member(f, h, i));
     THIP_RC(ob_status_one(h, i));
     const size_t n = h->n, m = h->m;
     const float *k = h->arena + (size_t)i * h->stride + 4 * n + 6 * m;      // Tx Ty Ts Sv
@@ -397,20 +651,147 @@ int ob_precond(OwnBatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
     return 0;
 }
 
-int ob_replace(OwnBatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
+int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
 {
     THIP_NEED_INIT();
-    THIP_RC(ob_member(h, i));
+    THIP_RC(ob_member(f, h, i));
     if (!dev_mat_a || !dev_vec_b || !dev_vec_c) return fail(THIP_E_INVALID, "null A, b or c", __FILE__, __LINE__);
     if (((uintptr_t)dev_mat_a | (uintptr_t)dev_vec_b | (uintptr_t)dev_vec_c | (uintptr_t)dev_vec_b_rowabs) & 3u)
         return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
     const SbSlot s{ dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs };
     THIP_TRY(hipMemcpyAsync(h->slots + i, &s, sizeof(SbSlot), hipMemcpyHostToDevice, ctx().stream));
     THIP_TRY(hipStreamSynchronize(ctx().stream));           // (s is a local)
-    THIP_RC(h->launch_init(h, i, 1));
+    THIP_RC(ob_launch_init(h, i, 1));
     const auto at = std::lower_bound(h->live.begin(), h->live.end(), i);
     if (at == h->live.end() || *at != i) h->live.insert(at, i);
-    return ob_status_one(h, i);
+    THIP_RC(ob_status_one(h, i));
+    if (f.streams) {
+        const unsigned char un = ((uintptr_t)dev_mat_a & 15u) != 0;
+        h->n_unaligned += un;
+        h->n_unaligned -= h->unaligned[(size_t)i];
+        h->unaligned[(size_t)i] = un;
+    }
+    return 0;
+}
+
+// the shape rules alone: the family's check (which fills *cones, *cls and *psd when they are given), its thread choice and the LDS of
+// one workgroup
+int ob_fits(const ObFamily &f, size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
+            int *host_threads, std::vector<int> *cones = nullptr, std::vector<unsigned char> *cls = nullptr, ObPsd *psd_out = nullptr)
+{
+    ObPsd psd;
+    THIP_RC(f.check(n, m, n_seg, seg_type, seg_len, cones, cls, &psd));
+    const int t = f.threads_for(n, m);
+    if (host_threads) *host_threads = t;
+    if (host_lds_bytes) *host_lds_bytes = f.lds_for(n, m, t, psd);
+    // (the bound is on the widest workgroup a test may force: no accepted shape can fail to launch)
+    if (f.lds_for(n, m, *std::max_element(f.forced, f.forced + 3), psd) > OB_LDS_MAX)
+        return fail(THIP_E_INVALID, "the problem does not fit the LDS of one CU", __FILE__, __LINE__);
+    if (psd_out) *psd_out = psd;
+    return 0;
+}
+
+// H: the family's handle type.  Every refusal comes before the first allocation; a later failure destroys what was built
+template <class H>
+int ob_create(ObFamily &f, size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b, const float *dev_vecs_c,
+              const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+              const thip_param *par, H **out)
+{
+    if (!out) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    *out = nullptr;
+    THIP_NEED_INIT();
+    const ObText &tx = f.text;
+    if (!par || !dev_mats_a || !dev_vecs_b || !dev_vecs_c) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    if (n_prob < 1 || n_prob > OB_MAX_PROB) return fail(THIP_E_INVALID, tx.count, __FILE__, __LINE__);
+    if (par->state_arith != THIP_STATE_COMPENSATED && par->state_arith != THIP_STATE_PLAIN)
+        return fail(THIP_E_INVALID, "bad thip_param.state_arith", __FILE__, __LINE__);
+    if (((uintptr_t)dev_mats_a | (uintptr_t)dev_vecs_b | (uintptr_t)dev_vecs_c | (uintptr_t)dev_vecs_b_rowabs) & 3u)
+        return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
+    H *h = new H();
+    h->fam = &f;
+    int rc = ob_fits(f, n, m, n_seg, host_seg_type, host_seg_len, nullptr, nullptr, &h->cones, &h->cls, &h->psd);
+    if (rc != 0) { delete h; return rc; }
+    h->n = n; h->m = m; h->n_prob = n_prob;
+    h->par = *par;
+    h->stride = f.stride_for(n, m);
+    ob_plan(h);
+    if (f.streams) {
+        h->unaligned.assign(n_prob, 0);
+        for (size_t p = 0; p < n_prob; ++p) {
+            h->unaligned[p] = (((uintptr_t)(dev_mats_a + p * m * n)) & 15u) != 0;
+            h->n_unaligned += h->unaligned[p];
+        }
+    }
+    rc = ob_attr(f);
+    if (rc == 0) rc = ob_build(h, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs);
+    if (rc != 0) { ob_destroy(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+// the fields every family's info record begins with
+struct ObInfo {
+    template <class INFO>
+    void operator()(const OwnBatch *h, INFO &o) const
+    {
+        o.n_prob = (int32_t)h->n_prob; o.threads = h->threads; o.lds_bytes = (int32_t)h->lds; o.live = (int32_t)h->live.size();
+        o.arena_bytes = h->stride * h->n_prob * sizeof(float);
+        o.device_bytes = h->bytes;
+        o.device_bytes_all = h->fam->total;
+        o.launches = h->launches; o.workgroups = h->workgroups;
+    }
+};
+
+// FILL: ObInfo, or the family's functor that adds to it
+template <class INFO, class FILL>
+int ob_info_out(const OwnBatch *h, INFO *host_info, FILL fill)
+{
+    if (!h || !host_info) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    memset(host_info, 0, sizeof(*host_info));
+    fill(h, *host_info);
+    return 0;
+}
+
+int ob_force_threads(const ObFamily &f, OwnBatch *h, int threads)
+{
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (threads != 0 && std::find(f.forced, f.forced + 3, threads) == f.forced + 3)
+        return fail(THIP_E_INVALID, f.text.force_sizes, __FILE__, __LINE__);
+    if (h->inited) return fail(THIP_E_INVALID, f.text.force_late, __FILE__, __LINE__);
+    h->forced = threads;
+    ob_plan(h);
+    return 0;
 }
 
 }  // namespace
+
+// the C API of a family (the declarations of include/totsu_f32hip.h and include/totsu_f32hip_test.h): NAME as in thip_NAME_create,
+// FAM its ObFamily, FILL what fills its info record.  struct thip_NAME, the handle, is the family's to define (an OwnBatch)
+#define OB_DEFINE_API(NAME, FAM, FILL)                                                                                              \
+    extern "C" {                                                                                                                    \
+    int thip_##NAME##_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,             \
+                           size_t *host_lds_bytes, int *host_threads)                                                               \
+    { return ob_fits(FAM, n, m, n_seg, host_seg_type, host_seg_len, host_lds_bytes, host_threads); }                                \
+    int thip_##NAME##_destroy(thip_##NAME *h) { return ob_destroy(h); }                                                             \
+    int thip_##NAME##_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,                   \
+                             const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,   \
+                             const int64_t *host_seg_len, const thip_param *par, thip_##NAME **out)                                 \
+    { return ob_create(FAM, n, m, n_prob, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs, n_seg, host_seg_type,              \
+                       host_seg_len, par, out); }                                                                                   \
+    int thip_##NAME##_set_param(thip_##NAME *h, const thip_param *par) { return ob_set_param(h, par); }                             \
+    int thip_##NAME##_init(thip_##NAME *h) { return ob_init(FAM, h); }                                                              \
+    int thip_##NAME##_run(thip_##NAME *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)                          \
+    { return ob_run(FAM, h, max_steps, poll_every, host_status, false); }                                                           \
+    int thip_##NAME##_run_until_any(thip_##NAME *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)                \
+    { return ob_run(FAM, h, max_steps, poll_every, host_status, true); }                                                            \
+    int thip_##NAME##_status(thip_##NAME *h, int i, thip_status *host_status) { return ob_status(FAM, h, i, host_status); }         \
+    int thip_##NAME##_solution(thip_##NAME *h, int i, float *host_x, float *host_y) { return ob_solution(FAM, h, i, host_x, host_y); } \
+    int thip_##NAME##_iterate(thip_##NAME *h, int i, float *host_x, float *host_y) { return ob_iterate(FAM, h, i, host_x, host_y); } \
+    int thip_##NAME##_precond(thip_##NAME *h, int i, float *host_dp_tau, float *host_dp_sigma)                                      \
+    { return ob_precond(FAM, h, i, host_dp_tau, host_dp_sigma); }                                                                   \
+    int thip_##NAME##_replace(thip_##NAME *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,        \
+                              const float *dev_vec_b_rowabs)                                                                        \
+    { return ob_replace(FAM, h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs); }                                            \
+    int thip_##NAME##_info(const thip_##NAME *h, thip_##NAME##_info_t *host_info) { return ob_info_out(h, host_info, FILL()); }       \
+    int thip_test_##NAME##_force_threads(thip_##NAME *h, int threads) { return ob_force_threads(FAM, h, threads); }                 \
+    }

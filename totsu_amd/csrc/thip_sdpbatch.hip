@@ -23,9 +23,10 @@
 //   largest order  > 32: one 64 x 65 operand (4160 floats) lies in it, three more follow the class bytes: 3 * 64 * 65 * 4 = 49 920 bytes.
 // sp_check is the single source of the rule.  No atomics: a problem's iterates are a function of (its data, the workgroup size, the
 // constants) alone.
+//
+// This file: the projection, the kernels, the shape rule and the family's table; the C API is thip_ownbatch.h's, instantiated by
+// one line; thip_test_sdpbatch_project follows it.
 #include "thip_midstream.h"
-
-#include <mutex>
 
 using namespace thip;
 
@@ -161,7 +162,7 @@ __device__ __forceinline__ void sp_project_any(float *x, float *rx, int k, float
 struct SpCones {
     static constexpr bool psd = true;
     int tail;                               // where the operands behind the class bytes begin, in floats
-    __device__ __forceinline__ void operator()(float *S, const MbMap &L, const MbArgs &a) const
+    __device__ __forceinline__ void operator()(float *S, const MbMap &L, const ObArgs &a) const
     {
         for (int c = 0; c < a.n_cones; ++c) {
             const int kind = a.cones[3 * c + 2];
@@ -175,9 +176,9 @@ struct SpCones {
     }
 };
 
-struct SpArgs { MbArgs mb; int tail; };
+struct SpArgs { ObArgs mb; int tail; };
 
-__global__ __launch_bounds__(1024) void sdpbatch_init_k(const MbArgs a) { mb_init_body(a); }
+__global__ __launch_bounds__(1024) void sdpbatch_init_k(const ObArgs a) { mb_init_body(a); }
 
 __global__ __launch_bounds__(1024) void sdpbatch_k(const SpArgs a) { mb_iterate_body(a.mb, SpCones{ a.tail }); }
 
@@ -190,213 +191,66 @@ __global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, 
                    reinterpret_cast<double *>(S));
 }
 
-size_t g_sp_bytes = 0;                      // device memory held by every thip_sdpbatch of the process
+const ObText SP_TEXT = { "SDP batch not initialised", "null SDP batch", "an SDP batch holds 1 .. 1048576 problems", nullptr,
+                         "the workgroup size is 256 or 1024 (0: by shape)",
+                         "thip_test_sdpbatch_force_threads comes before thip_sdpbatch_init" };
 
-const ObText SP_TEXT = { "SDP batch not initialised", "null SDP batch", "an SDP batch holds 1 .. 1048576 problems", nullptr };
-
-struct SpShape { int max_k = 0, n_psd = 0; size_t lds = 0, tail_bytes = 0; };
+// the mid batch's map, and the operands behind the class bytes (the same for every workgroup size)
+size_t sp_lds_for(size_t n, size_t m, int, const ObPsd &psd) { return MbMap((int)n, (int)m).bytes((int)m) + psd.tail_bytes; }
 
 // the shape rules (no device needed): the single source of the limit
 int sp_check(size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, std::vector<int> *cones,
-             std::vector<unsigned char> *cls, SpShape *shape)
+             std::vector<unsigned char> *cls, ObPsd *psd)
 {
     if (m < 1 || m > MB_MAX_DIM || n < 1 || n > MB_MAX_DIM)
         return fail(THIP_E_INVALID, "an SDP batch takes 1 <= m <= 4096 and 1 <= n <= 4096", __FILE__, __LINE__);
     std::vector<int> local;
     if (!cones) cones = &local;
     THIP_RC(ob_segments(SP_TEXT, m, n_seg, seg_type, seg_len, cones, cls, SP_MAX_ORDER));
-    SpShape s;
+    ObPsd s;
     for (size_t i = 0; i + 2 < cones->size(); i += 3)
         if ((*cones)[i + 2] >= 2) { s.n_psd += 1; s.max_k = std::max(s.max_k, (*cones)[i + 2] - 1); }
     s.tail_bytes = sp_tail_floats(s.max_k) * sizeof(float);
-    s.lds = MbMap((int)n, (int)m).bytes((int)m) + s.tail_bytes;
-    if (s.lds > MB_LDS_MAX)
+    if (sp_lds_for(n, m, 0, s) > OB_LDS_MAX)
         return fail(THIP_E_INVALID, "the vectors of the problem (8 n + 13 m floats and 24 832 bytes) and the three operands a PSD order "
                                     "above 32 adds (49 920 bytes) do not fit the LDS of one CU", __FILE__, __LINE__);
-    if (shape) *shape = s;
+    if (psd) *psd = s;
     return 0;
 }
 
-}  // namespace
+int sp_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
+{
+    if (!run) return ob_launch(h, sdpbatch_init_k, a, count);
+    return ob_launch(h, sdpbatch_k, SpArgs{ a, (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float)) }, count);
+}
 
-struct thip_sdpbatch : MbHandle {
-    SpShape shape;
+ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch,
+                       { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k } };
+
+// thip_midbatch_info_t's fields, and the PSD cones'
+struct SpInfo {
+    void operator()(const OwnBatch *h, thip_sdpbatch_info_t &o) const
+    {
+        MbInfo()(h, o);
+        o.max_psd_order = h->psd.max_k; o.n_psd = h->psd.n_psd;
+        o.psd_lds_bytes = h->psd.tail_bytes;
+    }
 };
 
-namespace {
-
-int sp_attr()
-{
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [&]() {
-        err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MB_LDS_MAX);
-        if (err == hipSuccess)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_init_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)MB_LDS_MAX);
-        if (err == hipSuccess)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdpbatch_project_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)MB_LDS_MAX);
-    });
-    THIP_TRY(err);
-    return 0;
-}
-
-void sp_plan(thip_sdpbatch *h)
-{
-    h->threads = h->forced ? h->forced : mb_threads_for(h->n, h->m);
-    h->lds = h->shape.lds;
-}
-
-int sp_launch_init(OwnBatch *h, int first, int count)
-{
-    MbArgs a = mb_args(h);
-    a.first = first;
-    hipLaunchKernelGGL(sdpbatch_init_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
-    THIP_LAUNCH_CHECK();
-    return 0;
-}
-
-int sp_launch_run(OwnBatch *h, int count, int steps, const int *live)
-{
-    SpArgs a{};
-    a.mb = mb_args(h);
-    a.mb.steps = steps;
-    a.mb.live = live;
-    a.tail = (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float));
-    hipLaunchKernelGGL(sdpbatch_k, dim3((unsigned)count), dim3((unsigned)h->threads), h->lds, ctx().stream, a);
-    THIP_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace
 
-#define SP_NEED(h)                                                                  \
-    do {                                                                            \
-        if (!(h)) { THIP_NEED_INIT(); return fail(THIP_E_INVALID, SP_TEXT.uninit, __FILE__, __LINE__); } \
-    } while (0)
+struct thip_sdpbatch : OwnBatch {};
+
+OB_DEFINE_API(sdpbatch, SP_FAMILY, SpInfo)
 
 extern "C" {
-
-int thip_sdpbatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
-                       size_t *host_lds_bytes, int *host_threads)
-{
-    SpShape s;
-    THIP_RC(sp_check(n, m, n_seg, host_seg_type, host_seg_len, nullptr, nullptr, &s));
-    if (host_threads) *host_threads = mb_threads_for(n, m);
-    if (host_lds_bytes) *host_lds_bytes = s.lds;                                    // (the same for every workgroup size)
-    return 0;
-}
-
-int thip_sdpbatch_destroy(thip_sdpbatch *h)
-{
-    if (!h) return 0;
-    ob_destroy(h);
-    delete h;
-    return 0;
-}
-
-int thip_sdpbatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b, const float *dev_vecs_c,
-                         const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
-                         const thip_param *par, thip_sdpbatch **out)
-{
-    if (!out) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    *out = nullptr;
-    THIP_NEED_INIT();
-    THIP_RC(ob_create_args(SP_TEXT, n_prob, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs, par));
-    thip_sdpbatch *h = new thip_sdpbatch();
-    h->text = &SP_TEXT; h->total = &g_sp_bytes; h->launch_init = sp_launch_init; h->launch_run = sp_launch_run;
-    // every refusal comes before the first allocation
-    int rc = sp_check(n, m, n_seg, host_seg_type, host_seg_len, &h->cones, &h->cls, &h->shape);
-    if (rc != 0) { delete h; return rc; }
-    h->n = n; h->m = m; h->n_prob = n_prob;
-    h->par = *par;
-    h->stride = mb_stride(n, m);
-    sp_plan(h);
-    mb_note_alignment(h, dev_mats_a);
-    rc = sp_attr();
-    if (rc == 0) rc = ob_build(h, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs);
-    if (rc != 0) { thip_sdpbatch_destroy(h); return rc; }
-    *out = h;
-    return 0;
-}
-
-int thip_sdpbatch_set_param(thip_sdpbatch *h, const thip_param *par) { return ob_set_param(h, par); }
-
-int thip_sdpbatch_init(thip_sdpbatch *h) { return ob_init(h, SP_TEXT); }
-
-int thip_sdpbatch_run(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
-{
-    SP_NEED(h);
-    return ob_run(h, max_steps, poll_every, host_status, false);
-}
-
-int thip_sdpbatch_run_until_any(thip_sdpbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
-{
-    SP_NEED(h);
-    return ob_run(h, max_steps, poll_every, host_status, true);
-}
-
-int thip_sdpbatch_status(thip_sdpbatch *h, int i, thip_status *host_status)
-{
-    SP_NEED(h);
-    return ob_status(h, i, host_status);
-}
-
-int thip_sdpbatch_solution(thip_sdpbatch *h, int i, float *host_x, float *host_y)
-{
-    SP_NEED(h);
-    return ob_solution(h, i, host_x, host_y);
-}
-
-int thip_sdpbatch_iterate(thip_sdpbatch *h, int i, float *host_x, float *host_y)
-{
-    SP_NEED(h);
-    return ob_iterate(h, i, host_x, host_y);
-}
-
-int thip_sdpbatch_precond(thip_sdpbatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
-{
-    SP_NEED(h);
-    return ob_precond(h, i, host_dp_tau, host_dp_sigma);
-}
-
-int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
-                          const float *dev_vec_b_rowabs)
-{
-    SP_NEED(h);
-    THIP_RC(ob_replace(h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs));
-    mb_note_replaced(h, i, dev_mat_a);
-    return 0;
-}
-
-int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info)
-{
-    if (!h || !host_info) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
-    memset(host_info, 0, sizeof(*host_info));
-    mb_info(h, g_sp_bytes, *host_info);
-    host_info->max_psd_order = h->shape.max_k; host_info->n_psd = h->shape.n_psd;
-    host_info->psd_lds_bytes = h->shape.tail_bytes;
-    return 0;
-}
-
-int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads)
-{
-    if (!h) return fail(THIP_E_INVALID, "null SDP batch", __FILE__, __LINE__);
-    if (threads != 0 && threads != 256 && threads != 1024)
-        return fail(THIP_E_INVALID, "the workgroup size is 256 or 1024 (0: by shape)", __FILE__, __LINE__);
-    if (h->inited) return fail(THIP_E_INVALID, "thip_test_sdpbatch_force_threads comes before thip_sdpbatch_init", __FILE__, __LINE__);
-    h->forced = threads;
-    sp_plan(h);
-    return 0;
-}
 
 int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_rx_or_null)
 {
     THIP_NEED_INIT();
     if (k < 1 || k > SP_MAX_ORDER) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project: 1 <= k <= 64", __FILE__, __LINE__);
     if (count < 1 || !dev_packed) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project: no matrix", __FILE__, __LINE__);
-    THIP_RC(sp_attr());
+    THIP_RC(ob_attr(SP_FAMILY));
     const size_t lds = (64 + (k <= 32 ? 4 * (size_t)SP_OP32 : 4 * (size_t)SP_OP64)) * sizeof(float);
     hipLaunchKernelGGL(sdpbatch_project_k, dim3((unsigned)count), dim3(256), lds, ctx().stream, k, dev_packed, dev_rx_or_null);
     THIP_LAUNCH_CHECK();

@@ -3,7 +3,8 @@ one cone layout; their own A_p, b_p, c_p): one relaxation per graph, per scenari
 include/totsu_f32hip.h).  The kernel is the mid batch's iteration -- one workgroup per problem, every vector in LDS, A streamed twice
 per iteration -- with one more cone class: every PSD cone of order k <= 64 is projected by the workgroup itself between the two
 passes, on x_y and then on x_s, with f32 MFMAs on operands in LDS, so an iteration has no launch boundary inside.  The host
-machinery, the methods and the ValueErrors are `MidBatchSolver`'s; a layout without PSD segments gives its iterates bit for bit.
+machinery, the methods and the ValueErrors are `OwnBatchSolver`'s (totsu_amd/ownbatch.py); a layout without PSD segments gives the
+mid batch's iterates bit for bit.
 
 Taken: 1 <= m, n <= 4096; the zero, nonnegative, second-order, rotated second-order and PSD cones, every PSD segment of
 k (k + 1) / 2 rows with 1 <= k <= 64 (what ProbSDP.dense() holds); an LDS map of at most 163 840 bytes --
@@ -16,14 +17,13 @@ cover m, no problem at all, arrays of the wrong length.
 `conic_batch(denses)` picks between the three own-A batches by shape and layout."""
 from . import _lib
 from . import midbatch as _mb
-from . import smallbatch as _sb
 from .midbatch import MidBatchSolver
-from .smallbatch import SmallBatchSolver
+from .ownbatch import OwnBatchSolver, _fits, first_that_takes
 
 
 def fits(n, m, seg_type, seg_len):
     """the shape rules alone (thip_sdpbatch_fits; needs no GPU): (lds_bytes, threads) of one workgroup, or ValueError"""
-    return _sb._fits("thip_sdpbatch_", n, m, seg_type, seg_len)
+    return _fits("thip_sdpbatch_", n, m, seg_type, seg_len)
 
 
 class SdpBatchSolver(MidBatchSolver):
@@ -42,15 +42,9 @@ def conic_batch(denses, param=None, **kw):
     in what was measured.  The SDP batch wins at every one of the five layouts run (45 x 6 order 9 .. 1176 x 48 order 48) and every P,
     down to P = 16 -- by 9.2x (560 x 528) to 14x there, by 135x to 222x at P = 256 --, so the choice is by rule alone.  Below P = 16
     nothing was measured; a single problem is FusedSolver's case."""
-    denses = SmallBatchSolver.check_same_layout(denses)
+    denses = OwnBatchSolver.check_same_layout(denses)
     d0 = denses[0]
-    errs = []
-    for cls, rule in ((SmallBatchSolver, _sb.fits), (MidBatchSolver, _mb.fits), (SdpBatchSolver, fits)):
-        try:
-            rule(d0.n, d0.m, d0.seg_type, d0.seg_len)
-        except ValueError as e:
-            errs.append(str(e))
-            continue
-        return cls.from_dense(denses, param, **kw)
-    raise ValueError("none of SmallBatchSolver, MidBatchSolver and SdpBatchSolver takes %d x %d problems with this cone layout (%s): "
-                     "run one FusedSolver per problem" % (d0.m, d0.n, errs[-1]))
+    cls = first_that_takes(_mb.FAMILIES + ((SdpBatchSolver, fits),), d0.n, d0.m, d0.seg_type, d0.seg_len,
+                           "none of SmallBatchSolver, MidBatchSolver and SdpBatchSolver takes %d x %d problems with this cone layout "
+                           "(%s): run one FusedSolver per problem")
+    return cls.from_dense(denses, param, **kw)
