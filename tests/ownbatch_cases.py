@@ -115,6 +115,14 @@ def _part_dense(T, grid, seed):
     return d
 
 
+def _psd_block(T, n, k, seed):
+    """the rows of one PSD cone of order k of a stacked problem in n unknowns: (its k (k + 1) / 2 rows of A, of b, its share of c),
+    those of _sdp_dense(T, n, k, seed).  What _mixed_dense and tests/cone_layouts.py build their PSD segments from"""
+    d = _sdp_dense(T, n, k, seed)
+    sk = tri(k)
+    return np.asarray(d.mat_a, dtype=F).reshape((n, d.m)).T[:sk], np.asarray(d.vec_b, dtype=F)[:sk], np.asarray(d.vec_c, dtype=F)
+
+
 def _mixed_dense(T, seed):
     """in the manner of tests/test_gpu_solver.py::test_iterates_many_psd_cones: 3 nonnegative rows in front (no PSD block starts on a
     multiple of 4), PSD cones of eight orders, then a second-order cone of 17 rows and a rotated one of 5"""
@@ -125,13 +133,12 @@ def _mixed_dense(T, seed):
     bs, st, sl = [np.abs(rng.standard_normal(3)).astype(F) + 1.0], [_lib.CONE_RPOS], [3]
     c0 = np.zeros(n, F)
     for q, k in enumerate(MIXED_ORDERS):
-        d = _sdp_dense(T, n, k, 10 + q + 100 * seed)
-        sk = tri(k)
-        blocks.append(np.asarray(d.mat_a, dtype=F).reshape((n, d.m)).T[:sk])
-        bs.append(np.asarray(d.vec_b, dtype=F)[:sk])
+        rows, b, c = _psd_block(T, n, k, 10 + q + 100 * seed)
+        blocks.append(rows)
+        bs.append(b)
         st.append(_lib.CONE_PSD)
-        sl.append(sk)
-        c0 = c0 + np.asarray(d.vec_c, dtype=F)
+        sl.append(tri(k))
+        c0 = c0 + c
     for t, rows in ((_lib.CONE_SOC, 17), (_lib.CONE_ROTSOC, 5)):   # s = b - A x with large leading entries: inside the cone at x = 0
         blocks.append((rng.standard_normal((rows, n)) / 4).astype(F))
         b = (rng.standard_normal(rows) / 4).astype(F)

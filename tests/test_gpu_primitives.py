@@ -237,6 +237,66 @@ def test_soc_batched_ragged(L):
         d.free(); od.free(); dt.free()
 
 
+def test_soc_exact_boundaries(L):
+    """thip_proj_soc_batched on inputs that sit exactly on the case boundaries of cone_soc.rs:49-61: v an integer Pythagorean tuple
+    (its norm is exact in f32 and in f64) with s0 = ||v||, s0 = -||v||, and both moved by one ulp to either side; s0 = 0 with
+    v = 0; -0.0; a single negative element; rotated cones of two rows with r + s negative, zero and positive.  A wave per cone,
+    and with a cone of 4097 rows in the launch a block per cone.  Not rotated: the result is O.proj cast to f32, exactly.
+    Rotated: within this file's 2e-5 of the cone's largest entry"""
+    from totsu_amd._lib import lib
+    from totsu_amd.fused import DeviceBuffer
+    f = np.float32
+    tuples = [np.array(v, f) for v in ([3, 4], [4, 3], [1, 2, 2], [2, 3, 6], [8, 15], [12, 5], [1, 4, 8], [2, 10, 11])] + [np.ones(64, f)]
+    inf = f(np.inf)
+
+    def around(v):
+        nv = f(np.sqrt(np.sum(v.astype(np.float64) ** 2)))
+        assert float(nv) ** 2 == np.sum(v.astype(np.float64) ** 2)
+        return [np.concatenate([[s0], v]).astype(f) for s0 in (nv, np.nextafter(nv, inf), np.nextafter(nv, -inf),
+                                                                 -nv, np.nextafter(-nv, inf), np.nextafter(-nv, -inf))]
+    cones = [c for v in tuples for c in around(v)]
+    cones += [np.zeros(3, f), np.array([-0.0, 0.0, 0.0], f), np.array([0.0, -0.0, 0.0], f), np.array([-0.0], f), np.array([0.0], f),
+              np.array([-2.5], f), np.array([3.0], f), np.array([-1.0, 0.0], f), np.array([0.0, 1.0], f), np.array([1.0, -1.0], f),
+              np.array([1.0, 1.0], f), np.zeros(0, f)]
+    two = [np.array(v, f) for v in ([-1, -2], [-3, 1], [1, -1], [-1, 1], [0, 0], [-0.0, 0.0], [2, 1], [1, 2], [3, -1], [0, 5], [5, 0])]
+    big = around(np.ones(4096, f))                                   # ||v|| = 64, 4097 rows: soc_k<true>
+    for rot, sets in ((0, (cones, cones + big)), (1, (cones + two, cones + two + big))):
+        for group in sets:
+            if rot:       # and the same boundaries in the rotated coordinates (their f32 rounding moves them off by an ulp or so)
+                group = group + [_to_rotated(c) for c in group if c.size >= 2]
+            lens = [c.size for c in group]
+            offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            x = np.concatenate(group).astype(f)
+            d = DeviceBuffer.from_host(x)
+            od = DeviceBuffer(2 * len(offs))
+            lib.thip_h2d(od.ptr, offs.ctypes.data, 2 * len(offs))      # int64 as pairs of floats
+            lib.thip_proj_soc_batched(d.ptr, od.ptr, len(lens), rot, max(lens))
+            got = d.to_host()
+            d.free(); od.free()
+            worst, wrong = 0.0, []
+            for i, c in enumerate(group):
+                g = got[offs[i]:offs[i + 1]]
+                ref = O.proj(O.CONE_ROTSOC if rot else O.CONE_SOC, c.astype(np.float64))
+                if rot:
+                    err = np.abs(g - ref).max(initial=0.0) / max(np.abs(c).max(initial=0.0), 1e-30)
+                    worst = max(worst, err)
+                    assert err <= 2e-5, (i, c[:4], g[:4], ref[:4])
+                else:
+                    want = ref.astype(f)
+                    if not np.array_equal(g, want):
+                        print("cone %d of %d rows, input %s: got %s, O.proj in f32 %s" % (i, c.size, c[:4], g[:4], want[:4]))
+                        wrong.append(i)
+            assert not wrong, (rot, max(lens), wrong)
+            print("rotated %d, %d cones, longest %d: worst error %.2e" % (rot, len(lens), max(lens), worst))
+
+
+def _to_rotated(c):
+    """(r, s) -> ((r + s), (r - s)) / sqrt 2 on the first two entries, in f64, rounded to f32"""
+    x = c.astype(np.float64)
+    x[0], x[1] = (x[0] + x[1]) / np.sqrt(2.0), (x[0] - x[1]) / np.sqrt(2.0)
+    return x.astype(np.float32)
+
+
 def test_rng_matches_oracle_bitwise(L):
     from totsu_amd._lib import lib
     from totsu_amd.fused import DeviceBuffer

@@ -74,27 +74,30 @@ __global__ __launch_bounds__(BLK) void soc_k(float *__restrict__ x0, float *__re
     const double sumsq = BLOCKWISE ? block_sum_d(acc, shd) : wave_sum_d(acc);
     const float norm_v = (float)sqrt(sumsq);
 
-    // cone_soc.rs:49-61
-    float f, s_new;
-    if (norm_v <= -s0) { f = 0.0f; s_new = 0.0f; }
-    else if (norm_v <= s0) { f = 1.0f; s_new = s0; }
-    else { f = (1.0f + s0 / norm_v) / 2.0f; s_new = (norm_v + s0) / 2.0f; }
+    // cone_soc.rs:49-61.  The factor, the new head and the products with the factor are formed in f64, like the squares: in f32
+    // 1 + s0 / ||v|| cancels near s0 = -||v|| (one ulp inside that edge the f32 factor is off by a quarter of its value), and
+    // one ulp inside s0 = ||v|| it rounds to 1.  Each result is the f64 one rounded once
+    double f;
+    float s_new;
+    if (norm_v <= -s0) { f = 0.0; s_new = 0.0f; }
+    else if (norm_v <= s0) { f = 1.0; s_new = s0; }
+    else { f = (1.0 + (double)s0 / (double)norm_v) / 2.0; s_new = (float)(((double)norm_v + (double)s0) / 2.0); }
 
     if (!rotated) {
-        if (f == 1.0f && rx == nullptr) return;
+        if (f == 1.0 && rx == nullptr) return;
         if (gid == 0) {
             x[beg] = s_new;
             if (rx) rx[beg] = rx[beg] - 2.0f * s_new;
         }
         for (int64_t i = beg + 1 + gid; i < end; i += gsz) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
+            const float nv = (f == 1.0) ? x[i] : (float)(f * (double)x[i]);
             x[i] = nv;
             if (rx) rx[i] = rx[i] - 2.0f * nv;
         }
     } else {
-        const float v1n = f * v1;
+        const float v1n = (float)(f * (double)v1);
         for (int64_t i = beg + 2 + gid; i < end; i += gsz) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
+            const float nv = (f == 1.0) ? x[i] : (float)(f * (double)x[i]);
             x[i] = nv;
             if (rx) rx[i] = rx[i] - 2.0f * nv;
         }
