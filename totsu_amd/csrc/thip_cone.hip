@@ -8,6 +8,7 @@
 // all cones, one wavefront per cone (width-64 shuffle tree for ||v||^2), or one workgroup per cone when
 // cones are long.
 #include "thip_common.h"
+#include "thip_step.h"
 
 using namespace thip;
 
@@ -40,74 +41,9 @@ __global__ __launch_bounds__(BLK) void soc_k(float *__restrict__ x0, float *__re
     if (cone >= n_cones) { cone -= n_cones; x = x1; rx = rx1; }
     const int64_t beg = begs ? begs[cone] : 0;
     const int64_t end = ends ? ends[cone] : single_len;
-    const int64_t len = end - beg;
-    if (len <= 0) return;                  // uniform per group
-    const int gid = BLOCKWISE ? (int)threadIdx.x : lane;
-    const int gsz = BLOCKWISE ? BLK : 64;
-    const float fsqrt2 = sqrtf(2.0f);
-
-    if (rotated && len == 1) {             // cone_rotsoc.rs:46-49
-        if (gid == 0) {
-            const float v = fmaxf(x[beg], 0.0f);
-            x[beg] = v;
-            if (rx) rx[beg] = rx[beg] - 2.0f * v;
-        }
-        return;
-    }
-
-    float s0, v1 = 0.0f;
-    if (rotated) {                         // cone_rotsoc.rs:51-54
-        const float r = x[beg], s = x[beg + 1];
-        s0 = (r + s) / fsqrt2;
-        v1 = (r - s) / fsqrt2;
-    } else {
-        s0 = x[beg];
-    }
-
-    // ||v|| over x[beg+1 .. end): the reference takes LinAlg::norm (cone_soc.rs:47), an nrm2 that neither underflows nor
-    // overflows on the squares -- here the squares are f64
-    double acc = 0.0;
-    for (int64_t i = beg + 1 + gid; i < end; i += gsz) {
-        const double t = (double)((rotated && i == beg + 1) ? v1 : x[i]);
-        acc += t * t;
-    }
-    const double sumsq = BLOCKWISE ? block_sum_d(acc, shd) : wave_sum_d(acc);
-    const float norm_v = (float)sqrt(sumsq);
-
-    // cone_soc.rs:49-61.  The factor, the new head and the products with the factor are formed in f64, like the squares: in f32
-    // 1 + s0 / ||v|| cancels near s0 = -||v|| (one ulp inside that edge the f32 factor is off by a quarter of its value), and
-    // one ulp inside s0 = ||v|| it rounds to 1.  Each result is the f64 one rounded once
-    double f;
-    float s_new;
-    if (norm_v <= -s0) { f = 0.0; s_new = 0.0f; }
-    else if (norm_v <= s0) { f = 1.0; s_new = s0; }
-    else { f = (1.0 + (double)s0 / (double)norm_v) / 2.0; s_new = (float)(((double)norm_v + (double)s0) / 2.0); }
-
-    if (!rotated) {
-        if (f == 1.0 && rx == nullptr) return;
-        if (gid == 0) {
-            x[beg] = s_new;
-            if (rx) rx[beg] = rx[beg] - 2.0f * s_new;
-        }
-        for (int64_t i = beg + 1 + gid; i < end; i += gsz) {
-            const float nv = (f == 1.0) ? x[i] : (float)(f * (double)x[i]);
-            x[i] = nv;
-            if (rx) rx[i] = rx[i] - 2.0f * nv;
-        }
-    } else {
-        const float v1n = (float)(f * (double)v1);
-        for (int64_t i = beg + 2 + gid; i < end; i += gsz) {
-            const float nv = (f == 1.0) ? x[i] : (float)(f * (double)x[i]);
-            x[i] = nv;
-            if (rx) rx[i] = rx[i] - 2.0f * nv;
-        }
-        if (gid == 0) {                    // cone_rotsoc.rs:58-61
-            const float a = (s_new + v1n) / fsqrt2, b = (s_new - v1n) / fsqrt2;
-            x[beg] = a;
-            x[beg + 1] = b;
-            if (rx) { rx[beg] = rx[beg] - 2.0f * a; rx[beg + 1] = rx[beg + 1] - 2.0f * b; }
-        }
-    }
+    // cone_soc.rs:38-65, cone_rotsoc.rs:38-65: the factor, the new head and the products with the factor in f64, like the squares
+    soc_project<double, int64_t, BLOCKWISE>(x, rx, beg, end, rotated, BLOCKWISE ? (int)threadIdx.x : lane,
+                                            BLOCKWISE ? BLK : 64, shd);
 }
 
 template <bool BLOCKWISE>

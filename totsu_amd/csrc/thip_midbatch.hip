@@ -11,7 +11,7 @@
 // The LDS map, the pass over A (mb_pass) and the bodies of both kernels are thip_midstream.h's, shared with the SDP batch
 // (thip_sdpbatch.hip), which adds PSD cones to the block-cone phase; this family takes none.  mb_check is the single source of the limit.
 //
-// The rest of the iteration is the small batch's, on the same device functions (thip_ownbatch.h): sb_comp_add, the class bytes,
+// The rest of the iteration is the small batch's, on the same device functions (thip_step.h, thip_ownbatch.h): the class bytes,
 // one wave per block cone (sb_soc), block_sums, both endings of status_eval.
 //
 // This file: the two kernels, the shape rule and the family's table; the C API is thip_ownbatch.h's, instantiated by the last line.

@@ -219,18 +219,17 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
         mb_pass<false>(A, vec, m, n, u, v, h, g, hp, gp);
         block_sums<4>(q, sh);
         const float cx_old = q[2], by_old = q[3];
-        for (int i = tid; i < n; i += T) xx[i] = sb_comp_add(xx[i], Tx[i] * (g[i] + c[i] * s.kappa), kx, i, comp);
+        for (int i = tid; i < n; i += T) xx[i] = kahan_add_at(xx[i], inc_xx(Tx[i], g[i], c[i], s.kappa), comp, kx, i);
         for (int i = tid; i < m; i += T) {
             const unsigned char k = cls[i];
             const float oy = xy[i], os = xs[i];
-            float ny = sb_comp_add(oy, Ty[i] * (b[i] * s.kappa - h[i]), ky, i, comp);
-            float ns = sb_comp_add(os, Ts[i] * v[i], ks, i, comp);
-            if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
-            else if (k == 0) { ns = 0.0f; }
+            float ny = kahan_add_at(oy, inc_xy(Ty[i], b[i], s.kappa, h[i]), comp, ky, i);
+            float ns = kahan_add_at(os, inc_xs(Ts[i], v[i]), comp, ks, i);
+            cone_elementwise(k, ny, ns);
             xy[i] = ny;
             xs[i] = ns;
             h[i] = oy;                                             // (rx_y is not needed: what sb_soc writes there is dropped)
-            rxs[i] = (k < 2) ? os - 2.0f * ns : os;
+            rxs[i] = cone_rx(k, os, ns);
         }
         {
             const float old = s.tau;
@@ -255,12 +254,12 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
         // ---- y += S o (-K rx) (ycrit_k), the pair carried on ----
         for (int i = tid; i < n; i += T) {
             const float gn = g[i];
-            u[i] = sb_comp_add(u[i], Tx[i] * (-(gx[i] - 2.0f * gn) - c[i] * s.rtau), ku, i, comp);
+            u[i] = kahan_add_at(u[i], inc_u(Tx[i], rx_fold(gx[i], gn), c[i], s.rtau), comp, ku, i);
             gx[i] = gn;
         }
         for (int i = tid; i < m; i += T) {
             const float hn = h[i];
-            v[i] = sb_comp_add(v[i], Sv[i] * ((hx[i] - 2.0f * hn) + rxs[i] - b[i] * s.rtau), kv, i, comp);
+            v[i] = kahan_add_at(v[i], inc_v(Sv[i], rx_fold(hx[i], hn), rxs[i], b[i], s.rtau), comp, kv, i);
             hx[i] = hn;
         }
         s.kappa = fminf(s.kappa + s.s_kappa * ((cx_old - 2.0f * cx) + (by_old - 2.0f * by)), 0.0f);     // solver.rs:566-567

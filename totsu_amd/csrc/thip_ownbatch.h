@@ -2,7 +2,7 @@
 // thip_sdpbatch.hip: A streamed from memory, thip_midstream.h).
 //   device: the launch arguments (ObArgs), the status block and the slot of a problem, the problem's scalars (ObScalars), the
 //           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
-//           functions of the iteration that do not touch A (block_sums, sb_comp_add, sb_soc).  The two recurrences -- three passes
+//           functions of the iteration that do not touch A (block_sums; thip_step.h: the arithmetic every loop shares).  The two recurrences -- three passes
 //           from LDS, two carried passes from memory -- stay with their families.
 //   host:   slots, arena, all 64-byte status blocks in one copy, the live list, replace as the init kernel on one slot, and the C
 //           API itself: a family is a table (ObFamily: its words, its shape rule, its thread choice, its LDS map's size, its
@@ -11,6 +11,7 @@
 #pragma once
 
 #include "thip_common.h"
+#include "thip_step.h"
 
 #include <algorithm>
 #include <mutex>
@@ -85,73 +86,11 @@ __device__ __forceinline__ void block_sums(float *q, float *sh)
     }
 }
 
-// comp_add of thip_solver_kernels.inc
-__device__ __forceinline__ float sb_comp_add(float x, float inc, float *k, int i, bool comp)
-{
-    if (!comp) return x + inc;
-    const float y = inc - k[i];
-    const float t = x + y;
-    k[i] = (t - x) - y;
-    return t;
-}
-
-// soc_k of thip_cone.hip for one cone by one wave, with rx <- rx - 2 x folded in (cone_soc.rs:38-65, cone_rotsoc.rs:38-65)
+// one cone by one wave, with rx <- rx - 2 x folded in: the factor in f32 (thip_step.h)
 __device__ __forceinline__ void sb_soc(float *x, float *rx, int beg, int end, int rotated, int lane)
 {
-    const int len = end - beg;
-    if (len <= 0) return;
-    const float fsqrt2 = sqrtf(2.0f);
-    if (rotated && len == 1) {
-        if (lane == 0) {
-            const float v = fmaxf(x[beg], 0.0f);
-            x[beg] = v;
-            rx[beg] = rx[beg] - 2.0f * v;
-        }
-        return;
-    }
-    float s0, v1 = 0.0f;
-    if (rotated) {
-        const float r = x[beg], s = x[beg + 1];
-        s0 = (r + s) / fsqrt2;
-        v1 = (r - s) / fsqrt2;
-    } else {
-        s0 = x[beg];
-    }
-    double acc = 0.0;
-    for (int i = beg + 1 + lane; i < end; i += 64) {
-        const double t = (double)((rotated && i == beg + 1) ? v1 : x[i]);
-        acc += t * t;
-    }
-    const float norm_v = (float)sqrt(wave_sum_d(acc));
-    float f, s_new;
-    if (norm_v <= -s0) { f = 0.0f; s_new = 0.0f; }
-    else if (norm_v <= s0) { f = 1.0f; s_new = s0; }
-    else { f = (1.0f + s0 / norm_v) / 2.0f; s_new = (norm_v + s0) / 2.0f; }
-    if (!rotated) {
-        if (lane == 0) {
-            x[beg] = s_new;
-            rx[beg] = rx[beg] - 2.0f * s_new;
-        }
-        for (int i = beg + 1 + lane; i < end; i += 64) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
-            x[i] = nv;
-            rx[i] = rx[i] - 2.0f * nv;
-        }
-    } else {
-        const float v1n = f * v1;
-        for (int i = beg + 2 + lane; i < end; i += 64) {
-            const float nv = (f == 1.0f) ? x[i] : f * x[i];
-            x[i] = nv;
-            rx[i] = rx[i] - 2.0f * nv;
-        }
-        if (lane == 0) {
-            const float a = (s_new + v1n) / fsqrt2, b = (s_new - v1n) / fsqrt2;
-            x[beg] = a;
-            x[beg + 1] = b;
-            rx[beg] = rx[beg] - 2.0f * a;
-            rx[beg + 1] = rx[beg + 1] - 2.0f * b;
-        }
-    }
+    __builtin_assume(rx != nullptr);
+    soc_project<float, int, false>(x, rx, beg, end, rotated, lane, 64, nullptr);
 }
 
 // the scalars of a problem, held in registers across a launch: from its status block and back
@@ -242,8 +181,9 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
 }
 
 // the sums of the criteria of the iterate (x_x, x_y, x_s) given h = A x_x, g = A^T x_y: q <- ||p||^2, b.x_y, ||d||^2, c.x_x
-// (post_k / ycrit_k).  conv (tau > eps_zero) and rt (1 / tau then, else 1) are formed here and again in ob_status_eval, from tau, not
-// handed in: the compiler then sees, as it did with one body per family, that rt is 1 / tau wherever conv holds
+// conv (tau > eps_zero) and rt (1 / tau then, else 1) are formed here, from tau, not handed in: the compiler then sees that rt is
+// 1 / tau wherever conv holds.  p and d are crit_p's and crit_d's (thip_step.h), written out: those form conv and rt per call, which
+// the compiler hoists out of a loop but not out of two -- one more division per iteration here
 __device__ __forceinline__ void ob_criteria_sums(float *q, int n, int m, float tau, float eps_zero, const float *b, const float *c,
                                                  const float *xx, const float *xy, const float *xs, const float *h, const float *g,
                                                  float *sh)
@@ -272,38 +212,13 @@ __device__ __forceinline__ void ob_criteria_sums(float *q, int n, int m, float t
 // where a problem stops (thip_param's fields; passed by value, see ob_problem)
 struct ObLimits { float eps_acc, eps_inf, eps_zero; long long max_iter; };
 
-// status_eval (thip_solver_kernels.inc) on those sums: kind, the criteria and the state of s, whose tau is the new iterate's.
-// Uniform: every thread holds the same sums.  The state is a local until the end, so that the chain of ifs stays a chain of branches
+// the verdict on those sums into s, whose tau is the new iterate's.  Uniform: every thread holds the same sums
 __device__ __forceinline__ void ob_status_eval(ObScalars &s, const ObLimits a, float pp, float by, float dd, float cx)
 {
-    const bool conv = s.tau > a.eps_zero;
-    const float rt = conv ? 1.0f / s.tau : 1.0f;
-    int state = s.state;
-    const bool excess_iter = (a.max_iter >= 0) ? (s.iter + 1 >= a.max_iter) : false;
-    const float norm_p = sqrtf(pp), norm_d = sqrtf(dd);
-    if (conv) {
-        const float g_x = rt * cx;
-        const float g_y = rt * by;
-        const float gg = g_x + g_y;
-        s.kind = 0;
-        s.cri0 = norm_p / (1.0f + s.norm_b);
-        s.cri1 = norm_d / (1.0f + s.norm_c);
-        s.cri2 = fabsf(gg) / (1.0f + fabsf(g_x) + fabsf(g_y));
-        const bool term_conv = (s.cri0 <= a.eps_acc) && (s.cri1 <= a.eps_acc) && (s.cri2 <= a.eps_acc);
-        if (term_conv) state = THIP_ST_OK;
-        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-    } else {
-        const float m_cx = -cx;
-        const float m_by = -by;
-        s.kind = 1;
-        s.cri0 = (m_cx > a.eps_zero) ? norm_p * s.norm_c / m_cx : __builtin_inff();
-        s.cri1 = (m_by > a.eps_zero) ? norm_d * s.norm_b / m_by : __builtin_inff();
-        s.cri2 = 0.0f;
-        if (s.cri0 <= a.eps_inf) state = THIP_ST_UNBOUNDED;
-        else if (s.cri1 <= a.eps_inf) state = THIP_ST_INFEASIBLE;
-        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-    }
-    s.state = state;
+    const StepVerdict o = step_verdict(s.tau, s.iter, s.norm_b, s.norm_c, a.eps_acc, a.eps_inf, a.eps_zero, a.max_iter, pp, by, dd, cx,
+                                       s.state);
+    s.kind = o.kind; s.cri0 = o.cri0; s.cri1 = o.cri1; s.cri2 = o.cri2;
+    s.state = o.state;
 }
 
 __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,

@@ -5,8 +5,8 @@
 //
 // Recurrence: the 3-pass ("fused") one -- A u / A^T v, A rx_x / A^T rx_y, A x_x / A^T x_y, each pair from LDS.  A pass over an
 // LDS-resident A is a few hundred cycles, so the carried form's saved pass is not worth its two extra state vectors and its second
-// rounding of K rx.  The element-wise arithmetic is that of xupdate_k / ycrit_k / status_eval (thip_solver_kernels.inc) and of
-// soc_k / group_min_k (thip_cone.hip).
+// rounding of K rx.  The element-wise arithmetic is thip_step.h's, as in every other loop of the step; the preconditioner's
+// minimum over a block cone is group_min_k's (thip_cone.hip).
 //
 // LDS: A with leading dimension lda = m | 1 (odd): the row walk of A x has consecutive lanes on consecutive words, the column walk of
 // A^T y has consecutive lanes lda words apart -- an odd stride visits every bank once.  Behind A: every vector of the iteration.
@@ -180,21 +180,20 @@ __global__ __launch_bounds__(1024) void smallbatch_k(const SbArgs a)
         block_sums<2>(q, sh);
         for (int i = tid; i < n; i += T) {
             const float old = xx[i];
-            const float nx = sb_comp_add(old, Tx[i] * (g[i] + c[i] * s.kappa), kx, i, comp);
+            const float nx = kahan_add_at(old, inc_xx(Tx[i], g[i], c[i], s.kappa), comp, kx, i);
             xx[i] = nx;
-            rxx[i] = old - 2.0f * nx;
+            rxx[i] = rx_fold(old, nx);
         }
         for (int i = tid; i < m; i += T) {
             const unsigned char k = cls[i];
             const float oy = xy[i], os = xs[i];
-            float ny = sb_comp_add(oy, Ty[i] * (b[i] * s.kappa - h[i]), ky, i, comp);
-            float ns = sb_comp_add(os, Ts[i] * v[i], ks, i, comp);
-            if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
-            else if (k == 0) { ns = 0.0f; }
+            float ny = kahan_add_at(oy, inc_xy(Ty[i], b[i], s.kappa, h[i]), comp, ky, i);
+            float ns = kahan_add_at(os, inc_xs(Ts[i], v[i]), comp, ks, i);
+            cone_elementwise(k, ny, ns);
             xy[i] = ny;
             xs[i] = ns;
-            rxy[i] = (k < 2) ? oy - 2.0f * ny : oy;
-            rxs[i] = (k < 2) ? os - 2.0f * ns : os;
+            rxy[i] = cone_rx(k, oy, ny);
+            rxs[i] = cone_rx(k, os, ns);
         }
         {
             const float old = s.tau;
@@ -217,8 +216,8 @@ __global__ __launch_bounds__(1024) void smallbatch_k(const SbArgs a)
         for (int i = tid; i < m; i += T) q[1] = fmaf(b[i], rxy[i], q[1]);
         products<false>(A, lda, m, n, rxx, rxy, h, g, red);
         block_sums<2>(q, sh);
-        for (int i = tid; i < n; i += T) u[i] = sb_comp_add(u[i], Tx[i] * (-g[i] - c[i] * s.rtau), ku, i, comp);
-        for (int i = tid; i < m; i += T) v[i] = sb_comp_add(v[i], Sv[i] * (h[i] + rxs[i] - b[i] * s.rtau), kv, i, comp);
+        for (int i = tid; i < n; i += T) u[i] = kahan_add_at(u[i], inc_u(Tx[i], g[i], c[i], s.rtau), comp, ku, i);
+        for (int i = tid; i < m; i += T) v[i] = kahan_add_at(v[i], inc_v(Sv[i], h[i], rxs[i], b[i], s.rtau), comp, kv, i);
         s.kappa = fminf(s.kappa + s.s_kappa * (q[0] + q[1]), 0.0f);     // solver.rs:566-567
         __syncthreads();
         // ---- criteria: h = A x_x, g = A^T x_y (post_k / ycrit_k / status_eval) ----

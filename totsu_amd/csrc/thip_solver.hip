@@ -19,6 +19,7 @@
 // vector is replicated; the only exchange is a sum-all-reduce of the n-vector A_g^T y_g (with the sharded
 // scalars riding in its tail) per transposed product.
 #include "thip_common.h"
+#include "thip_step.h"
 
 #include <algorithm>
 #include <cmath>

@@ -87,8 +87,6 @@ __global__ __launch_bounds__(BLK) void post_k(int n, int m,
     const size_t gstride = (size_t)gridDim.x * 64;
     float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
     const float tau = st->tau;
-    const bool conv = tau > eps_zero;
-    const float rt = conv ? 1.0f / tau : 1.0f;
 
     for (size_t i0 = blockIdx.x * (size_t)64; i0 < (size_t)n; i0 += gstride) {
         const size_t i = i0 + e;
@@ -118,9 +116,7 @@ __global__ __launch_bounds__(BLK) void post_k(int n, int m,
             if (dm_a) q1 = fmaf(dm_a[i], dm_b[i], q1);
             if (crit) {
                 const float bi = b[i];
-                float p;
-                if (conv) { p = xs[i] * rt - bi; p = fmaf(rt, s, p); }
-                else p = xs[i] + s;
+                const float p = crit_p(tau, eps_zero, xs[i], bi, s);
                 q2 = fmaf(p, p, q2);
                 q3 = fmaf(bi, xy[i], q3);
             }
@@ -149,17 +145,8 @@ __device__ __forceinline__ float block_sum_of_partials(const float *part, int np
     return (float)acc;
 }
 
-// x + inc, optionally compensated: k[i] carries the rounding error of the previous additions into this entry (Kahan).
-// The f32 iterate otherwise stops moving once an update is below half an ulp of the entry while the dual residual
-// is still ~1e-5..1e-4 (a floor the reference's f32 arithmetic has too; numpy emulation: 6.3e-6 -> 1e-7 at n = 200).
-__device__ __forceinline__ float comp_add(float x, float inc, float *__restrict__ k, size_t i)
-{
-    if (k == nullptr) return x + inc;
-    const float y = inc - k[i];
-    const float t = x + y;
-    k[i] = (t - x) - y;
-    return t;
-}
+// x + inc, compensated (kahan_add, thip_step.h) where the iterate has Kahan terms: k != NULL
+__device__ __forceinline__ float comp_add(float x, float inc, float *k, size_t i) { return kahan_add_at(x, inc, k != nullptr, k, i); }
 
 // x-update, solver.rs:538-555 (everything except the block cones):
 //   x += T o tx with tx = -K^T y (SelfDualEmbed::trans_op, solver.rs:133-157):
@@ -200,22 +187,21 @@ __global__ __launch_bounds__(BLK) void xupdate_k(int n, int m, const float *__re
     if (do_n)
     for (size_t i = blockIdx.x * (size_t)BLK + threadIdx.x; i < (size_t)n; i += gstride) {
         const float old = xx[i];
-        const float nw = comp_add(old, Tx[i] * (gT[i] + c[i] * kappa), kx, i);
+        const float nw = comp_add(old, inc_xx(Tx[i], gT[i], c[i], kappa), kx, i);
         xx[i] = nw;
-        rxx[i] = old - 2.0f * nw;
+        rxx[i] = rx_fold(old, nw);
     }
     if (do_m)
     for (size_t i = blockIdx.x * (size_t)BLK + threadIdx.x; i < (size_t)m; i += gstride) {
         const unsigned char k = cls[i];
         const float oy = xy[i], os = xs[i];
-        float ny = comp_add(oy, Ty[i] * (b[i] * kappa - hN[i]), ky, i);
-        float ns = comp_add(os, Ts[i] * v[i], ks, i);
-        if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
-        else if (k == 0) { ns = 0.0f; }
+        float ny = comp_add(oy, inc_xy(Ty[i], b[i], kappa, hN[i]), ky, i);
+        float ns = comp_add(os, inc_xs(Ts[i], v[i]), ks, i);
+        cone_elementwise(k, ny, ns);
         xy[i] = ny;
         xs[i] = ns;
-        rxy[i] = (k < 2) ? oy - 2.0f * ny : oy;
-        rxs[i] = (k < 2) ? os - 2.0f * ns : os;
+        rxy[i] = cone_rx(k, oy, ny);
+        rxs[i] = cone_rx(k, os, ns);
     }
     if (do_tau && blockIdx.x == 0 && threadIdx.x == 0) {
         // every other thread only reads st->kappa / st->stop; tau is written by this thread alone
@@ -271,8 +257,6 @@ __global__ __launch_bounds__(BLK) void ycrit_k(int n, int m, int doy, int carrie
     }
     const float rtau = st->r_tau;
     const float tau = st->tau;
-    const bool conv = tau > eps_zero;
-    const float rt = conv ? 1.0f / tau : 1.0f;
     const size_t gstride = (size_t)gridDim.x * BLK;
     float dd = 0.0f, cx = 0.0f;
     if (do_n)
@@ -280,12 +264,12 @@ __global__ __launch_bounds__(BLK) void ycrit_k(int n, int m, int doy, int carrie
         const float ci = c[i];
         if (doy) {
             float g2;
-            if (carried) { const float nw = g3[i]; g2 = gP[i] - 2.0f * nw; gP[i] = nw; }
+            if (carried) { const float nw = g3[i]; g2 = rx_fold(gP[i], nw); gP[i] = nw; }
             else g2 = g2in[i];
-            u[i] = comp_add(u[i], Su[i] * (-g2 - ci * rtau), ku, i);
+            u[i] = comp_add(u[i], inc_u(Su[i], g2, ci, rtau), ku, i);
         }
         if (docrit) {
-            const float d = conv ? fmaf(rt, g3[i], ci) : g3[i];
+            const float d = crit_d(tau, eps_zero, ci, g3[i]);
             dd = fmaf(d, d, dd);
             cx = fmaf(ci, xx[i], cx);
         }
@@ -294,9 +278,9 @@ __global__ __launch_bounds__(BLK) void ycrit_k(int n, int m, int doy, int carrie
         if (do_m)
         for (size_t i = blockIdx.x * (size_t)BLK + threadIdx.x; i < (size_t)m; i += gstride) {
             float h2;
-            if (carried) { const float nw = h3[i]; h2 = hP[i] - 2.0f * nw; hP[i] = nw; }
+            if (carried) { const float nw = h3[i]; h2 = rx_fold(hP[i], nw); hP[i] = nw; }
             else h2 = h2in[i];
-            v[i] = comp_add(v[i], Sv[i] * (h2 + rxs[i] - b[i] * rtau), kv, i);
+            v[i] = comp_add(v[i], inc_v(Sv[i], h2, rxs[i], b[i], rtau), kv, i);
         }
         if (do_kappa && blockIdx.x == 0 && threadIdx.x == 0) {
             const float k = st->kappa + st->s_kappa * (dc + db);
@@ -354,32 +338,10 @@ __device__ __forceinline__ StatOut status_eval(const StatArgs &a, float tau, lon
     const float pp = (float)sums[0], by = (float)sums[1];
     const float dd = (float)sums[2], cx = (float)sums[3];
     const float dcu = (float)sums[4], dbv = (float)sums[5];
-    const bool excess_iter = (a.max_iter >= 0) ? (i + 1 >= a.max_iter) : false;
-    const float norm_p = sqrtf(pp), norm_d = sqrtf(dd);
-    int state = THIP_ST_RUNNING;
-    if (tau > a.eps_zero) {
-        const float rt = 1.0f / tau;
-        const float g_x = rt * cx;
-        const float g_y = rt * by;
-        const float g = g_x + g_y;
-        const float cri_pri = norm_p / (1.0f + norm_b);
-        const float cri_dual = norm_d / (1.0f + norm_c);
-        const float cri_gap = fabsf(g) / (1.0f + fabsf(g_x) + fabsf(g_y));
-        o.kind = 0; o.cri[0] = cri_pri; o.cri[1] = cri_dual; o.cri[2] = cri_gap;
-        const bool term_conv = (cri_pri <= a.eps_acc) && (cri_dual <= a.eps_acc) && (cri_gap <= a.eps_acc);
-        if (term_conv) state = THIP_ST_OK;
-        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-    } else {
-        const float m_cx = -cx;
-        const float m_by = -by;
-        const float cri_unbdd = (m_cx > a.eps_zero) ? norm_p * norm_c / m_cx : __builtin_inff();
-        const float cri_infeas = (m_by > a.eps_zero) ? norm_d * norm_b / m_by : __builtin_inff();
-        o.kind = 1; o.cri[0] = cri_unbdd; o.cri[1] = cri_infeas; o.cri[2] = 0.0f;
-        const bool term_unbdd = cri_unbdd <= a.eps_inf, term_infeas = cri_infeas <= a.eps_inf;
-        if (term_unbdd) state = THIP_ST_UNBOUNDED;
-        else if (term_infeas) state = THIP_ST_INFEASIBLE;
-        else if (excess_iter) state = THIP_ST_EXCESS_ITER;
-    }
+    const StepVerdict sv = step_verdict(tau, i, norm_b, norm_c, a.eps_acc, a.eps_inf, a.eps_zero, a.max_iter, pp, by, dd, cx,
+                                        THIP_ST_RUNNING);
+    const int state = sv.state;
+    o.kind = sv.kind; o.cri[0] = sv.cri0; o.cri[1] = sv.cri1; o.cri[2] = sv.cri2;
     o.state = state;
     if (state == THIP_ST_RUNNING && a.ps_cu != nullptr) {
         // sweep schedule: c.u_k and b.v_k are complete here too -- the tau update of the NEXT step (solver.rs:551-552)
@@ -420,8 +382,36 @@ __global__ __launch_bounds__(BLK) void status_k(const StatArgs a, DevStatus *st)
 //   SWEEP     kappa_k (every workgroup for itself, at entry) ; u_k, x_x_{k+1}, gP = A^T x_y_k, the shares of A u_k and A x_x_{k+1}, and -- per workgroup, over the columns it
 //             writes -- the partial sums over n: ||d_k||^2, c.x_x_k, c.u_k, c.rx_x_k
 //   status_k  the termination test of iterate k (solver.rs:381-451)
-// The arithmetic of every update is xupdate_k's / ycrit_k's / post_k's.
+// The arithmetic of every update is thip_step.h's.
 // ---------------------------------------------------------------------------------------------------
+// row i's shares of hN = A u (sa) and of A x_x (sb): the quarter kq of the groups, 32 / 8 / 1 at a time.  Sixteen loads in flight,
+// added in the order of the plain loop: the shares were written by workgroups on other XCDs, so every one of them is a trip to
+// the Infinity Cache.  !ok: both zero, nothing read
+__device__ __forceinline__ void sum_shares(const float *partH, size_t mpad, int ngroups, int kq, size_t i, bool ok,
+                                           float &sa, float &sb)
+{
+    float sa0 = 0.0f, sa1 = 0.0f, sb0 = 0.0f, sb1 = 0.0f;
+    if (ok) {
+        int g = kq;
+        for (; g + 28 < ngroups; g += 32) {
+            float t[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float *q = partH + (size_t)(g + 8 * j) * 2 * mpad + i;
+                t[4 * j] = q[0]; t[4 * j + 1] = q[mpad]; t[4 * j + 2] = q[8 * mpad]; t[4 * j + 3] = q[9 * mpad];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sa0 += t[4 * j]; sb0 += t[4 * j + 1]; sa1 += t[4 * j + 2]; sb1 += t[4 * j + 3]; }
+        }
+        for (; g + 4 < ngroups; g += 8) {
+            const float *q = partH + (size_t)g * 2 * mpad + i;
+            sa0 += q[0]; sb0 += q[mpad]; sa1 += q[8 * mpad]; sb1 += q[9 * mpad];
+        }
+        if (g < ngroups) { sa0 += partH[((size_t)g * 2 + 0) * mpad + i]; sb0 += partH[((size_t)g * 2 + 1) * mpad + i]; }
+    }
+    sa = sa0 + sa1; sb = sb0 + sb1;
+}
+
 // MERGE (no block cones: every row's projection is element-wise): the same launch also does sw_vm_k's part of the row -- v_k,
 // the sums over m -- with tau_k / rx_tau as the previous termination test left them (DevStatus::tau_next), and leaves its
 // four block partials in `part` (gridDim.x each)
@@ -459,34 +449,29 @@ __global__ __launch_bounds__(FLAT ? 1024 : BLK) void sw_xm_k(int m, int ngroups,
         tau = st->tau_next; rtau = st->r_tau_next;      // tau_k, rx_tau as status_k / sw_tau_k left them (read-only here)
     }
     const float kappa = st->kappa;
-    const bool conv = tau > eps_zero;
-    const float rt = conv ? 1.0f / tau : 1.0f;
     float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
     // 256 threads = 64 rows x 4 group lanes (post_k's shape): the sum over the groups' shares of one row -- up to 256 of
     // them, 128 at the 10 000-variable LP -- is split four ways, combined through LDS, and lane 0 of a row does the update
     auto row = [&](const size_t i, const float hN, const float hx) {
             const unsigned char k = cls[i];
             const float oy = xy[i], os = xs[i], bi = b[i], vi = v[i];
-            float ny = comp_add(oy, Ty[i] * (bi * kappa - hN), ky, i);
-            float ns = comp_add(os, Ts[i] * vi, ks, i);
-            if (k == 1) { ny = fmaxf(ny, 0.0f); ns = fmaxf(ns, 0.0f); }
-            else if (k == 0) { ns = 0.0f; }
+            float ny = comp_add(oy, inc_xy(Ty[i], bi, kappa, hN), ky, i);
+            float ns = comp_add(os, inc_xs(Ts[i], vi), ks, i);
+            cone_elementwise(k, ny, ns);
             xy[i] = ny;
             xs[i] = ns;
-            const float ry = (k < 2) ? oy - 2.0f * ny : oy, rs = (k < 2) ? os - 2.0f * ns : os;
+            const float ry = cone_rx(k, oy, ny), rs = cone_rx(k, os, ns);
             rxy[i] = ry;
             rxs[i] = rs;
             if constexpr (MERGE) {
                 // sw_vm_k's row: v_k from h2 = hP - 2 h3 (h3 = A x_x_k) ; the criteria sums over m
-                const float h2 = hP[i] - 2.0f * hx;
+                const float h2 = rx_fold(hP[i], hx);
                 hP[i] = hx;
-                const float vn = comp_add(vi, Sv[i] * (h2 + rs - bi * rtau), kv, i);
+                const float vn = comp_add(vi, inc_v(Sv[i], h2, rs, bi, rtau), kv, i);
                 v[i] = vn;
                 q0 = fmaf(bi, vn, q0);
                 q1 = fmaf(bi, ry, q1);
-                float p;
-                if (conv) { p = ns * rt - bi; p = fmaf(rt, hx, p); }
-                else p = ns + hx;
+                const float p = crit_p(tau, eps_zero, ns, bi, hx);
                 q2 = fmaf(p, p, q2);
                 q3 = fmaf(bi, ny, q3);
             } else {
@@ -508,28 +493,8 @@ __global__ __launch_bounds__(FLAT ? 1024 : BLK) void sw_xm_k(int m, int ngroups,
     const size_t gstride = (size_t)gridDim.x * 64;
     for (size_t i0 = blockIdx.x * (size_t)64; i0 < (size_t)m; i0 += gstride) {
         const size_t i = i0 + e;
-        float sa0 = 0.0f, sa1 = 0.0f, sb0 = 0.0f, sb1 = 0.0f;
-        if (i < (size_t)m) {
-            int g = kq;
-            // (sixteen loads in flight, added in the order of the plain loop below: the shares were written by workgroups on
-            // other XCDs, so every one of them is a trip to the Infinity Cache)
-            for (; g + 28 < ngroups; g += 32) {
-                float t[16];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float *q = partH + (size_t)(g + 8 * j) * 2 * mpad + i;
-                    t[4 * j] = q[0]; t[4 * j + 1] = q[mpad]; t[4 * j + 2] = q[8 * mpad]; t[4 * j + 3] = q[9 * mpad];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { sa0 += t[4 * j]; sb0 += t[4 * j + 1]; sa1 += t[4 * j + 2]; sb1 += t[4 * j + 3]; }
-            }
-            for (; g + 4 < ngroups; g += 8) {
-                const float *q = partH + (size_t)g * 2 * mpad + i;
-                sa0 += q[0]; sb0 += q[mpad]; sa1 += q[8 * mpad]; sb1 += q[9 * mpad];
-            }
-            if (g < ngroups) { sa0 += partH[((size_t)g * 2 + 0) * mpad + i]; sb0 += partH[((size_t)g * 2 + 1) * mpad + i]; }
-        }
-        const float sa = sa0 + sa1, sb = sb0 + sb1;
+        float sa, sb;
+        sum_shares(partH, mpad, ngroups, kq, i, i < (size_t)m, sa, sb);
         if (kq > 0) { comb[0][kq - 1][e] = sa; comb[1][kq - 1][e] = sb; }
         __syncthreads();
         if (kq == 0 && i < (size_t)m) {
@@ -564,8 +529,8 @@ __global__ __launch_bounds__(FLAT ? 1024 : BLK) void sw_xm_k(int m, int ngroups,
 
 // Every row in a second-order cone of at most 129 rows (BASELINE configs[2]: 1000 cones of 100): the WHOLE m-tail of a step
 // as one launch, one workgroup per cone (looping when there are more than EG cones) -- sw_xm_k's row: the groups' shares
-// summed by four lanes per row exactly as there, x_y / x_s; then on the workgroup's first wave soc_k's projection of both
-// blocks (cone_soc.rs:38-65; the same lane <-> row mapping and f64 sum of squares) and sw_vm_k's row (v, the sums over m).
+// summed by four lanes per row exactly as there, x_y / x_s; then on the workgroup's first wave the projection of both
+// blocks (cone_soc.rs:38-65; soc_k's lane <-> row mapping and f64 sum of squares, soc_scale in f32) and sw_vm_k's row (v, the sums over m).
 // Lane l of that wave holds rows beg + 1 + l and beg + 65 + l, lane 0 also the cone's first row.  Every per-row value has
 // the arithmetic of the three-launch form; only the block partials of the four sums over m are grouped differently.
 __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__restrict__ begs, const int64_t *__restrict__ ends,
@@ -595,8 +560,6 @@ __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__r
         tau = st->tau_next; rtau = st->r_tau_next;
     }
     const float kappa = st->kappa;
-    const bool conv = tau > eps_zero;
-    const float rt = conv ? 1.0f / tau : 1.0f;
     __shared__ float comb[3][2][3][64];           // [row slot][product][lane quarter - 1][row lane]
     float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
     for (int cone = blockIdx.x; cone < n_cones; cone += gridDim.x) {
@@ -621,39 +584,11 @@ __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__r
                 if (kv) kvv[k] = kv[i];
             }
         }
-        // comp_add with the Kahan term already in a register
-        auto cadd = [](float x, float inc, float *__restrict__ kp, size_t i, float kval) -> float {
-            if (kp == nullptr) return x + inc;
-            const float y = inc - kval;
-            const float t = x + y;
-            kp[i] = (t - x) - y;
-            return t;
-        };
         float sas[3], sbs[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             // the shares of row idx[k]: this thread's quarter of the groups, in sw_xm_k's order
-            float sa0 = 0.0f, sa1 = 0.0f, sb0 = 0.0f, sb1 = 0.0f;
-            if (ok[k]) {
-                const size_t i = idx[k];
-                int g = kq;
-                for (; g + 28 < ngroups; g += 32) {
-                    float t[16];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float *q = partH + (size_t)(g + 8 * j) * 2 * mpad + i;
-                        t[4 * j] = q[0]; t[4 * j + 1] = q[mpad]; t[4 * j + 2] = q[8 * mpad]; t[4 * j + 3] = q[9 * mpad];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { sa0 += t[4 * j]; sb0 += t[4 * j + 1]; sa1 += t[4 * j + 2]; sb1 += t[4 * j + 3]; }
-                }
-                for (; g + 4 < ngroups; g += 8) {
-                    const float *q = partH + (size_t)g * 2 * mpad + i;
-                    sa0 += q[0]; sb0 += q[mpad]; sa1 += q[8 * mpad]; sb1 += q[9 * mpad];
-                }
-                if (g < ngroups) { sa0 += partH[((size_t)g * 2 + 0) * mpad + i]; sb0 += partH[((size_t)g * 2 + 1) * mpad + i]; }
-            }
-            sas[k] = sa0 + sa1; sbs[k] = sb0 + sb1;
+            sum_shares(partH, mpad, ngroups, kq, idx[k], ok[k], sas[k], sbs[k]);
             if (kq > 0) { comb[k][0][kq - 1][e] = sas[k]; comb[k][1][kq - 1][e] = sbs[k]; }
         }
         __syncthreads();
@@ -673,10 +608,10 @@ __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__r
             ny[k] = ns[k] = 0.0f;
             if (!ok[k]) continue;
             const size_t i = idx[k];
-            ny[k] = cadd(oy[k], tyv[k] * (bi[k] * kappa - hNs[k]), ky, i, kyv[k]);
-            ns[k] = cadd(os[k], tsv[k] * vi[k], ks, i, ksv[k]);
+            ny[k] = kahan_add_to(oy[k], inc_xy(tyv[k], bi[k], kappa, hNs[k]), ky != nullptr, kyv[k], ky, i);
+            ns[k] = kahan_add_to(os[k], inc_xs(tsv[k], vi[k]), ks != nullptr, ksv[k], ks, i);
         }
-        // the projection of the x_y block and of the x_s block (soc_k, not rotated)
+        // the projection of the x_y block and of the x_s block (not rotated; the factor in f32)
 #pragma unroll
         for (int which = 0; which < 2; ++which) {
             float *x = which ? ns : ny;
@@ -686,11 +621,9 @@ __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__r
             if (ok[1]) acc += (double)x[1] * (double)x[1];
             const float norm_v = (float)sqrt(wave_sum_d(acc));
             float f, s_new;
-            if (norm_v <= -s0) { f = 0.0f; s_new = 0.0f; }
-            else if (norm_v <= s0) { f = 1.0f; s_new = s0; }
-            else { f = (1.0f + s0 / norm_v) / 2.0f; s_new = (norm_v + s0) / 2.0f; }
+            soc_scale<float>(s0, norm_v, f, s_new);
             x[2] = s_new;
-            if (f != 1.0f) { x[0] = f * x[0]; x[1] = f * x[1]; }
+            if (f != 1.0f) { x[0] = soc_scaled<float>(f, x[0]); x[1] = soc_scaled<float>(f, x[1]); }
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -698,19 +631,17 @@ __global__ __launch_bounds__(BLK) void sw_cone_k(int n_cones, const int64_t *__r
             const size_t i = idx[k];
             xy[i] = ny[k];
             xs[i] = ns[k];
-            const float ry = oy[k] - 2.0f * ny[k], rs = os[k] - 2.0f * ns[k];
+            const float ry = rx_fold(oy[k], ny[k]), rs = rx_fold(os[k], ns[k]);
             rxy[i] = ry;
             rxs[i] = rs;
             const float hx = hxs[k];
-            const float h2 = hPv[k] - 2.0f * hx;
+            const float h2 = rx_fold(hPv[k], hx);
             hP[i] = hx;
-            const float vn = cadd(vi[k], svv[k] * (h2 + rs - bi[k] * rtau), kv, i, kvv[k]);
+            const float vn = kahan_add_to(vi[k], inc_v(svv[k], h2, rs, bi[k], rtau), kv != nullptr, kvv[k], kv, i);
             v[i] = vn;
             q0 = fmaf(bi[k], vn, q0);
             q1 = fmaf(bi[k], ry, q1);
-            float p;
-            if (conv) { p = ns[k] * rt - bi[k]; p = fmaf(rt, hx, p); }
-            else p = ns[k] + hx;
+            const float p = crit_p(tau, eps_zero, ns[k], bi[k], hx);
             q2 = fmaf(p, p, q2);
             q3 = fmaf(bi[k], ny[k], q3);
         }
@@ -775,21 +706,17 @@ __global__ __launch_bounds__(BLK) void sw_vm_k(int m, const float *__restrict__ 
     __shared__ float sh[16];
     if (blockIdx.x == 0 && threadIdx.x == 0) st->kappa_in = st->kappa;      // nobody writes kappa between here and the sweep
     const float rtau = st->r_tau, tau = st->tau;
-    const bool conv = tau > eps_zero;
-    const float rt = conv ? 1.0f / tau : 1.0f;
     float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
     const size_t gstride = (size_t)gridDim.x * BLK;
     for (size_t i = blockIdx.x * (size_t)BLK + threadIdx.x; i < (size_t)m; i += gstride) {
         const float nw = h3[i], bi = b[i];
-        const float h2 = hP[i] - 2.0f * nw;
+        const float h2 = rx_fold(hP[i], nw);
         hP[i] = nw;
-        const float vn = comp_add(v[i], Sv[i] * (h2 + rxs[i] - bi * rtau), kv, i);
+        const float vn = comp_add(v[i], inc_v(Sv[i], h2, rxs[i], bi, rtau), kv, i);
         v[i] = vn;
         q0 = fmaf(bi, vn, q0);
         q1 = fmaf(bi, rxy[i], q1);
-        float p;
-        if (conv) { p = xs[i] * rt - bi; p = fmaf(rt, nw, p); }
-        else p = xs[i] + nw;
+        const float p = crit_p(tau, eps_zero, xs[i], bi, nw);
         q2 = fmaf(p, p, q2);
         q3 = fmaf(bi, xy[i], q3);
     }
