@@ -112,6 +112,54 @@ int thip_test_gemv_multi(size_t m, size_t n, const float *mat, int nv, const flo
                          float *const *host_out_n, float *const *host_out_t, const int *host_stopped, int nj, int target_blocks,
                          int reps, float *host_ms);
 
+/* The plan one launch of the single-vector dual GEMV ran (or would run) under: rows per load (4: f32, 8: 16-bit, 1: the unaligned
+ * fallback), row groups per lane, columns per unrolled step, the grid (row tiles x column chunks), columns per chunk, and the form
+ * of the partial last row tile: m_load > 0 = unguarded whole-vector loads of rows below m_load, 0 = the per-lane guarded form.  A call
+ * split at a column reports the chunk rows and chunk widths of the two launches (chunks / chunks2, cols_per_chunk / cols_per_chunk2). */
+typedef struct thip_gemv_plan_rec {
+    int32_t vw, nj, ku, tiles, chunks, cols_per_chunk, m_load;
+    int32_t chunks2, cols_per_chunk2, reserved;
+} thip_gemv_plan_rec;
+
+#define THIP_TEST_E_GUARD 10901   /* thip_test_dual_gemv: a word behind the partial-sum scratch changed */
+
+/* test entry point of the single-vector dual GEMV (thip_gemv.hip; tests/test_gpu_gemv_tilings.py): ONE pinned instance of the kernel
+ * alone, its partial sums finished into out_n = A xn (m floats) and / or out_t = A^T xt (n floats), all on the device.
+ *   mat, lda, kind, inv_scale, pad_zero: the stored matrix exactly as it lies in device memory -- column-major, lda >= m in elements
+ *     of `kind` (THIP_A_F32 / THIP_A_BF16 / THIP_A_F16; F16 with its n per-column 1 / scale); pad_zero != 0 promises that the rows
+ *     m .. lda - 1 are zeros (the library's own copies), which lets a partial last row tile load whole vectors;
+ *   do_n / do_t: the products to compute (both: from one read of A); abs_mode: |A| times ones (xn / xt not read);
+ *   nj, target_blocks >= 0: the tiling hint, any values (0 / 0: none -- the shape heuristic);
+ *   col_split: 0 = one launch over all columns; else a multiple of 8 below n: two launches over [0, c) and [c, n) that fill consecutive
+ *     chunk rows of the partial sums, as the column-split pipeline of the solver issues them;
+ *   stopped != 0: the device stop flag is set -- the kernels and the second stage return at once, the outputs stay as given.
+ * The partial sums go to a scratch of the solver's own size filled with NaNs beforehand (a sum that is consumed but was never written
+ * shows in the result) with a guard tail behind it: THIP_TEST_E_GUARD when the tail changed.  THIP_E_INVALID, nothing launched: lda < m,
+ * a null vector a product needs, f16 without scales, a bad col_split.  *host_plan (may be NULL): the plan that ran. */
+typedef struct thip_gemv_test {
+    size_t m, n, lda;
+    const void *mat;
+    const float *inv_scale;
+    int32_t kind, pad_zero;
+    const float *xn, *xt;
+    float *out_n, *out_t;
+    int32_t do_n, do_t, abs_mode, nj, target_blocks, stopped;
+    size_t col_split;
+} thip_gemv_test;
+int thip_test_dual_gemv(const thip_gemv_test *t, thip_gemv_plan_rec *host_plan);
+
+/* the same planning with nothing launched (needs no GPU and no thip_init): the plan of one launch over the columns [col0, col1) of an
+ * m x n matrix read vw = 4, 8 or 1 rows per load under the hint (nj, target_blocks), the floats dual_gemv_scratch_floats(m, n) reserves
+ * for any plan's partial sums (a solver allocates twice that), and the column at which the solver's column-split pipeline splits n
+ * columns (0: it does not).  m_load is that of a matrix whose rows below m are not known to be zeros. */
+int thip_test_gemv_plan(size_t m, size_t n, int vw, int nj, int target_blocks, size_t col0, size_t col1,
+                        thip_gemv_plan_rec *host_plan, size_t *host_scratch_floats, size_t *host_split_col);
+
+/* TEST HOOK: pins the tiling of the dual GEMV for the stored form of A and the launch form (one launch per pass, or the column-split
+ * pipeline) the next thip_solver_run will use to the candidate_index-th of the plans the autotune times, as if the autotune had picked
+ * it; -1: back to the shape heuristic.  After thip_solver_init, before the first run.  THIP_E_INVALID: an index out of range. */
+int thip_test_solver_pin_gemv_plan(thip_solver *s, int candidate_index);
+
 /* TEST HOOK: the workgroup size of a small batch (thip_smallbatch.hip): 64, 256 or 1024 threads, 0 = by shape.  Before
  * thip_smallbatch_init. */
 int thip_test_smallbatch_force_threads(thip_smallbatch *h, int threads);

@@ -78,6 +78,25 @@ pub struct thip_sweep_test {
     pub host_sums: *mut f32,
 }
 
+#[repr(C)]
+pub struct thip_gemv_plan_rec {
+    pub vw: i32, pub nj: i32, pub ku: i32, pub tiles: i32, pub chunks: i32, pub cols_per_chunk: i32, pub m_load: i32,
+    pub chunks2: i32, pub cols_per_chunk2: i32, pub reserved: i32,
+}
+pub const THIP_TEST_E_GUARD: c_int = 10901;
+
+#[repr(C)]
+pub struct thip_gemv_test {
+    pub m: usize, pub n: usize, pub lda: usize,
+    pub mat: *const c_void,
+    pub inv_scale: *const f32,
+    pub kind: i32, pub pad_zero: i32,
+    pub xn: *const f32, pub xt: *const f32,
+    pub out_n: *mut f32, pub out_t: *mut f32,
+    pub do_n: i32, pub do_t: i32, pub abs_mode: i32, pub nj: i32, pub target_blocks: i32, pub stopped: i32,
+    pub col_split: usize,
+}
+
 pub enum thip_solver {}
 pub enum thip_batch {}
 pub enum thip_smallbatch {}
@@ -345,6 +364,10 @@ extern "C" {
     pub fn thip_test_gemv_multi(m: usize, n: usize, mat: *const f32, nv: c_int, host_xn: *const *const f32, host_xt: *const *const f32,
                                 host_out_n: *const *mut f32, host_out_t: *const *mut f32, host_stopped: *const c_int, nj: c_int,
                                 target_blocks: c_int, reps: c_int, host_ms: *mut f32) -> c_int;
+    pub fn thip_test_dual_gemv(t: *const thip_gemv_test, host_plan: *mut thip_gemv_plan_rec) -> c_int;
+    pub fn thip_test_gemv_plan(m: usize, n: usize, vw: c_int, nj: c_int, target_blocks: c_int, col0: usize, col1: usize,
+                               host_plan: *mut thip_gemv_plan_rec, host_scratch_floats: *mut usize, host_split_col: *mut usize) -> c_int;
+    pub fn thip_test_solver_pin_gemv_plan(s: *mut thip_solver, candidate_index: c_int) -> c_int;
     pub fn thip_test_spin_allreduce(s: *mut thip_solver, latency_us: c_int) -> c_int;
     pub fn thip_test_sweep(t: *const thip_sweep_test, host_ms: *mut f32, host_info: *mut c_int) -> c_int;
     pub fn thip_test_solver_kahan(s: *mut thip_solver, host_kx: *mut f32, host_ky: *mut f32, host_ks: *mut f32, host_ku: *mut f32,

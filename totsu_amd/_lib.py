@@ -77,6 +77,19 @@ class SdpBatchInfo(C.Structure):
     _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
 
 
+class GemvPlanRec(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("vw", "nj", "ku", "tiles", "chunks", "cols_per_chunk", "m_load", "chunks2",
+                                         "cols_per_chunk2", "reserved")]
+
+
+class GemvTest(C.Structure):
+    _fields_ = [("m", C.c_size_t), ("n", C.c_size_t), ("lda", C.c_size_t), ("mat", C.c_void_p), ("inv_scale", C.c_void_p),
+                ("kind", C.c_int32), ("pad_zero", C.c_int32), ("xn", C.c_void_p), ("xt", C.c_void_p), ("out_n", C.c_void_p),
+                ("out_t", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("do_n", "do_t", "abs_mode", "nj", "target_blocks", "stopped")] + [("col_split", C.c_size_t)]
+
+
+TEST_E_GUARD = 10901
 BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
 SMALLBATCH_MAX_DIM, SMALLBATCH_MAX_AREA, SMALLBATCH_MAX_PROB, SMALLBATCH_LDS_MAX = 1024, 24576, 1048576, 163840
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -227,6 +240,9 @@ PROTOTYPES = {
     "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
     "thip_test_sdpbatch_project": (_i, [_i, _i, _vp, _vp]),
+    "thip_test_dual_gemv": (_i, [C.POINTER(GemvTest), C.POINTER(GemvPlanRec)]),
+    "thip_test_gemv_plan": (_i, [_sz, _sz, _i, _i, _i, _sz, _sz, C.POINTER(GemvPlanRec), C.POINTER(_sz), C.POINTER(_sz)]),
+    "thip_test_solver_pin_gemv_plan": (_i, [_vp, _i]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "thip_prof_read_psd": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

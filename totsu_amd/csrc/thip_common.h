@@ -228,6 +228,7 @@ int dual_gemv_chunk_rows(size_t n_row, size_t cols, const DenseA &A, const GemvH
 int dual_gemv_partials_geometry(size_t n_row, size_t n_col, const DenseA &A, bool do_n, bool do_t,
                                 float *scratch_base, GemvPartials *out);
 size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col);
+size_t gemv_split_column(size_t n_col);               // where the column-split pipeline splits a pass (0: it does not)
 // y[i] = alpha * sum_k part[k*stride + i] + beta * y[i]
 int finalize_partials(hipStream_t st, size_t n, const float *part, int np, size_t stride, float alpha, float beta,
                       float *y, const int *stop);

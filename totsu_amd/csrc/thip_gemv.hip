@@ -602,6 +602,25 @@ static void clamp_rows(Plan &p, size_t n_row, const DenseA &A)
     if (clamp_on && p.vw > 1 && (n_row % p.vw == 0 || (A.pad_zero && A.lda >= m_up))) p.m_load = (int)m_up;
 }
 
+// the tiling of ONE launch over `cols` columns of an (n_row x n_col) matrix read `vw` rows per load: the chunking of the range's
+// own shape, the strides of the whole matrix, the form of the partial last row tile.  Every launch and every test hook plans here
+static Plan range_plan(size_t n_row, size_t n_col, size_t cols, int vw, const GemvHint *hint, const DenseA &A)
+{
+    Plan p = make_plan(n_row, cols, vw, hint);
+    p.strideN = round_up(n_row, 4);
+    p.strideT = round_up(n_col, 4);
+    clamp_rows(p, n_row, A);
+    return p;
+}
+
+// the column at which overlap modes 2 / 3 split a pass over an n-column matrix (thip_solver_passes.inc): a function of n alone, a
+// multiple of 8 floats (every buffer offset stays 32-byte aligned); 0: too few columns to split
+size_t gemv_split_column(size_t n_col)
+{
+    if (n_col < 16) return 0;
+    return (n_col / 2) & ~(size_t)7;
+}
+
 size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col)
 {
     size_t best = 0;
@@ -610,9 +629,17 @@ size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col)
     static const int vws[3] = { 4, 1, 8 };
     for (int i = -1; i < nc; ++i)
         for (int v = 0; v < 3; ++v) {
-            const Plan p = make_plan(n_row, n_col, vws[v], i < 0 ? nullptr : &c[i]);
+            const GemvHint *h = i < 0 ? nullptr : &c[i];
+            const Plan p = make_plan(n_row, n_col, vws[v], h);
             const size_t f = (size_t)p.chunks * p.strideN + (size_t)p.tiles * p.strideT;
             if (f > best) best = f;
+            // the column-split form lives in TWICE this many floats (ensure_gemv_scratch): its two half-launches chunk their own
+            // columns, and a half may fall under the 64 MB mark that halves the least chunk width -- up to twice the chunk rows + 1
+            const size_t c1 = gemv_split_column(n_col);
+            if (c1 == 0) continue;
+            const size_t rows = (size_t)make_plan(n_row, c1, vws[v], h).chunks + (size_t)make_plan(n_row, n_col - c1, vws[v], h).chunks;
+            const size_t fs = (rows * p.strideN + (size_t)p.tiles * p.strideT + 1) / 2;
+            if (fs > best) best = fs;
         }
     return best + 64;
 }
@@ -623,11 +650,12 @@ size_t dual_gemv_scratch_floats(size_t n_row, size_t n_col)
 // them all), T partials into columns col0 .. col1 of every tile row.  max_chunk_rows = the chunk rows partN has room for (< 0:
 // this launch's own: the whole matrix in one launch); *chunks_used = chunk rows this launch filled.  `out` describes the layout
 // (nN = chunk_row0 + *chunks_used).  col0 only needs the alignment of the vector loads (a multiple of 4 floats; 8 for 16-bit storage).
-int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
-                            const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
-                            float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
-                            const GemvHint *hint, size_t col0, size_t col1, int chunk_row0, int max_chunk_rows,
-                            int *chunks_used)
+// (*ran, when given: the plan the launch ran under -- the test hooks report it)
+static int partials_cols(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
+                         const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
+                         float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
+                         const GemvHint *hint, size_t col0, size_t col1, int chunk_row0, int max_chunk_rows,
+                         int *chunks_used, Plan *ran)
 {
     if (chunks_used) *chunks_used = 0;
     *out = GemvPartials{};
@@ -641,10 +669,8 @@ int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const De
     R.mat = (const char *)A.mat + col0 * lda * A.elem_bytes();
     const char *base = (const char *)R.mat;
     // tiling of the range's own shape (its columns decide the chunking); strides are those of the whole matrix
-    Plan p = make_plan(n_row, col1 - col0, A.vec_ok() ? R.vec_width() : 1, hint);
-    p.strideN = round_up(n_row, 4);
-    p.strideT = round_up(n_col, 4);
-    clamp_rows(p, n_row, A);
+    const Plan p = range_plan(n_row, n_col, col1 - col0, A.vec_ok() ? R.vec_width() : 1, hint, A);
+    if (ran) *ran = p;
     if (max_chunk_rows < 0) max_chunk_rows = chunk_row0 + p.chunks;
     if (chunk_row0 + p.chunks > max_chunk_rows) return fail(THIP_E_WORK, "gemv scratch: too many chunk rows", __FILE__, __LINE__);
     const size_t needN = do_n ? (size_t)max_chunk_rows * p.strideN : 0;
@@ -664,6 +690,16 @@ int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const De
     else      launch_any(p, st, (const float *)base, lda, m, n, xnr, xt, do_n, do_t, abs_mode, pn, pt, stop_flag);
     THIP_LAUNCH_CHECK();
     return 0;
+}
+
+int dual_gemv_partials_cols(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
+                            const float *xn, const float *xt, bool do_n, bool do_t, bool abs_mode,
+                            float *scratch_base, size_t scratch_floats, GemvPartials *out, const int *stop_flag,
+                            const GemvHint *hint, size_t col0, size_t col1, int chunk_row0, int max_chunk_rows,
+                            int *chunks_used)
+{
+    return partials_cols(st, n_row, n_col, A, xn, xt, do_n, do_t, abs_mode, scratch_base, scratch_floats, out, stop_flag, hint,
+                         col0, col1, chunk_row0, max_chunk_rows, chunks_used, nullptr);
 }
 
 int dual_gemv_partials(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A,
@@ -839,6 +875,95 @@ int thip_absadd_sympack(size_t n, const float *mat, float *y)
     hipLaunchKernelGGL(sp_absadd_k, dim3((unsigned)((n + 3) / 4)), dim3(BLK), 0, ctx().stream, (int)n, mat, y);
     THIP_LAUNCH_CHECK();
     return 0;
+}
+
+
+// ---- TEST HOOKS (totsu_f32hip_test.h): one pinned instance of dual_gemv_k alone, and its planning without a launch ----------
+
+static void plan_record(const Plan &p, thip_gemv_plan_rec *r)
+{
+    r->vw = p.vw; r->nj = p.nj; r->ku = p.ku; r->tiles = p.tiles; r->chunks = p.chunks; r->cols_per_chunk = p.cols_per_chunk;
+    r->m_load = p.m_load; r->chunks2 = 0; r->cols_per_chunk2 = 0; r->reserved = 0;
+}
+
+int thip_test_gemv_plan(size_t m, size_t n, int vw, int nj, int target_blocks, size_t col0, size_t col1,
+                        thip_gemv_plan_rec *host_plan, size_t *host_scratch_floats, size_t *host_split_col)
+{
+    if (m == 0 || n == 0 || m > 0x7fffffffull || n > 0x7fffffffull || col1 > n || col1 <= col0 || nj < 0 || target_blocks < 0
+        || !(vw == 1 || vw == 4 || vw == 8))
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    // a matrix of that vector width with a pitch of its own and unknown rows below m: the last row tile is unguarded when m % vw == 0
+    const DenseA shape{ nullptr, round_up(m, 16), vw == 8 ? THIP_A_BF16 : THIP_A_F32, nullptr, false };
+    const GemvHint hint{ nj, target_blocks };
+    const Plan p = range_plan(m, n, col1 - col0, vw, (nj > 0 || target_blocks > 0) ? &hint : nullptr, shape);
+    if (host_plan) plan_record(p, host_plan);
+    if (host_scratch_floats) *host_scratch_floats = dual_gemv_scratch_floats(m, n);
+    if (host_split_col) *host_split_col = gemv_split_column(n);
+    return 0;
+}
+
+int thip_test_dual_gemv(const thip_gemv_test *t, thip_gemv_plan_rec *host_plan)
+{
+    THIP_NEED_INIT();
+    if (!t || !t->mat || t->m == 0 || t->n == 0 || t->lda < t->m || t->nj < 0 || t->target_blocks < 0 || (!t->do_n && !t->do_t)
+        || (t->do_n && (!t->out_n || (!t->abs_mode && !t->xn))) || (t->do_t && (!t->out_t || (!t->abs_mode && !t->xt)))
+        || !(t->kind == THIP_A_F32 || t->kind == THIP_A_BF16 || t->kind == THIP_A_F16) || (t->kind == THIP_A_F16 && !t->inv_scale)
+        || (t->col_split != 0 && (t->col_split % 8 != 0 || t->col_split >= t->n)))
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    constexpr size_t GUARD = 256;
+    constexpr unsigned NAN_WORD = 0x7fc00abcu, GUARD_WORD = 0x5a5a5a5au;
+    hipStream_t st = ctx().stream;
+    const size_t m = t->m, n = t->n;
+    const DenseA A{ t->mat, t->lda, t->kind, t->kind == THIP_A_F16 ? t->inv_scale : nullptr, t->pad_zero != 0 };
+    const bool do_n = t->do_n != 0, do_t = t->do_t != 0, abs_mode = t->abs_mode != 0;
+    // the solver's own allocation (ensure_gemv_scratch), every word a NaN -- a partial sum that is consumed but was never written
+    // shows in the result -- and a guard tail behind it
+    const size_t work = 2 * dual_gemv_scratch_floats(m, n);
+    float *scr = nullptr;
+    int *flag = nullptr;
+    thip_gemv_plan_rec rec{};
+    int rc = 0;
+    // (one exit: everything allocated here is released whatever fails)
+    auto body = [&]() -> int {
+        THIP_TRY(hipMalloc((void **)&scr, (work + GUARD) * sizeof(float)));
+        THIP_TRY(hipMalloc((void **)&flag, sizeof(int)));
+        THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)scr, (int)NAN_WORD, work, st));
+        THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(scr + work), (int)GUARD_WORD, GUARD, st));
+        THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flag, t->stopped ? 1 : 0, 1, st));
+        const GemvHint hint{ t->nj, t->target_blocks };
+        const GemvHint *h = (t->nj > 0 || t->target_blocks > 0) ? &hint : nullptr;
+        GemvPartials gp;
+        Plan p;
+        if (t->col_split == 0) {
+            THIP_RC(partials_cols(st, m, n, A, t->xn, t->xt, do_n, do_t, abs_mode, scr, work, &gp, flag, h, 0, n, 0, -1, nullptr, &p));
+            plan_record(p, &rec);
+        } else {
+            // two launches over [0, c) and [c, n) filling consecutive chunk rows, as products_cols issues them
+            const size_t c = t->col_split;
+            const int rows1 = dual_gemv_chunk_rows(m, c, A, h, nullptr), rows2 = dual_gemv_chunk_rows(m, n - c, A, h, nullptr);
+            int used1 = 0, used2 = 0;
+            Plan p2;
+            THIP_RC(partials_cols(st, m, n, A, t->xn, t->xt, do_n, do_t, abs_mode, scr, work, &gp, flag, h, 0, c, 0, rows1 + rows2, &used1, &p));
+            THIP_RC(partials_cols(st, m, n, A, t->xn, t->xt, do_n, do_t, abs_mode, scr, work, &gp, flag, h, c, n, rows1, rows1 + rows2, &used2, &p2));
+            plan_record(p, &rec);
+            rec.chunks = used1; rec.chunks2 = used2; rec.cols_per_chunk2 = p2.cols_per_chunk;
+            if (p2.vw != p.vw || p2.nj != p.nj || p2.tiles != p.tiles || p2.m_load != p.m_load || used1 != rows1 || used2 != rows2)
+                return fail(THIP_E_INVALID, "the two column ranges were planned differently", __FILE__, __LINE__);
+        }
+        if (do_n) THIP_RC(finalize_partials(st, m, gp.partN, gp.nN, gp.strideN, 1.0f, 0.0f, t->out_n, flag));
+        if (do_t) THIP_RC(finalize_partials(st, n, gp.partT, gp.nT, gp.strideT, 1.0f, 0.0f, t->out_t, flag));
+        unsigned tail[GUARD];
+        THIP_TRY(hipMemcpyAsync(tail, scr + work, sizeof(tail), hipMemcpyDeviceToHost, st));
+        THIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < GUARD; ++i)
+            if (tail[i] != GUARD_WORD) return fail(THIP_TEST_E_GUARD, "a launch wrote behind the gemv scratch", __FILE__, __LINE__);
+        return 0;
+    };
+    rc = body();
+    if (rc != 0) hipStreamSynchronize(st);
+    hipFree(scr); hipFree(flag);
+    if (host_plan) *host_plan = rec;
+    return rc;
 }
 
 }  // extern "C"

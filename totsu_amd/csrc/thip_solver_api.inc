@@ -669,6 +669,20 @@ int thip_solver_gemv_plan(const thip_solver *s, int *host_nj, int *host_blocks, 
     return 0;
 }
 
+// TEST HOOK (totsu_f32hip_test.h): a candidate tiling installed the way the autotune installs its pick
+int thip_test_solver_pin_gemv_plan(thip_solver *s, int candidate_index)
+{
+    THIP_NEED_INIT();
+    int nc = 0;
+    const GemvHint *c = gemv_candidates(&nc);
+    if (!s || !s->inited || candidate_index < -1 || candidate_index >= nc)
+        return fail(THIP_E_INVALID, "null or uninitialised solver, or no such candidate plan", __FILE__, __LINE__);
+    THIP_RC(prepare_split(s));                   // the launch form of the next run (and its own tuning, where that is due)
+    if (candidate_index < 0) s->plan[s->sa.in_use().is16()][s->split_plan] = GemvPlan{};
+    else set_gemv_plan(s, s->split_plan, c[candidate_index], 0.0f);
+    return prepare_split(s);                     // the chunk rows of the split form under the plan now in use
+}
+
 int thip_solver_sweep_plan(thip_solver *s, int *host_members, int *host_cols_per_panel, int *host_slots, float *host_ms)
 {
     THIP_NEED_INIT();

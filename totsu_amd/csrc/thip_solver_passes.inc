@@ -302,8 +302,8 @@ int one_iteration(thip_solver *s)
 // rank's own tuned plan.  A multiple of 8 floats keeps every buffer offset 32-byte aligned.
 size_t split_column(const thip_solver *s)
 {
-    if (s->op != A_DENSE || s->m == 0 || s->n < 16) return 0;
-    return (s->n / 2) & ~(size_t)7;
+    if (s->op != A_DENSE || s->m == 0) return 0;
+    return gemv_split_column(s->n);
 }
 
 bool split_active(const thip_solver *s)
@@ -312,6 +312,13 @@ bool split_active(const thip_solver *s)
 }
 
 int autotune_gemv(thip_solver *s);
+
+// THE place a tiling is installed for the stored form in use and a launch form (split: the column-split pipeline): the autotune's
+// pick, or a test's pin (thip_test_solver_pin_gemv_plan)
+void set_gemv_plan(thip_solver *s, bool split, GemvHint hint, float ms)
+{
+    s->plan[s->sa.in_use().is16()][split] = GemvPlan{ hint, true, ms };
+}
 
 // decides the form of the next run: column-split (its own tuned plan, its split column) or one launch per pass
 int prepare_split(thip_solver *s)
@@ -525,7 +532,7 @@ int autotune_gemv(thip_solver *s)
         }
         if (ms < best) { best = ms; pick = c[i]; }
     }
-    plan = GemvPlan{ pick, true, best };
+    set_gemv_plan(s, sp, pick, best);
     THIP_TRY(hipEventDestroy(e0));
     THIP_TRY(hipEventDestroy(e1));
     return 0;

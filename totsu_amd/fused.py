@@ -324,6 +324,11 @@ class FusedSolver:
         lib.thip_solver_gemv_plan(self.h, C.byref(nj), C.byref(bl), C.byref(ms))
         return {"rows_groups_per_lane": nj.value, "target_workgroups": bl.value, "autotune_ms": ms.value}
 
+    def pin_gemv_plan(self, candidate_index):
+        """TEST HOOK (thip_test_solver_pin_gemv_plan): the dual GEMV's tiling for the stored form and launch form the next run uses
+        becomes the candidate_index-th plan the autotune times (-1: the shape heuristic again); before the first run"""
+        lib.thip_test_solver_pin_gemv_plan(self.h, int(candidate_index))
+
     def schedule_in_use(self):
         """the schedule the next run executes: "sweep" falls back to "carried" when the one-pass kernel cannot take the
         problem (thip_solver_schedule_in_use)"""
