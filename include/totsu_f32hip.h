@@ -677,6 +677,64 @@ int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const
 int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
+/* ---------------------------------------------------------------------------------------------
+ * The RAGGED batch: many conic programs, each with its own dense f32 A, its own n_p, m_p and its own cone layout, in one batch
+ * (thip_raggedbatch.hip).  The iteration is thip_sdpbatch's on every problem -- one workgroup per running problem,
+ * its vectors in LDS, its A streamed twice per iteration, its PSD cones projected on chip --, and a problem's iterates are, bit for
+ * bit, those of a thip_midbatch / thip_sdpbatch that holds it alone.  A problem is taken exactly when thip_sdpbatch_fits takes it.
+ * The arrays: one device array per kind (A, b, c, the row sums) and, per problem, its offset into it IN FLOATS (host_at_*), so the
+ * caller decides where every A lies: an A whose address is a multiple of 16 bytes and whose m_p is a multiple of 4 is read with
+ * 16-byte loads, every other one with 4-byte loads of the same entries.  Problem p's A is column-major, lda = m_p.  The cone
+ * segments are concatenated problem after problem; host_n_seg[p] says how many belong to problem p.  host_at_rowabs[p] == -1 (or a
+ * NULL array): problem p carries no row sums and uses |b|.
+ * A launch has one workgroup size and one LDS size: the problems are split by shape into a 256-thread and a 1024-thread class
+ * (m_p n_p <= 8192: 256), each with the largest LDS map of its members, and every poll makes one launch per class that has a
+ * running problem, the longest problems (m_p n_p) first.  Problems take 6 n_p + 10 m_p floats of the arena each, packed; identical
+ * layouts (m, segments) share one cone table.  1 <= n_prob <= 1 048 576.  Everything else is THIP_E_INVALID before anything is
+ * allocated, and the message names the first problem refused.
+ * Lengths are the problem's own: solution(i) writes n_i and m_i floats, iterate(i) n_i + 2 m_i + 1 and n_i + m_i + 1, precond(i)
+ * the same.  replace(i, ...) hands slot i new data of ITS shape and layout: the init kernel on that slot.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_raggedbatch thip_raggedbatch;
+typedef struct thip_raggedbatch_class_t {
+    int32_t n_prob, live;             /* members; members RUNNING as of the last poll */
+    int32_t threads, lds_bytes;       /* of every workgroup of the class: 256 or 1024; the largest map of its members */
+    int64_t launches, workgroups;     /* issued by run / run_until_any since thip_raggedbatch_init */
+} thip_raggedbatch_class_t;
+typedef struct thip_raggedbatch_info_t {
+    int32_t n_prob, live;
+    int32_t n_layouts, n_load16;      /* distinct (m, segments) tables; problems whose A is read with 16-byte loads */
+    size_t  arena_bytes;              /* the problems' state, packed: 4 sum (6 n_p + 10 m_p) */
+    size_t  device_bytes;             /* everything this object allocated on the device */
+    size_t  device_bytes_all;         /* the same, summed over every thip_raggedbatch alive in the process */
+    int64_t launches, workgroups;     /* summed over the classes */
+    size_t  a_bytes_per_iter;         /* bytes of A read when every problem advances one iteration: sum 2 m_p n_p 4 */
+    thip_raggedbatch_class_t cls[2];  /* the 256-thread class, the 1024-thread class */
+} thip_raggedbatch_info_t;
+/* the shape rules alone (needs no device): 0, or THIP_E_INVALID with the index of the first problem refused in *host_first_refused
+ * (-1: the refusal names no problem).  host_lds_bytes / host_threads: n_prob entries, what one workgroup of the problem alone
+ * would take; either may be NULL */
+int thip_raggedbatch_fits(size_t n_prob, const size_t *host_n, const size_t *host_m, const size_t *host_n_seg,
+                          const int32_t *host_seg_type, const int64_t *host_seg_len, int *host_first_refused,
+                          size_t *host_lds_bytes, int *host_threads);
+int thip_raggedbatch_create(size_t n_prob, const size_t *host_n, const size_t *host_m, const float *dev_a, const int64_t *host_at_a,
+                            const float *dev_b, const int64_t *host_at_b, const float *dev_c, const int64_t *host_at_c,
+                            const float *dev_b_rowabs, const int64_t *host_at_rowabs, const size_t *host_n_seg,
+                            const int32_t *host_seg_type, const int64_t *host_seg_len, const thip_param *par,
+                            thip_raggedbatch **out);
+int thip_raggedbatch_set_param(thip_raggedbatch *h, const thip_param *par);
+int thip_raggedbatch_init(thip_raggedbatch *h);
+int thip_raggedbatch_run(thip_raggedbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_raggedbatch_run_until_any(thip_raggedbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_raggedbatch_status(thip_raggedbatch *h, int i, thip_status *host_status);
+int thip_raggedbatch_solution(thip_raggedbatch *h, int i, float *host_x, float *host_y);
+int thip_raggedbatch_iterate(thip_raggedbatch *h, int i, float *host_x, float *host_y);
+int thip_raggedbatch_precond(thip_raggedbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                             const float *dev_vec_b_rowabs);
+int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
+int thip_raggedbatch_destroy(thip_raggedbatch *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

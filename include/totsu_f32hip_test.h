@@ -177,6 +177,19 @@ int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads);
  * dev_rx_or_null != NULL: rx <- rx - 2 x of the same layout rides in the pack. */
 int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_rx_or_null);
 
+/* TEST HOOK: the workgroup size of a ragged batch (thip_raggedbatch.hip): 256 or 1024 threads put every problem in that one
+ * class, 0 = by shape.  Before thip_raggedbatch_init. */
+int thip_test_raggedbatch_force_threads(thip_raggedbatch *h, int threads);
+
+/* TEST HOOK: the launch plan thip_raggedbatch_create would make (needs no device), for the arrays of thip_raggedbatch_fits and a
+ * forced workgroup size (0: by shape).  host_class[p]: 0 (256 threads) or 1 (1024); host_order: the 256-thread class's members
+ * in the order of its live list, then the 1024-thread class's; host_layout[p]: the index of problem p's cone table;
+ * host_arena_at[p]: where its state starts in the arena, in floats -- n_prob entries each, any may be NULL.  host_info: the
+ * counts, the classes' thread counts and LDS bytes, n_layouts, arena_bytes and a_bytes_per_iter (NULL: not wanted). */
+int thip_test_raggedbatch_plan(size_t n_prob, const size_t *host_n, const size_t *host_m, const size_t *host_n_seg,
+                               const int32_t *host_seg_type, const int64_t *host_seg_len, int force_threads, int *host_class,
+                               int *host_order, int *host_layout, int64_t *host_arena_at, thip_raggedbatch_info_t *host_info);
+
 #ifdef __cplusplus
 }
 #endif

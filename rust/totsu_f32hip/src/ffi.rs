@@ -62,6 +62,21 @@ pub struct thip_sdpbatch_info_t {
     pub max_psd_order: i32, pub n_psd: i32,
     pub psd_lds_bytes: usize,
 }
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_raggedbatch_class_t {
+    pub n_prob: i32, pub live: i32, pub threads: i32, pub lds_bytes: i32,
+    pub launches: i64, pub workgroups: i64,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_raggedbatch_info_t {
+    pub n_prob: i32, pub live: i32, pub n_layouts: i32, pub n_load16: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub a_bytes_per_iter: usize,
+    pub cls: [thip_raggedbatch_class_t; 2],
+}
 pub const THIP_BATCH_MAX: c_int = 64;
 pub const THIP_BATCH_GROUP_DEFAULT: c_int = 8;
 
@@ -102,6 +117,7 @@ pub enum thip_batch {}
 pub enum thip_smallbatch {}
 pub enum thip_midbatch {}
 pub enum thip_sdpbatch {}
+pub enum thip_raggedbatch {}
 pub enum thip_sptile {}
 pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
@@ -330,6 +346,34 @@ extern "C" {
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
     pub fn thip_test_sdpbatch_project(k: c_int, count: c_int, dev_packed: *mut f32, dev_rx_or_null: *mut f32) -> c_int;
+
+    // problems of different shapes and cone layouts in one batch: the SDP batch's iteration on a problem the workgroup looks up
+    // (thip_raggedbatch.hip)
+    pub fn thip_raggedbatch_fits(n_prob: usize, host_n: *const usize, host_m: *const usize, host_n_seg: *const usize,
+                                 host_seg_type: *const i32, host_seg_len: *const i64, host_first_refused: *mut c_int,
+                                 host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;
+    pub fn thip_raggedbatch_create(n_prob: usize, host_n: *const usize, host_m: *const usize, dev_a: *const f32,
+                                   host_at_a: *const i64, dev_b: *const f32, host_at_b: *const i64, dev_c: *const f32,
+                                   host_at_c: *const i64, dev_b_rowabs: *const f32, host_at_rowabs: *const i64,
+                                   host_n_seg: *const usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                                   par: *const thip_param, out: *mut *mut thip_raggedbatch) -> c_int;
+    pub fn thip_raggedbatch_set_param(h: *mut thip_raggedbatch, par: *const thip_param) -> c_int;
+    pub fn thip_raggedbatch_init(h: *mut thip_raggedbatch) -> c_int;
+    pub fn thip_raggedbatch_run(h: *mut thip_raggedbatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedbatch_run_until_any(h: *mut thip_raggedbatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedbatch_status(h: *mut thip_raggedbatch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedbatch_solution(h: *mut thip_raggedbatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_raggedbatch_iterate(h: *mut thip_raggedbatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_raggedbatch_precond(h: *mut thip_raggedbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_raggedbatch_replace(h: *mut thip_raggedbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
+                                    dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_raggedbatch_info(h: *const thip_raggedbatch, host_info: *mut thip_raggedbatch_info_t) -> c_int;
+    pub fn thip_raggedbatch_destroy(h: *mut thip_raggedbatch) -> c_int;
+    pub fn thip_test_raggedbatch_force_threads(h: *mut thip_raggedbatch, threads: c_int) -> c_int;
+    pub fn thip_test_raggedbatch_plan(n_prob: usize, host_n: *const usize, host_m: *const usize, host_n_seg: *const usize,
+                                      host_seg_type: *const i32, host_seg_len: *const i64, force_threads: c_int,
+                                      host_class: *mut c_int, host_order: *mut c_int, host_layout: *mut c_int,
+                                      host_arena_at: *mut i64, host_info: *mut thip_raggedbatch_info_t) -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

@@ -30,7 +30,12 @@ by the workgroup itself (f32 MFMAs on operands in LDS), with up to 1024 threads:
 
     sdpbatch_k, sdpbatch_init_k (and the test hook's sdpbatch_project_k): no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
 
-usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch]"""
+The ragged batch (thip_raggedbatch.hip, --family raggedbatch) is the SDP batch's iteration on a problem of its own shape and cone
+layout that the workgroup looks up in a table:
+
+    raggedbatch_k and raggedbatch_init_k: the SDP batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
+
+usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch]"""
 import re
 import sys
 
@@ -90,6 +95,7 @@ OWNBATCH = {
     "smallbatch": (r"smallbatch(_init)?_k", ("smallbatch_k", "smallbatch_init_k"), None, "on-chip small-batch", "thip_smallbatch.hip"),
     "midbatch": (r"midbatch(_init)?_k", ("midbatch_k", "midbatch_init_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
     "sdpbatch": (r"sdpbatch(_init|_project)?_k", ("sdpbatch_k", "sdpbatch_init_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
+    "raggedbatch": (r"raggedbatch(_init)?_k", ("raggedbatch_k", "raggedbatch_init_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
 }
 
 

@@ -77,6 +77,18 @@ class SdpBatchInfo(C.Structure):
     _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
 
 
+class RaggedBatchClass(C.Structure):
+    _fields_ = [("n_prob", C.c_int32), ("live", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32),
+                ("launches", C.c_int64), ("workgroups", C.c_int64)]
+
+
+class RaggedBatchInfo(C.Structure):
+    _fields_ = [("n_prob", C.c_int32), ("live", C.c_int32), ("n_layouts", C.c_int32), ("n_load16", C.c_int32),
+                ("arena_bytes", C.c_size_t), ("device_bytes", C.c_size_t), ("device_bytes_all", C.c_size_t),
+                ("launches", C.c_int64), ("workgroups", C.c_int64), ("a_bytes_per_iter", C.c_size_t),
+                ("cls", RaggedBatchClass * 2)]
+
+
 class GemvPlanRec(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("vw", "nj", "ku", "tiles", "chunks", "cols_per_chunk", "m_load", "chunks2",
                                          "cols_per_chunk2", "reserved")]
@@ -271,6 +283,29 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
     })
+
+# the ragged batch: the same methods on a handle whose problems each have their own shape (totsu_amd/csrc/thip_raggedbatch.hip)
+_psz, _p32, _p64 = C.POINTER(_sz), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_p = "thip_raggedbatch_"
+PROTOTYPES.update({
+    _p + "fits": (_i, [_sz, _psz, _psz, _psz, _p32, _p64, C.POINTER(_i), _psz, C.POINTER(_i)]),
+    _p + "create": (_i, [_sz, _psz, _psz, _vp, _p64, _vp, _p64, _vp, _p64, _vp, _p64, _psz, _p32, _p64, C.POINTER(Param),
+                         C.POINTER(_vp)]),
+    _p + "set_param": PROTOTYPES["thip_sdpbatch_set_param"],
+    _p + "init": PROTOTYPES["thip_sdpbatch_init"],
+    _p + "run": PROTOTYPES["thip_sdpbatch_run"],
+    _p + "run_until_any": PROTOTYPES["thip_sdpbatch_run_until_any"],
+    _p + "status": PROTOTYPES["thip_sdpbatch_status"],
+    _p + "solution": PROTOTYPES["thip_sdpbatch_solution"],
+    _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
+    _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
+    _p + "replace": PROTOTYPES["thip_sdpbatch_replace"],
+    _p + "info": (_i, [_vp, C.POINTER(RaggedBatchInfo)]),
+    _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
+    "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
+    "thip_test_raggedbatch_plan": (_i, [_sz, _psz, _psz, _psz, _p32, _p64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p64,
+                                        C.POINTER(RaggedBatchInfo)]),
+})
 
 _NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen"}
 

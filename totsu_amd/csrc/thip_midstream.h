@@ -1,9 +1,10 @@
-// thip_midstream.h -- what the two batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
-// second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip): the LDS map of a problem's vectors, the pass over A
+// thip_midstream.h -- what the batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
+// second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip; thip_raggedbatch.hip: the same on problems of
+// different shapes, through the locator seam of the bodies): the LDS map of a problem's vectors, the pass over A
 // (mb_pass), the iteration's body -- the carried recurrence, two passes per iteration, every vector in LDS -- with one hook in the
 // block-cone phase between the two passes, the thread choice and what both add to the info record.  The init kernel's body, the
 // criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
-// Included once by each of the two translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// Included once by each of the three translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
 // A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when
@@ -164,22 +165,24 @@ struct MbNoPsd {
 };
 
 // ob_init_body with the |A| sums from one streamed pass
-__device__ __forceinline__ void mb_init_body(const ObArgs &a)
+template <class AT = ObUniform>
+__device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT())
 {
     const int n = a.n, m = a.m;
     const MbMap L(n, m);
     float *S = mb_lds;
-    ob_init_body(a, ob_problem(a.live, a.first), L, S, [&](const float *A) {
+    ob_init_body(a, at.problem(a), L, S, [&](const float *A) {
         mb_pass<true>(A, mb_vec(A, m), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
-    });
+    }, at);
 }
 
 // `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
-// (called by every thread, after the second-order cones; hp, gp and g are dead there)
-template <class PSD>
-__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones)
+// (called by every thread, after the second-order cones; hp, gp and g are dead there).  AT: which problem and where its arena block
+// lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor)
+template <class PSD, class AT = ObUniform>
+__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones, const AT &at = AT())
 {
-    const int p = ob_problem(a.live, a.first);
+    const int p = at.problem(a);
     SbStatus *const gst = a.st + p;
     if (gst->stop != 0) return;
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -200,7 +203,7 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
     const SbSlot sl = a.slots[p];
     const float *const A = sl.a;
     const bool vec = mb_vec(A, m);
-    float *const ar = a.arena + (size_t)p * a.stride;
+    float *const ar = at.block(a, p);
     {
         const int nstate = 6 * n + 10 * m;                 // the arena's order is the LDS order from xx on
         for (int i = tid; i < nstate; i += T) xx[i] = ar[i];

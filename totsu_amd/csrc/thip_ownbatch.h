@@ -1,5 +1,5 @@
-// thip_ownbatch.h -- what the "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip and
-// thip_sdpbatch.hip: A streamed from memory, thip_midstream.h).
+// thip_ownbatch.h -- what the "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip,
+// thip_sdpbatch.hip and thip_raggedbatch.hip: A streamed from memory, thip_midstream.h).
 //   device: the launch arguments (ObArgs), the status block and the slot of a problem, the problem's scalars (ObScalars), the
 //           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
 //           functions of the iteration that do not touch A (block_sums; thip_step.h: the arithmetic every loop shares).  The two recurrences -- three passes
@@ -65,6 +65,16 @@ using ObArgs = ObArgsT<ObShape>;
 // address taken they become flat loads
 __device__ __forceinline__ int ob_problem(const int *live, int first) { return live ? live[blockIdx.x] : first + (int)blockIdx.x; }
 
+// the seam between the shared bodies and a batch's bookkeeping: which problem the workgroup serves, where that problem's block of
+// the arena begins and how many floats it carries behind the preconditioner.  ObUniform: one stride for every problem (the three
+// uniform families; the words are the ones the bodies held before the seam, at the places they held them).  The ragged batch
+// (thip_raggedbatch.hip) hands in what it read from its problem's descriptor
+struct ObUniform {
+    template <class ARGS> __device__ __forceinline__ int problem(const ARGS &a) const { return ob_problem(a.live, a.first); }
+    template <class ARGS> __device__ __forceinline__ float *block(const ARGS &a, int p) const { return a.arena + (size_t)p * a.stride; }
+    template <class ARGS> __device__ __forceinline__ int carried(const ARGS &a, int n, int m) const { return (int)a.stride - (5 * n + 9 * m); }
+};
+
 // Q sums over the workgroup; every thread gets every result.  sh: 64 floats of LDS
 template <int Q>
 __device__ __forceinline__ void block_sums(float *q, float *sh)
@@ -121,8 +131,8 @@ struct ObScalars {
 // of |A| in S[L.h ..] and the column sums in S[L.g ..], visible to every thread on return.  product_group takes the minimum over
 // every block cone, second-order or PSD.  What the family carries in the arena behind the preconditioner (the stride says how
 // much) starts at zero: A 0, A^T 0
-template <class ARGS, class MAP, class SUMS>
-__device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L, float *S, const SUMS &abs_sums)
+template <class ARGS, class MAP, class SUMS, class AT = ObUniform>
+__device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L, float *S, const SUMS &abs_sums, const AT &at = AT())
 {
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
     const SbSlot sl = a.slots[p];
@@ -134,7 +144,7 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
     for (int i = tid; i < n; i += T) { const float t = S[L.c + i]; q[2] = fmaf(t, t, q[2]); q[3] += fabsf(t); }
     block_sums<4>(q, S + L.sh);
     abs_sums(sl.a);
-    float *ar = a.arena + (size_t)p * a.stride;
+    float *ar = at.block(a, p);
     float *gTx = ar + 4 * n + 6 * m, *gTy = gTx + n, *gTs = gTy + m, *gSv = gTs + m, *gcar = gSv + m;
     for (int i = tid; i < n; i += T) {
         const float t = S[L.g + i] + fabsf(S[L.c + i]);
@@ -163,7 +173,7 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
     __syncthreads();
     for (int i = tid; i < m; i += T) { gTy[i] = S[L.Ty + i]; gTs[i] = S[L.Ts + i]; }
     for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
-    const int ncar = (int)a.stride - (5 * n + 9 * m);
+    const int ncar = at.carried(a, n, m);
     for (int i = tid; i < ncar; i += T) gcar[i] = 0.0f;
     if (tid == 0) {
         SbStatus s;
@@ -513,26 +523,21 @@ int ob_status(const ObFamily &f, OwnBatch *h, int i, thip_status *host_status)
     return 0;
 }
 
-int ob_solution(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
+// solution, iterate and precond of problem i, whose block of the arena is ar and whose shape is n, m (the _at forms: a handle of one
+// shape passes its own, the ragged batch the problem's)
+int ob_solution_at(OwnBatch *h, int i, const float *ar, size_t n, size_t m, float *host_x, float *host_y)
 {
-    THIP_NEED_INIT();
-    THIP_RC(ob_member(f, h, i));
     THIP_RC(ob_status_one(h, i));
-    const float *ar = h->arena + (size_t)i * h->stride;
-    if (host_x) THIP_RC(thip_d2h(host_x, ar, h->n));
-    if (host_y) THIP_RC(thip_d2h(host_y, ar + 4 * h->n, h->m));
-    ob_finalize(h->hst[i], host_x, h->n);
-    ob_finalize(h->hst[i], host_y, h->m);
+    if (host_x) THIP_RC(thip_d2h(host_x, ar, n));
+    if (host_y) THIP_RC(thip_d2h(host_y, ar + 4 * n, m));
+    ob_finalize(h->hst[i], host_x, n);
+    ob_finalize(h->hst[i], host_y, m);
     return 0;
 }
 
-int ob_iterate(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
+int ob_iterate_at(OwnBatch *h, int i, const float *ar, size_t n, size_t m, float *host_x, float *host_y)
 {
-    THIP_NEED_INIT();
-    THIP_RC(ob_member(f, h, i));
-    THIP_RC(ob_status_one(h, i));
-    const size_t n = h->n, m = h->m;
-    const float *ar = h->arena + (size_t)i * h->stride;      // xx u kx ku | xy xs v ..
+    THIP_RC(ob_status_one(h, i));                            // ar: xx u kx ku | xy xs v ..
     if (host_x) {
         THIP_RC(thip_d2h(host_x, ar, n));
         THIP_RC(thip_d2h(host_x + n, ar + 4 * n, 2 * m));
@@ -547,13 +552,10 @@ int ob_iterate(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host
     return 0;
 }
 
-int ob_precond(const ObFamily &f, OwnBatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
+int ob_precond_at(OwnBatch *h, int i, const float *ar, size_t n, size_t m, float *host_dp_tau, float *host_dp_sigma)
 {
-    THIP_NEED_INIT();
-    THIP_RC(ob_member(f, h, i));
     THIP_RC(ob_status_one(h, i));
-    const size_t n = h->n, m = h->m;
-    const float *k = h->arena + (size_t)i * h->stride + 4 * n + 6 * m;      // Tx Ty Ts Sv
+    const float *k = ar + 4 * n + 6 * m;                                    // Tx Ty Ts Sv
     if (host_dp_tau) {
         THIP_RC(thip_d2h(host_dp_tau, k, n + 2 * m));
         host_dp_tau[n + 2 * m] = h->hst[i].t_tau;
@@ -564,6 +566,27 @@ int ob_precond(const ObFamily &f, OwnBatch *h, int i, float *host_dp_tau, float 
         host_dp_sigma[n + m] = h->hst[i].s_kappa;
     }
     return 0;
+}
+
+int ob_solution(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_member(f, h, i));
+    return ob_solution_at(h, i, h->arena + (size_t)i * h->stride, h->n, h->m, host_x, host_y);
+}
+
+int ob_iterate(const ObFamily &f, OwnBatch *h, int i, float *host_x, float *host_y)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_member(f, h, i));
+    return ob_iterate_at(h, i, h->arena + (size_t)i * h->stride, h->n, h->m, host_x, host_y);
+}
+
+int ob_precond(const ObFamily &f, OwnBatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_member(f, h, i));
+    return ob_precond_at(h, i, h->arena + (size_t)i * h->stride, h->n, h->m, host_dp_tau, host_dp_sigma);
 }
 
 int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
