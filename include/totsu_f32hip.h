@@ -735,6 +735,63 @@ int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a,
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
 int thip_raggedbatch_destroy(thip_raggedbatch *h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Many problems of one shape n, m and one cone layout, each with its own SPARSE A with its own pattern (thip_sparsebatch.hip;
+ * DESIGN.md 4.2).  The iteration is thip_sdpbatch's -- one workgroup per running problem, its vectors in LDS, all five cones, PSD
+ * orders <= 64 projected on chip --, but a pass walks the problem's entries instead of streaming m n floats.  Problem p arrives as
+ * HOST CSC arrays (column pointers from 0, row indices strictly ascending inside a column, f32 values; explicit zeros are kept as
+ * entries); the library packs every problem on the host into a blob of 4-byte words that holds the entries twice, in column order
+ * and in row order, and uploads all of them in one copy.  Every slot reserves the same capacity,
+ * 16 nnz_cap + 4 (2 (m + n) + 4) bytes rounded up to 16, so replace can hand a slot another pattern of at most nnz_cap entries.
+ * The rule is thip_sdpbatch_fits' on (n, m, layout).  The blob is RESIDENT -- copied into LDS once per launch and read there -- when
+ * the LDS map of thip_sdpbatch plus the capacity is at most 163 840 bytes; otherwise the batch is taken all the same and every pass
+ * reads the entries from memory (STREAMED).  Both give the same bits.  Refused (THIP_E_INVALID, before anything is allocated):
+ * column pointers that are not monotone from 0, a row index out of range or not strictly ascending, a value that is not finite,
+ * more entries than nnz_cap, nnz_cap > m n, and what thip_sdpbatch_fits refuses.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_sparsebatch thip_sparsebatch;
+typedef struct thip_sparsebatch_info_t {
+    int32_t n_prob, threads;          /* as thip_midbatch_info_t ... */
+    int32_t lds_bytes, live;
+    size_t  arena_bytes;
+    size_t  device_bytes;             /* everything this object allocated on the device, the blobs among it */
+    size_t  device_bytes_all;         /* summed over every thip_sparsebatch alive in the process */
+    int64_t launches, workgroups;
+    size_t  a_bytes_per_iter;         /* bytes of A read from memory per problem-iteration: 0 when resident, else twice the blob's
+                                         used bytes (the mean over the slots) */
+    int32_t max_psd_order, n_psd;     /* as thip_sdpbatch_info_t */
+    size_t  psd_lds_bytes;
+    size_t  nnz_cap;                  /* entries a slot can take */
+    size_t  nnz_total;                /* entries held, summed over the slots */
+    size_t  blob_bytes;               /* the capacity every slot reserves */
+    int32_t resident, reserved;       /* 1: the blob is read from LDS, 0: from memory */
+} thip_sparsebatch_info_t;
+/* the rule alone (needs no device): 0 and the LDS bytes / threads of one workgroup and whether a blob of capacity nnz_cap is
+ * resident, or THIP_E_INVALID */
+int thip_sparsebatch_fits(size_t n, size_t m, size_t nnz_cap, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                          size_t *host_lds_bytes, int *host_threads, int *host_resident);
+/* host_colptr: n_prob (n + 1) column pointers, each problem's from 0; problem p's row indices and values are the
+ * host_colptr[p (n + 1) + n] entries of host_rowidx / host_values from host_start[p] on.  dev_vecs_b, dev_vecs_c,
+ * dev_vecs_b_rowabs (may be NULL: |b|): device arrays, problem after problem.  nnz_cap: 0 = the largest entry count given */
+int thip_sparsebatch_create(size_t n, size_t m, size_t n_prob, const int64_t *host_colptr, const int64_t *host_start,
+                            const int32_t *host_rowidx, const float *host_values, const float *dev_vecs_b, const float *dev_vecs_c,
+                            const float *dev_vecs_b_rowabs, size_t nnz_cap, size_t n_seg, const int32_t *host_seg_type,
+                            const int64_t *host_seg_len, const thip_param *par, thip_sparsebatch **out);
+int thip_sparsebatch_set_param(thip_sparsebatch *h, const thip_param *par);
+int thip_sparsebatch_init(thip_sparsebatch *h);
+int thip_sparsebatch_run(thip_sparsebatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_sparsebatch_run_until_any(thip_sparsebatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_sparsebatch_status(thip_sparsebatch *h, int i, thip_status *host_status);
+int thip_sparsebatch_solution(thip_sparsebatch *h, int i, float *host_x, float *host_y);
+int thip_sparsebatch_iterate(thip_sparsebatch *h, int i, float *host_x, float *host_y);
+int thip_sparsebatch_precond(thip_sparsebatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+/* slot i -- running or stopped -- takes the host CSC arrays of one problem (any pattern of at most nnz_cap entries) and device
+ * b, c, row sums, and is initialised afresh; no other slot is touched */
+int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx,
+                             const float *host_values, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs);
+int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
+int thip_sparsebatch_destroy(thip_sparsebatch *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

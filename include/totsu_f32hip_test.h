@@ -190,6 +190,20 @@ int thip_test_raggedbatch_plan(size_t n_prob, const size_t *host_n, const size_t
                                const int32_t *host_seg_type, const int64_t *host_seg_len, int force_threads, int *host_class,
                                int *host_order, int *host_layout, int64_t *host_arena_at, thip_raggedbatch_info_t *host_info);
 
+/* TEST HOOK: the workgroup size of a sparse batch (thip_sparsebatch.hip): 256 or 1024 threads, 0 = by shape.  Before
+ * thip_sparsebatch_init. */
+int thip_test_sparsebatch_force_threads(thip_sparsebatch *h, int threads);
+
+/* TEST HOOK: where a sparse batch reads its blobs: 0 from memory (streamed), 1 from LDS (resident; THIP_E_INVALID when the blob does
+ * not fit beside the vectors).  Before thip_sparsebatch_init. */
+int thip_test_sparsebatch_force_resident(thip_sparsebatch *h, int resident);
+
+/* TEST HOOK: the blob thip_sparsebatch_create would store for one problem given as host CSC arrays (needs no device), with every
+ * refusal of the stored form (nnz_cap: 0 = m n).  host_used_words: the words the blob uses; host_words (may be NULL): cap_words words
+ * to receive them; host_long (may be NULL): the row length above which a row is summed by a wave. */
+int thip_test_sparsebatch_pack(size_t n, size_t m, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,
+                               size_t nnz_cap, uint32_t *host_words, size_t cap_words, size_t *host_used_words, int *host_long);
+
 #ifdef __cplusplus
 }
 #endif

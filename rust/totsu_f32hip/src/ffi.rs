@@ -64,6 +64,18 @@ pub struct thip_sdpbatch_info_t {
 }
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
+pub struct thip_sparsebatch_info_t {
+    pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub a_bytes_per_iter: usize,
+    pub max_psd_order: i32, pub n_psd: i32,
+    pub psd_lds_bytes: usize,
+    pub nnz_cap: usize, pub nnz_total: usize, pub blob_bytes: usize,
+    pub resident: i32, pub reserved: i32,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
 pub struct thip_raggedbatch_class_t {
     pub n_prob: i32, pub live: i32, pub threads: i32, pub lds_bytes: i32,
     pub launches: i64, pub workgroups: i64,
@@ -118,6 +130,7 @@ pub enum thip_smallbatch {}
 pub enum thip_midbatch {}
 pub enum thip_sdpbatch {}
 pub enum thip_raggedbatch {}
+pub enum thip_sparsebatch {}
 pub enum thip_sptile {}
 pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
@@ -374,6 +387,31 @@ extern "C" {
                                       host_seg_type: *const i32, host_seg_len: *const i64, force_threads: c_int,
                                       host_class: *mut c_int, host_order: *mut c_int, host_layout: *mut c_int,
                                       host_arena_at: *mut i64, host_info: *mut thip_raggedbatch_info_t) -> c_int;
+    // problems of one shape, each with its own sparse A held as packed entries (thip_sparsebatch.hip)
+    pub fn thip_sparsebatch_fits(n: usize, m: usize, nnz_cap: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                                 host_lds_bytes: *mut usize, host_threads: *mut c_int, host_resident: *mut c_int) -> c_int;
+    pub fn thip_sparsebatch_create(n: usize, m: usize, n_prob: usize, host_colptr: *const i64, host_start: *const i64,
+                                   host_rowidx: *const i32, host_values: *const f32, dev_vecs_b: *const f32, dev_vecs_c: *const f32,
+                                   dev_vecs_b_rowabs: *const f32, nnz_cap: usize, n_seg: usize, host_seg_type: *const i32,
+                                   host_seg_len: *const i64, par: *const thip_param, out: *mut *mut thip_sparsebatch) -> c_int;
+    pub fn thip_sparsebatch_set_param(h: *mut thip_sparsebatch, par: *const thip_param) -> c_int;
+    pub fn thip_sparsebatch_init(h: *mut thip_sparsebatch) -> c_int;
+    pub fn thip_sparsebatch_run(h: *mut thip_sparsebatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sparsebatch_run_until_any(h: *mut thip_sparsebatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sparsebatch_status(h: *mut thip_sparsebatch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sparsebatch_solution(h: *mut thip_sparsebatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_sparsebatch_iterate(h: *mut thip_sparsebatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_sparsebatch_precond(h: *mut thip_sparsebatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_sparsebatch_replace(h: *mut thip_sparsebatch, i: c_int, host_colptr: *const i64, host_rowidx: *const i32,
+                                    host_values: *const f32, dev_vec_b: *const f32, dev_vec_c: *const f32,
+                                    dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_sparsebatch_info(h: *const thip_sparsebatch, host_info: *mut thip_sparsebatch_info_t) -> c_int;
+    pub fn thip_sparsebatch_destroy(h: *mut thip_sparsebatch) -> c_int;
+    pub fn thip_test_sparsebatch_force_threads(h: *mut thip_sparsebatch, threads: c_int) -> c_int;
+    pub fn thip_test_sparsebatch_force_resident(h: *mut thip_sparsebatch, resident: c_int) -> c_int;
+    pub fn thip_test_sparsebatch_pack(n: usize, m: usize, host_colptr: *const i64, host_rowidx: *const i32, host_values: *const f32,
+                                      nnz_cap: usize, host_words: *mut u32, cap_words: usize, host_used_words: *mut usize,
+                                      host_long: *mut c_int) -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

@@ -35,7 +35,13 @@ layout that the workgroup looks up in a table:
 
     raggedbatch_k and raggedbatch_init_k: the SDP batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
 
-usage: check_kernel_resources.py <remarks file> [--report] [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch]"""
+The sparse batch (thip_sparsebatch.hip, --family sparsebatch) is the same iteration with a pass that walks a problem's packed entries,
+in LDS or in memory:
+
+    sparsebatch_k and sparsebatch_init_k: the SDP batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
+
+usage: check_kernel_resources.py <remarks file> [--report]
+                                 [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch]"""
 import re
 import sys
 
@@ -96,6 +102,7 @@ OWNBATCH = {
     "midbatch": (r"midbatch(_init)?_k", ("midbatch_k", "midbatch_init_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
     "sdpbatch": (r"sdpbatch(_init|_project)?_k", ("sdpbatch_k", "sdpbatch_init_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
     "raggedbatch": (r"raggedbatch(_init)?_k", ("raggedbatch_k", "raggedbatch_init_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
+    "sparsebatch": (r"sparsebatch(_init)?_k", ("sparsebatch_k", "sparsebatch_init_k"), 128, "sparse batch", "thip_sparsebatch.hip"),
 }
 
 

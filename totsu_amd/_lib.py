@@ -77,6 +77,12 @@ class SdpBatchInfo(C.Structure):
     _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
 
 
+class SparseBatchInfo(C.Structure):
+    _fields_ = SmallBatchInfo._fields_ + [("a_bytes_per_iter", C.c_size_t), ("max_psd_order", C.c_int32), ("n_psd", C.c_int32),
+                                          ("psd_lds_bytes", C.c_size_t), ("nnz_cap", C.c_size_t), ("nnz_total", C.c_size_t),
+                                          ("blob_bytes", C.c_size_t), ("resident", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RaggedBatchClass(C.Structure):
     _fields_ = [("n_prob", C.c_int32), ("live", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32),
                 ("launches", C.c_int64), ("workgroups", C.c_int64)]
@@ -305,6 +311,27 @@ PROTOTYPES.update({
     "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
     "thip_test_raggedbatch_plan": (_i, [_sz, _psz, _psz, _psz, _p32, _p64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p64,
                                         C.POINTER(RaggedBatchInfo)]),
+})
+
+# the sparse batch: the same methods on host CSC arrays (totsu_amd/csrc/thip_sparsebatch.hip)
+_p = "thip_sparsebatch_"
+PROTOTYPES.update({
+    _p + "fits": (_i, [_sz, _sz, _sz, _sz, _p32, _p64, _psz, C.POINTER(_i), C.POINTER(_i)]),
+    _p + "create": (_i, [_sz, _sz, _sz, _p64, _p64, _p32, fp, _vp, _vp, _vp, _sz, _sz, _p32, _p64, C.POINTER(Param), C.POINTER(_vp)]),
+    _p + "set_param": PROTOTYPES["thip_sdpbatch_set_param"],
+    _p + "init": PROTOTYPES["thip_sdpbatch_init"],
+    _p + "run": PROTOTYPES["thip_sdpbatch_run"],
+    _p + "run_until_any": PROTOTYPES["thip_sdpbatch_run_until_any"],
+    _p + "status": PROTOTYPES["thip_sdpbatch_status"],
+    _p + "solution": PROTOTYPES["thip_sdpbatch_solution"],
+    _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
+    _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
+    _p + "replace": (_i, [_vp, _i, _p64, _p32, fp, _vp, _vp, _vp]),
+    _p + "info": (_i, [_vp, C.POINTER(SparseBatchInfo)]),
+    _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
+    "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
+    "thip_test_sparsebatch_force_resident": (_i, [_vp, _i]),
+    "thip_test_sparsebatch_pack": (_i, [_sz, _sz, _p64, _p32, fp, _sz, C.POINTER(C.c_uint32), _sz, _psz, C.POINTER(_i)]),
 })
 
 _NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen"}

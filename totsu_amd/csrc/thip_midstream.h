@@ -1,10 +1,10 @@
 // thip_midstream.h -- what the batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
 // second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip; thip_raggedbatch.hip: the same on problems of
-// different shapes, through the locator seam of the bodies): the LDS map of a problem's vectors, the pass over A
-// (mb_pass), the iteration's body -- the carried recurrence, two passes per iteration, every vector in LDS -- with one hook in the
-// block-cone phase between the two passes, the thread choice and what both add to the info record.  The init kernel's body, the
-// criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
-// Included once by each of the three translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// different shapes, through the locator seam of the bodies; thip_sparsebatch.hip: a sparse A held as packed entries, through the
+// matrix-policy seam): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
+// two passes per iteration, every vector in LDS -- with one hook in the block-cone phase between the two passes, the thread choice
+// and what they add to the info record.  The init kernel's body, the criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
+// Included once by each of the four translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
 // A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when
@@ -164,23 +164,37 @@ struct MbNoPsd {
     __device__ __forceinline__ void operator()(float *, const MbMap &, const ObArgs &) const {}
 };
 
-// ob_init_body with the |A| sums from one streamed pass
-template <class AT = ObUniform>
-__device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT())
+// the matrix policy of the two bodies: what the slot's `a` pointer means and what is loaded at launch entry (open: called by every
+// thread, before the barrier that ends the body's load phase), and how a pass is called.  MbDenseA: the pointer is the problem's
+// dense column-major A, nothing is loaded, the pass streams it (mb_pass).  thip_sparsebatch.hip hands in the policy of a sparse A
+struct MbDenseA {
+    struct Mat { const float *A; bool vec; };
+    __device__ __forceinline__ Mat open(const float *a, int m, int, float *) const { return Mat{ a, mb_vec(a, m) }; }
+    template <bool ABS>
+    __device__ __forceinline__ void pass(const Mat &M, int m, int n, const float *xn, const float *xt, float *h, float *g, float *hp,
+                                         float *gp) const
+    {
+        mb_pass<ABS>(M.A, M.vec, m, n, xn, xt, h, g, hp, gp);
+    }
+};
+
+// ob_init_body with the |A| sums from one pass
+template <class AT = ObUniform, class MAT = MbDenseA>
+__device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT(), const MAT &mat = MAT())
 {
     const int n = a.n, m = a.m;
     const MbMap L(n, m);
     float *S = mb_lds;
     ob_init_body(a, at.problem(a), L, S, [&](const float *A) {
-        mb_pass<true>(A, mb_vec(A, m), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
+        mat.template pass<true>(mat.open(A, m, n, S), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
     }, at);
 }
 
 // `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
 // (called by every thread, after the second-order cones; hp, gp and g are dead there).  AT: which problem and where its arena block
-// lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor)
-template <class PSD, class AT = ObUniform>
-__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones, const AT &at = AT())
+// lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor).  MAT: the matrix policy (above)
+template <class PSD, class AT = ObUniform, class MAT = MbDenseA>
+__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones, const AT &at = AT(), const MAT &mat = MAT())
 {
     const int p = at.problem(a);
     SbStatus *const gst = a.st + p;
@@ -201,8 +215,7 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
 
     // ---- load ----
     const SbSlot sl = a.slots[p];
-    const float *const A = sl.a;
-    const bool vec = mb_vec(A, m);
+    const auto A = mat.open(sl.a, m, n, S);
     float *const ar = at.block(a, p);
     {
         const int nstate = 6 * n + 10 * m;                 // the arena's order is the LDS order from xx on
@@ -219,7 +232,7 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
         float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
         for (int i = tid; i < n; i += T) { q[0] = fmaf(c[i], u[i], q[0]); q[2] = fmaf(c[i], xx[i], q[2]); }
         for (int i = tid; i < m; i += T) { q[1] = fmaf(b[i], v[i], q[1]); q[3] = fmaf(b[i], xy[i], q[3]); }
-        mb_pass<false>(A, vec, m, n, u, v, h, g, hp, gp);
+        mat.template pass<false>(A, m, n, u, v, h, g, hp, gp);
         block_sums<4>(q, sh);
         const float cx_old = q[2], by_old = q[3];
         for (int i = tid; i < n; i += T) xx[i] = kahan_add_at(xx[i], inc_xx(Tx[i], g[i], c[i], s.kappa), comp, kx, i);
@@ -251,7 +264,7 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
         }
         psd_cones(S, L, a);
         // ---- h = A x_x, g = A^T x_y of the new iterate: the criteria, and K rx = K x_k - 2 K x_{k+1} ----
-        mb_pass<false>(A, vec, m, n, xx, xy, h, g, hp, gp);
+        mat.template pass<false>(A, m, n, xx, xy, h, g, hp, gp);
         ob_criteria_sums(q, n, m, s.tau, a.eps_zero, b, c, xx, xy, xs, h, g, sh);
         const float pp = q[0], by = q[1], dd = q[2], cx = q[3];
         // ---- y += S o (-K rx) (ycrit_k), the pair carried on ----
