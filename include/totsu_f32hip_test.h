@@ -51,7 +51,13 @@ int thip_test_solver_kahan(thip_solver *s, float *host_kx, float *host_ky, float
  * [0] = the kernel's error word (0 = ok), [1] = members per group, [2] = groups, [3] = panels per group, [4] = 16-byte
  * slots per streaming thread, [5] = polls of all gathers that found a granule missing (summed over workgroups and launches),
  * [6] = the most polls any one gather needed.  force_members > 0: that many workgroups per column group instead of the planner's choice
- * (a power of two the rows fit); pub_agent != 0: partial dots published with agent-scope (sc1) stores. */
+ * (a power of two the rows fit); pub_agent != 0: partial dots published with agent-scope (sc1) stores.  host_info[7] = columns per
+ * panel.
+ * pin_g != 0: the EXACT geometry -- pin_w columns per panel (1, 2; 4 for 16-bit elements) and pin_g members per group, whatever the
+ * planner would choose, also a group size below the one its few-columns rule raises it to (groups without columns idle); `variant`
+ * and `force_members` are then not read.  What the kernel itself needs stays enforced, THIP_E_INVALID with nothing launched: m a
+ * multiple of the rows per 16-byte slot (4, 16-bit: 8), lda >= m, n >= 40 pin_w, pin_g a power of two up to 32 whose
+ * ceil(m / pin_g) rows fit the slots the (elem, pin_w) family has instances for. */
 typedef struct thip_sweep_test {
     size_t m, n, lda;
     const float *mat_a, *v, *xy, *c, *su, *tx;
@@ -66,8 +72,33 @@ typedef struct thip_sweep_test {
     const float *inv_s;             /* THIP_A_F16: 1 / scale per column (thip_to_f16), else NULL */
     float *host_sums;               /* optional, 4 floats on the HOST: the sums over n the sweep leaves for the criteria and the scalar
                                      * updates (tau taken as 1): ||c + A^T xy||^2, c.xx_in, c.u, c.(xx_in - 2 xx_out) */
+    int32_t pin_w, pin_g;           /* pin_g != 0: exactly this geometry (above) */
 } thip_sweep_test;
 int thip_test_sweep(const thip_sweep_test *t, float *host_ms, int *host_info);
+
+/* One geometry of the one-pass kernel: members (workgroups) per column group, groups (members x ngroups = 256), rows per member,
+ * columns per group, panels per group, 16-byte slots per streaming thread, columns per panel, the element kind; the padded length of
+ * a group's share of an N product in floats, and the 8-byte words of the granule ring. */
+typedef struct thip_sweep_plan_rec {
+    int32_t members, ngroups, rows_per_member, cols_per_group, npan, nslot, cols_per_panel, elem;
+    size_t mpad, gran_words;
+} thip_sweep_plan_rec;
+
+/* The planning of the one-pass kernel with nothing launched (needs no GPU and no thip_init; a device of 256 CUs is assumed): the
+ * geometry for an m x n matrix of `elem` with leading dimension lda at cols_per_panel columns per panel -- force_members = 0: the
+ * smallest group size the rows fit times gmul (1, 2, 4, 8), raised by the few-columns rule, as the solver's candidates are made;
+ * force_members > 0: exactly that group size, as thip_sweep_test.pin_g (gmul is not read).  THIP_E_INVALID where the kernel has no
+ * instance for it.  host_candidates (room for 6) / host_n_candidates: the geometries the solver's plan autotune would time on this
+ * matrix, in its order -- thip_test_solver_pin_sweep_plan takes an index into this list.  Any pointer may be NULL. */
+int thip_test_sweep_plan(size_t m, size_t n, size_t lda, int elem, int cols_per_panel, int gmul, int force_members,
+                         thip_sweep_plan_rec *host_plan, thip_sweep_plan_rec *host_candidates, int *host_n_candidates);
+
+/* TEST HOOK: pins the geometry of the one-pass kernel for the stored form of A in use to the candidate_index-th of the geometries
+ * the plan autotune would time on this matrix (thip_test_sweep_plan lists them), installed the way the autotune installs its pick but
+ * without a timing sweep and without the slower-than-the-carried-schedule safety net; -1: back to the library's choice.  After
+ * thip_solver_init, before the first run.  thip_solver_sweep_plan reports the pinned geometry.  THIP_E_INVALID, the solver left as
+ * it was: an index the matrix does not offer, or a solver the one-pass kernel does not run for. */
+int thip_test_solver_pin_sweep_plan(thip_solver *s, int candidate_index);
 
 /* test entry point for the matrix-core GEMM of the PSD projection chain: C = alpha * A * B + beta * D + gamma * I_n
  * with A symmetric and B arbitrary, all ld x ld column-major, ld a multiple of 64, zero padded beyond n */

@@ -103,6 +103,14 @@ pub struct thip_sweep_test {
     pub force_members: i32, pub pub_agent: i32, pub variant: i32, pub elem: i32,
     pub inv_s: *const f32,
     pub host_sums: *mut f32,
+    pub pin_w: i32, pub pin_g: i32,
+}
+
+#[repr(C)]
+pub struct thip_sweep_plan_rec {
+    pub members: i32, pub ngroups: i32, pub rows_per_member: i32, pub cols_per_group: i32, pub npan: i32, pub nslot: i32,
+    pub cols_per_panel: i32, pub elem: i32,
+    pub mpad: usize, pub gran_words: usize,
 }
 
 #[repr(C)]
@@ -452,6 +460,10 @@ extern "C" {
     pub fn thip_test_solver_pin_gemv_plan(s: *mut thip_solver, candidate_index: c_int) -> c_int;
     pub fn thip_test_spin_allreduce(s: *mut thip_solver, latency_us: c_int) -> c_int;
     pub fn thip_test_sweep(t: *const thip_sweep_test, host_ms: *mut f32, host_info: *mut c_int) -> c_int;
+    pub fn thip_test_sweep_plan(m: usize, n: usize, lda: usize, elem: c_int, cols_per_panel: c_int, gmul: c_int, force_members: c_int,
+                                host_plan: *mut thip_sweep_plan_rec, host_candidates: *mut thip_sweep_plan_rec,
+                                host_n_candidates: *mut c_int) -> c_int;
+    pub fn thip_test_solver_pin_sweep_plan(s: *mut thip_solver, candidate_index: c_int) -> c_int;
     pub fn thip_test_solver_kahan(s: *mut thip_solver, host_kx: *mut f32, host_ky: *mut f32, host_ks: *mut f32, host_ku: *mut f32,
                                   host_kv: *mut f32, host_mtail_form: *mut c_int) -> c_int;
     pub fn thip_test_sweep_fault(s: *mut thip_solver, kind: c_int, after_sweeps: i64, spin_max: c_int) -> c_int;

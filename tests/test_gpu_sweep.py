@@ -24,13 +24,34 @@ def T():
     return totsu_amd
 
 
-def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0):
+def _stored_16(A, m, elem):
+    """the 16-bit stored form of the rows of A (row j = column j of the m x n matrix, lda entries apart), made on the host by the
+    numpy restatements of thip_to_bf16 / thip_to_f16 (test_gpu_bf16.py checks them bit for bit): (bit patterns (n, lda), 1 / scale
+    per column or None, the matrix they stand for in f64 (n, m)).  Rows m .. lda - 1 hold a finite non-zero pattern: a kernel that
+    reads them shows it."""
+    from test_gpu_bf16 import bf16_bits, f16_quantize
+    n, lda = A.shape
+    bits = np.full((n, lda), 0x3c00, np.uint16)
+    if elem == 1:
+        bits[:, :m] = bf16_bits(A[:, :m])
+        return bits, None, (bits[:, :m].astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    q, inv, deq = f16_quantize(A[:, :m].T)
+    bits[:, :m] = q.T
+    return bits, inv, np.ascontiguousarray(deq.T)
+
+
+def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0, elem=0, pin=None):
+    """one launch of sweep_k alone against numpy f64 (on the matrix as stored: elem = 1 / 2 the bf16 / f16 form).  pin = (columns
+    per panel, members per group): that geometry exactly (thip_sweep_test.pin_w / pin_g), and the whole host_info comes back."""
     from totsu_amd import _lib
     from totsu_amd.fused import DeviceBuffer
     lib = _lib.lib
     rng = np.random.default_rng(seed)
     lda = lda or m
     A = (rng.standard_normal((n, lda)) / np.sqrt(n)).astype(np.float32)        # row j = column j of the m x n matrix
+    if elem:
+        bits, inv, Ad = _stored_16(A, m, elem)
+        A = np.concatenate([bits.ravel(), np.zeros(16, np.uint16)]).view(np.float32)
     v, xy = rng.standard_normal(m).astype(np.float32), rng.standard_normal(m).astype(np.float32)
     c = rng.standard_normal(n).astype(np.float32)
     su, tx = (rng.random(n) + 0.5).astype(np.float32), (rng.random(n) + 0.5).astype(np.float32)
@@ -40,6 +61,8 @@ def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0):
     kappa, rtau = -0.37, 0.81
     bufs = {k: DeviceBuffer.from_host(a) for k, a in dict(A=A.ravel(), v=v, xy=xy, c=c, su=su, tx=tx, u=u, xx=xx, gp=gp,
                                                           ku=ku, kx=kx).items()}
+    if elem == 2:
+        bufs["inv"] = DeviceBuffer.from_host(inv)
     outs = {k: DeviceBuffer(sz, zero=True) for k, sz in dict(xx_out=n, kx_out=n, hn=m, h3=m).items()}
     t = _lib.SweepTest()
     t.m, t.n, t.lda = m, n, lda
@@ -50,13 +73,17 @@ def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0):
     t.gp, t.hn, t.h3 = bufs["gp"].ptr, outs["hn"].ptr, outs["h3"].ptr
     t.kappa, t.rtau, t.first, t.reps = kappa, rtau, int(first), 1
     t.variant, t.force_members = variant, members
+    t.elem, t.inv_s = elem, (bufs["inv"].ptr if elem == 2 else None)
+    if pin is not None:
+        t.pin_w, t.pin_g = pin
     ms = (C.c_float * 2)()
     info = (C.c_int * 8)()
     sums = (C.c_float * 4)()
     t.host_sums = sums
     lib.thip_test_sweep(C.byref(t), ms, info)
     assert info[0] == 0, "the kernel raised its error word: %d" % info[0]
-    Ad = A[:, :m].astype(np.float64)
+    if not elem:
+        Ad = A[:, :m].astype(np.float64)
     gT, g3 = Ad @ v.astype(np.float64), Ad @ xy.astype(np.float64)
     k_u = ku.astype(np.float64) if comp else 0.0
     k_x = kx.astype(np.float64) if comp else 0.0
@@ -67,25 +94,30 @@ def _sweep_case(m, n, first, comp, seed, lda=None, variant=0, members=0):
     ref = {"u": u_ref, "x": x_ref, "gp": g3, "hn": Ad.T @ u_ref, "h3": Ad.T @ x_ref}
     for k in ref:
         err = np.abs(got[k] - ref[k]).max() / (np.abs(ref[k]).max() + 1e-30)
-        assert err < 5e-6, (m, n, first, comp, k, err)
+        assert err < 5e-6, (m, n, first, comp, elem, pin, k, err)
     # the sums over n the kernel leaves for the criteria and the scalar updates (tau = 1 in this entry point)
     c64, xx64 = c.astype(np.float64), xx.astype(np.float64)
     want = [((c64 + g3) ** 2).sum(), c64 @ xx64, c64 @ u_ref, c64 @ (xx64 - 2 * x_ref)]
     scale = [((c64 + g3) ** 2).sum(), np.abs(c64) @ np.abs(xx64), np.abs(c64) @ np.abs(u_ref), np.abs(c64) @ (np.abs(xx64) + 2 * np.abs(x_ref))]
     for q in range(4):
-        assert abs(sums[q] - want[q]) <= 2e-5 * scale[q], (m, n, first, comp, q, sums[q], want[q])
+        assert abs(sums[q] - want[q]) <= 2e-5 * scale[q], (m, n, first, comp, elem, pin, q, sums[q], want[q])
     # (the Kahan terms themselves: test_sweep_kernel_compensated_update_is_fast2sum_bit_for_bit -- here the f32 dots behind x_ref
     # err by more than a term is large)
     for b in list(bufs.values()) + list(outs.values()):
         b.free()
+    if pin is not None:
+        assert (info[7], info[1]) == tuple(pin), (pin, list(info))
+        return list(info)
     return info[1], info[2], info[3]
 
 
 @pytest.mark.parametrize("m,n", [(4096, 30000), (20000, 10000), (3584, 24000), (100000, 3000), (12500, 8000), (1000, 25000),
                                  (240, 120), (96, 83)])
 def test_sweep_kernel_vs_numpy(T, m, n):
-    """every group size (1 .. 32 workgroups per column), one and two 16-byte slots per thread, partial last panels,
-    groups without columns, with and without the u update / the Kahan terms"""
+    """one column per panel at the planner's own geometries (members per group, 16-byte slots per thread): (1, 3), (2, 6), (1, 2),
+    (8, 7), (2, 4), (1, 1) and twice (32, 1) -- partial last panels, groups without columns, with and without the u update / the
+    Kahan terms.  Every instance, group size and edge of the row deal and of the panel loops, at pinned geometries:
+    tests/test_gpu_sweep_instances.py"""
     for first in (0, 1):
         for comp in (0, 1):
             _sweep_case(m, n, first, comp, seed=m + 3 * n + first + 2 * comp)
@@ -104,7 +136,7 @@ def test_sweep_kernel_padded_leading_dimension(T):
     _sweep_case(2000, 5000, 0, 1, seed=5, lda=2048)
 
 
-def _exact_sweep_case(T, m, n, elem=0, variant=0, members=0, seed=0):
+def _exact_sweep_case(T, m, n, elem=0, variant=0, members=0, seed=0, pin=None):
     """sweep_k's update of x_x / u and of their Kahan terms, BIT FOR BIT, on data whose dot products are exact in f32 in any
     order of summation: A from {-1, -0.5, 0, 0.5, 1} (exact in bf16 and f16; the f16 column scales are powers of two), v, x_y,
     gP, c integers in [-4, 4] (every partial sum a multiple of 0.5 below 2^19), Su, Tx powers of two, kappa = -3/8,
@@ -113,6 +145,7 @@ def _exact_sweep_case(T, m, n, elem=0, variant=0, members=0, seed=0):
         y = f32(inc - k) ; x_out = f32(x + y) ; k_out = f32(f32(x_out - x) - y)
     on u, x_x = 1e3 x N(0, 1) with terms k of up to an ulp of their entry.  A term with the other sign, one that is not read, one
     that is not written, or a sum the compiler re-associated differs in the last bits.  Without the terms: x_out = f32(x + inc).
+    pin = (columns per panel, members per group): that geometry exactly (thip_sweep_test.pin_w / pin_g).
     Returns (members per group, groups, slots per thread)."""
     from totsu_amd import _lib
     D = T.DeviceBuffer
@@ -152,9 +185,12 @@ def _exact_sweep_case(T, m, n, elem=0, variant=0, members=0, seed=0):
         t.kappa, t.rtau, t.first, t.reps = float(kappa), float(rtau), first, 1
         t.variant, t.force_members, t.elem = variant, members, elem
         t.inv_s = mat.inv_ptr if elem == 2 else None
+        if pin is not None:
+            t.pin_w, t.pin_g = pin
         ms, info = (C.c_float * 2)(), (C.c_int * 8)()
         _lib.lib.thip_test_sweep(C.byref(t), ms, info)
         assert info[0] == 0, list(info)
+        assert pin is None or (info[7], info[1]) == tuple(pin), (pin, list(info))
         geom = (info[1], info[2], info[4])
         tag = (m, n, elem, variant, members, first, comp, geom)
         got_u, got_ku, got_x, got_kx = io["u"].to_host(), io["ku"].to_host(), outs["xx_out"].to_host(), outs["kx_out"].to_host()
@@ -189,14 +225,22 @@ def test_sweep_kernel_compensated_update_is_fast2sum_bit_for_bit(T, m, n, varian
     assert G * groups == 256
 
 
-def _check_sweep_iterates(T, dense, iters, tols):
-    ro = _oracle_snaps(dense, iters)
+def _check_sweep_iterates(T, dense, iters, tols, ro=None, pin=None, expect=None, a_storage="f32"):
+    """ro: the oracle's run on this problem (on the matrix as stored), where the caller shares one among cases; pin: the index of
+    the candidate geometry to install (thip_test_solver_pin_sweep_plan; -1 = the library's choice), expect: the (members, columns
+    per panel, slots) thip_solver_sweep_plan must then report.  Returns that report."""
+    ro = ro or _oracle_snaps(dense, iters)
     p = T.SolverParam()
     p.eps_acc = 1e-30
-    fs = T.FusedSolver.from_dense(dense, p, "sweep", sweep_min_bytes=0)
+    fs = T.FusedSolver.from_dense(dense, p, "sweep", sweep_min_bytes=0, a_storage=a_storage)
+    if pin is not None:
+        fs.pin_sweep_plan(pin)
     assert fs.schedule_in_use() == "sweep"
     assert fs.passes()[0] == 1
-    fc = T.FusedSolver.from_dense(dense, p, "carried")
+    plan = fs.sweep_plan()
+    geom = (plan["workgroups_per_column_group"], plan["columns_per_panel"], plan["slots_per_thread"])
+    assert expect is None or geom == tuple(expect), (pin, geom, expect)
+    fc = T.FusedSolver.from_dense(dense, p, "carried", a_storage=a_storage)
     N = dense.n + 2 * dense.m + 1
     done = 0
     for q, (it, tol) in enumerate(zip(iters, tols)):
@@ -216,6 +260,7 @@ def _check_sweep_iterates(T, dense, iters, tols):
         assert np.allclose(st.cri, ro.trace[it][2:], rtol=max(50 * tol, 1e-3), atol=1e-5), (it, st.cri, ro.trace[it])
     fs.destroy()
     fc.destroy()
+    return geom
 
 
 def _lp(T, sz, seed):

@@ -48,7 +48,12 @@ class SweepTest(C.Structure):
                                           "kx_out", "gp", "hn", "h3")] + \
                [("kappa", C.c_float), ("rtau", C.c_float), ("first", C.c_int32), ("reps", C.c_int32),
                 ("force_members", C.c_int32), ("pub_agent", C.c_int32), ("variant", C.c_int32), ("elem", C.c_int32), ("inv_s", C.c_void_p),
-                ("host_sums", C.POINTER(C.c_float))]
+                ("host_sums", C.POINTER(C.c_float)), ("pin_w", C.c_int32), ("pin_g", C.c_int32)]
+
+
+class SweepPlanRec(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("members", "ngroups", "rows_per_member", "cols_per_group", "npan", "nslot",
+                                         "cols_per_panel", "elem")] + [("mpad", C.c_size_t), ("gran_words", C.c_size_t)]
 
 
 class BatchInfo(C.Structure):
@@ -261,6 +266,8 @@ PROTOTYPES = {
     "thip_test_dual_gemv": (_i, [C.POINTER(GemvTest), C.POINTER(GemvPlanRec)]),
     "thip_test_gemv_plan": (_i, [_sz, _sz, _i, _i, _i, _sz, _sz, C.POINTER(GemvPlanRec), C.POINTER(_sz), C.POINTER(_sz)]),
     "thip_test_solver_pin_gemv_plan": (_i, [_vp, _i]),
+    "thip_test_sweep_plan": (_i, [_sz, _sz, _sz, _i, _i, _i, _i, C.POINTER(SweepPlanRec), C.POINTER(SweepPlanRec), C.POINTER(_i)]),
+    "thip_test_solver_pin_sweep_plan": (_i, [_vp, _i]),
     "thip_prof_enable": (_i, [_i]),
     "thip_prof_read": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "thip_prof_read_psd": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -696,6 +696,32 @@ int thip_solver_sweep_plan(thip_solver *s, int *host_members, int *host_cols_per
     return 0;
 }
 
+// TEST HOOK (totsu_f32hip_test.h): a candidate geometry installed the way the plan autotune installs its pick
+int thip_test_solver_pin_sweep_plan(thip_solver *s, int candidate_index)
+{
+    THIP_NEED_INIT();
+    if (!s || !s->inited || candidate_index < -1)
+        return fail(THIP_E_INVALID, "null or uninitialised solver, or no such candidate geometry", __FILE__, __LINE__);
+    if (candidate_index >= 0) {
+        // looked up before anything changes: a refused pin leaves the plan in use as it is
+        SweepGeom cand[6];
+        if (s->op != A_DENSE || s->schedule != THIP_SCHED_SWEEP || (s->allreduce != nullptr) != s->col_shard || s->m == 0 || s->n == 0
+            || candidate_index >= sweep_offer(s, cand, nullptr))
+            return fail(THIP_E_INVALID, "the one-pass kernel does not offer this candidate geometry for the solver's matrix", __FILE__, __LINE__);
+    }
+    const int pin_before = s->sweep_pin;
+    s->sweep_pin = candidate_index;
+    s->sweep_state = 0;
+    THIP_RC(sweep_prepare(s));
+    if (candidate_index >= 0 && (s->sweep_state != 1 || s->sweep_pin != candidate_index)) {
+        // (the schedule is off for this solve: below thip_solver_set_sweep_min_bytes, THIP_SWEEP_OFF, a placement other than 8 x 32)
+        s->sweep_pin = pin_before;
+        s->sweep_state = 0;
+        return fail(THIP_E_INVALID, "the one-pass schedule does not run for this solver: nothing to pin", __FILE__, __LINE__);
+    }
+    return 0;
+}
+
 int thip_prof_enable(int on)
 {
     THIP_NEED_INIT();

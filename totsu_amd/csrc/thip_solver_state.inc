@@ -119,6 +119,7 @@ struct thip_solver {
     float *sw_partH = nullptr; unsigned long long *sw_gran = nullptr; unsigned *sw_census = nullptr;
     float *sw_part = nullptr;     // 8 * EG block partials
     unsigned sw_seq = 0, sw_tag = 0;
+    int sweep_pin = -1;           // thip_test_solver_pin_sweep_plan: the candidate geometry to install untimed (-1: the library's choice)
     float sw_plan_ms = 0.0f;      // the chosen geometry's time per sweep as measured by the plan autotune (0: not tuned)
     // column-sharded sweep (thip_solver_set_column_shard): this rank holds a block of COLUMNS of A (all m rows), the
     // n-vectors are its block, the m-vectors are replicated; one all-reduce per iteration of cs_buf = [A u (mpad) ;

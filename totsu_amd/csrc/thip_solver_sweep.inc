@@ -33,6 +33,19 @@ int spt_buffers(thip_solver *s)
     return 0;
 }
 
+// the rows the kernel sweeps on the stored form of A in use (a library-owned copy has zero rows behind row m, and every m-vector of
+// the arena has zeros behind entry m) and the geometries it offers there (THIP_SWEEP_CLASS pins one); how many
+int sweep_offer(const thip_solver *s, SweepGeom *cand, size_t *m_eff_out)
+{
+    const DenseA A = s->sa.in_use();              // f32, or the 16-bit form the iteration streams now
+    const size_t epv = A.vec_elems();
+    const size_t m_up = (s->m + epv - 1) / epv * epv;
+    const size_t m_eff = (A.pad_zero && A.lda >= m_up) ? m_up : s->m;
+    if (m_eff_out) *m_eff_out = m_eff;
+    if (getenv("THIP_SWEEP_CLASS")) return sweep_plan(m_eff, s->n, A, &cand[0]) == 0 ? 1 : 0;
+    return sweep_candidates(m_eff, s->n, A, cand, 6);
+}
+
 int sweep_prepare(thip_solver *s)
 {
     if (s->op == A_TILED) {
@@ -62,20 +75,21 @@ int sweep_prepare(thip_solver *s)
     if (env_off) return 0;
     const DenseA A = s->sa.in_use();              // f32, or the 16-bit form the iteration streams now
     const int elem = A.kind;
-    const size_t esize = A.elem_bytes(), epv = A.vec_elems();
-    // a library-owned copy has zero rows behind row m, and every m-vector of the arena has zeros behind entry m
-    const size_t m_up = (s->m + epv - 1) / epv * epv;
-    const size_t m_eff = (A.pad_zero && A.lda >= m_up) ? m_up : s->m;
+    const size_t esize = A.elem_bytes();
     if (!s->col_shard && s->m * s->n * esize < s->sweep_min_bytes) return 0;
     // how the partial dots are published in this process: decided HERE, at plan time (the self-test allocates 64 MB and
     // synchronises; left to the first sweep_pass it ran in the middle of the first batch when the autotune is off)
     (void)sweep_publish_default();
-    // the geometries the kernel offers for this matrix (group size, columns per panel); THIP_SWEEP_CLASS pins one
+    // the geometries the kernel offers for this matrix (group size, columns per panel)
     SweepGeom cand[6];
-    int nc = 0;
-    if (getenv("THIP_SWEEP_CLASS")) { if (sweep_plan(m_eff, s->n, A, &cand[0]) == 0) nc = 1; }
-    else nc = sweep_candidates(m_eff, s->n, A, cand, 6);
+    size_t m_eff = 0;
+    int nc = sweep_offer(s, cand, &m_eff);
     if (nc == 0) return 0;
+    // TEST HOOK (thip_test_solver_pin_sweep_plan): that candidate alone, installed untimed.  A pin the matrix no longer offers (the
+    // stored form changed under it) is dropped
+    if (s->sweep_pin >= nc) s->sweep_pin = -1;
+    const bool pinned = s->sweep_pin >= 0;
+    if (pinned) { cand[0] = cand[s->sweep_pin]; nc = 1; }
     hipStream_t st = ctx().stream;
     if (!s->sw_census) {
         THIP_TRY(hipMalloc((void **)&s->sw_census, 64 * sizeof(unsigned)));
@@ -104,7 +118,7 @@ int sweep_prepare(thip_solver *s)
     SweepGeom g = cand[0];
     s->sw_plan_ms = 0.0f;
     const char *env_at = getenv("THIP_GEMV_AUTOTUNE");
-    const bool tune = !(s->autotune == 0 || (s->autotune < 0 && env_at && atoi(env_at) == 0));
+    const bool tune = !pinned && !(s->autotune == 0 || (s->autotune < 0 && env_at && atoi(env_at) == 0));
     if (tune) {
         // time every geometry on the actual matrix, like the GEMV plans: idempotent sweeps (first = 1: u stays, x_x goes
         // to the buffer that is not the iterate, gP is rewritten with what it has to hold anyway); one warm-up, five timed

@@ -74,13 +74,18 @@ int sweep_class()
 
 // One candidate geometry: W columns per panel (1 or 2: the two families of kernel instances), the smallest group size
 // the family's row capacity allows times gmul.  0 when the kernel can take the matrix that way.
-static int sweep_plan_one(size_t m, size_t n, const DenseA &A, int W, int gmul, SweepGeom *g, int force_G = 0)
+// exact (thip_test_sweep's pin, thip_test_sweep_plan): force_G is THE group size -- any power of two up to 32 whose members' rows
+// fit the family, also one below what the few-columns rule would raise it to (the kernel runs groups without columns; the rule is
+// there so that no workgroup idles).  num_cu < 0: this device's.
+static int sweep_plan_one(size_t m, size_t n, const DenseA &A, int W, int gmul, SweepGeom *g, int force_G = 0, bool exact = false,
+                          int num_cu = -1)
 {
     const int elem = A.kind;
     const size_t epv = A.vec_elems();                // rows per 16-byte slot
     if (m == 0 || n == 0 || m % epv != 0 || !A.vec_ok()) return 1;
-    if (n > ((size_t)1 << 30) || n < (size_t)40 * W) return 1;
-    if (ctx().num_cu != 256) return 1;
+    if (W != 1 && W != 2 && W != 4) return 1;
+    if (m > 0x7fffffffull || n > ((size_t)1 << 30) || n < (size_t)40 * W) return 1;
+    if ((num_cu < 0 ? ctx().num_cu : num_cu) != 256) return 1;
     const size_t slot_rows = (size_t)SW_CT * epv;
     // slots per streaming thread a kernel instance exists for: f32 1 .. 7 (one column per panel) / 1 .. 2 (two); 16-bit
     // storage keeps twice the rows per slot in registers (v, x_y, two accumulators: 32 VGPRs per slot): 1 .. 4 / 3 / 2
@@ -89,14 +94,19 @@ static int sweep_plan_one(size_t m, size_t n, const DenseA &A, int W, int gmul, 
     const size_t cap = slot_rows * max_slots;
     auto rows_of = [&](int G_) { return ((m + G_ - 1) / G_ + epv - 1) / epv * epv; };
     int G = 1;
-    while (G < 32 && rows_of(G) > cap) G *= 2;
-    if (rows_of(G) > cap) return 1;
-    for (int k = 1; k < gmul; k *= 2) { if (G >= 32) return 1; G *= 2; }
-    // few columns: fewer, larger groups, so that every group has its 40 panels and no workgroup idles
-    while (G < 32 && (size_t)(256 / G) * 40 * W > n) { if (gmul > 1) return 1; G *= 2; }
-    if (force_G) {          // thip_test_sweep: a given group size (a power of two the rows fit)
-        if (force_G < G || force_G > 32 || (force_G & (force_G - 1)) != 0) return 1;
+    if (exact) {
+        if (force_G < 1 || force_G > 32 || (force_G & (force_G - 1)) != 0 || rows_of(force_G) > cap) return 1;
         G = force_G;
+    } else {
+        while (G < 32 && rows_of(G) > cap) G *= 2;
+        if (rows_of(G) > cap) return 1;
+        for (int k = 1; k < gmul; k *= 2) { if (G >= 32) return 1; G *= 2; }
+        // few columns: fewer, larger groups, so that every group has its 40 panels and no workgroup idles
+        while (G < 32 && (size_t)(256 / G) * 40 * W > n) { if (gmul > 1) return 1; G *= 2; }
+        if (force_G) {          // thip_test_sweep: a given group size (a power of two the rows fit)
+            if (force_G < G || force_G > 32 || (force_G & (force_G - 1)) != 0) return 1;
+            G = force_G;
+        }
     }
     const size_t rpm = rows_of(G);
     const int ngroups = 256 / G;
@@ -139,7 +149,7 @@ int sweep_plan(size_t m, size_t n, const DenseA &A, SweepGeom *g)
 }
 
 // the geometries worth timing on a given matrix (thip_solver.hip times them on the actual matrix, like the GEMV plans)
-int sweep_candidates(size_t m, size_t n, const DenseA &A, SweepGeom *out, int max_out)
+static int sweep_candidates_on(size_t m, size_t n, const DenseA &A, SweepGeom *out, int max_out, int num_cu)
 {
     static const int cand32[6][2] = { { 1, 1 }, { 1, 2 }, { 1, 4 }, { 2, 1 }, { 2, 2 }, { 1, 8 } };
     // (16-bit: one column per panel first since the interval's sums are DPP adds -- before, two columns were the safer default)
@@ -148,12 +158,16 @@ int sweep_candidates(size_t m, size_t n, const DenseA &A, SweepGeom *out, int ma
     int k = 0;
     for (int c = 0; c < 6 && k < max_out; ++c) {
         SweepGeom g;
-        if (sweep_plan_one(m, n, A, cand[c][0], cand[c][1], &g) != 0) continue;
+        if (sweep_plan_one(m, n, A, cand[c][0], cand[c][1], &g, 0, false, num_cu) != 0) continue;
         bool dup = false;
         for (int j = 0; j < k; ++j) dup = dup || (out[j].G == g.G && out[j].w == g.w && out[j].nslot == g.nslot);
         if (!dup) out[k++] = g;
     }
     return k;
+}
+int sweep_candidates(size_t m, size_t n, const DenseA &A, SweepGeom *out, int max_out)
+{
+    return sweep_candidates_on(m, n, A, out, max_out, -1);
 }
 
 // the ring of every group + one spare 128-byte line per workgroup (the service wave's unconditional stores, thip_sweep_kernel.h)
@@ -221,6 +235,11 @@ static int run_test_sweep(const thip_sweep_test *t, int spin_max, float *host_ms
     // (f32: variant 12 = two columns per panel)
     const int w16 = t->elem ? ((t->variant == 1 || t->variant == 2 || t->variant == 4) ? t->variant : 0) : (t->variant == 12 ? 2 : 0);
     const DenseA A{ t->mat_a, t->lda, t->elem, t->inv_s, false };
+    if (t->pin_g != 0) {
+        // the exact geometry: pin_w columns per panel, pin_g members per group, or nothing is launched
+        if (!t->mat_a || t->lda < t->m || sweep_plan_one(t->m, t->n, A, t->pin_w, 1, &g, t->pin_g, true) != 0)
+            return fail(THIP_E_INVALID, "the one-pass kernel has no instance for the pinned geometry on this shape", __FILE__, __LINE__);
+    } else
     if (w16 ? sweep_plan_one(t->m, t->n, A, w16, 1, &g, t->force_members) != 0
         : (t->force_members > 0 ? sweep_plan_one(t->m, t->n, A, t->elem ? 2 : 1, 1, &g, t->force_members)
                                 : sweep_plan(t->m, t->n, A, &g)) != 0)
@@ -286,7 +305,7 @@ static int run_test_sweep(const thip_sweep_test *t, int spin_max, float *host_ms
     if (host_ms) { host_ms[0] = best; host_ms[1] = tot / reps; }
     if (host_info) {
         host_info[0] = (int)hc[9]; host_info[1] = g.G; host_info[2] = g.ngroups; host_info[3] = g.npan; host_info[4] = g.nslot;
-        host_info[5] = (int)hc[18]; host_info[6] = (int)hc[19];
+        host_info[5] = (int)hc[18]; host_info[6] = (int)hc[19]; host_info[7] = g.w;
     }
 #ifdef SW_PROFILE
     fprintf(stderr, "service wave, 10 ns ticks: wait %u, cold+publish %u, tags+poll %u, reduce+math+stores %u, loads %u, barrier %u; intervals that polled %u, polls %u\n",
@@ -305,6 +324,36 @@ extern "C" int thip_test_sweep(const thip_sweep_test *t, float *host_ms, int *ho
 {
     THIP_NEED_INIT();
     return run_test_sweep(t, SW_SPIN_MAX, host_ms, host_info);
+}
+
+// the planning alone (totsu_f32hip_test.h): no GPU, no thip_init -- a device of 256 CUs is assumed
+static void sweep_plan_record(const SweepGeom &g, thip_sweep_plan_rec *r)
+{
+    r->members = g.G; r->ngroups = g.ngroups; r->rows_per_member = g.rows_per_member; r->cols_per_group = g.cols_per_group;
+    r->npan = g.npan; r->nslot = g.nslot; r->cols_per_panel = g.w; r->elem = g.elem;
+    r->mpad = g.mpad; r->gran_words = sweep_gran_words(g);
+}
+
+extern "C" int thip_test_sweep_plan(size_t m, size_t n, size_t lda, int elem, int cols_per_panel, int gmul, int force_members,
+                                    thip_sweep_plan_rec *host_plan, thip_sweep_plan_rec *host_candidates, int *host_n_candidates)
+{
+    if (elem < 0 || elem > THIP_A_F16 || gmul < 1 || force_members < 0 || lda < m)
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    // (the matrix itself is not needed: any 16-byte aligned address stands for it)
+    const DenseA A{ reinterpret_cast<const void *>((uintptr_t)4096), lda, elem, nullptr, false };
+    if (host_candidates || host_n_candidates) {
+        SweepGeom cand[6];
+        const int nc = sweep_candidates_on(m, n, A, cand, 6, 256);
+        if (host_candidates) for (int c = 0; c < nc; ++c) sweep_plan_record(cand[c], host_candidates + c);
+        if (host_n_candidates) *host_n_candidates = nc;
+    }
+    if (host_plan) {
+        SweepGeom g;
+        if (sweep_plan_one(m, n, A, cols_per_panel, gmul, &g, force_members, force_members > 0, 256) != 0)
+            return fail(THIP_E_INVALID, "the one-pass kernel has no instance for this geometry on this shape", __FILE__, __LINE__);
+        sweep_plan_record(g, host_plan);
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------

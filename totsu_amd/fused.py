@@ -342,6 +342,11 @@ class FusedSolver:
         return {"workgroups_per_column_group": g.value, "columns_per_panel": w.value, "slots_per_thread": sl.value,
                 "autotune_ms_per_sweep": ms.value}
 
+    def pin_sweep_plan(self, candidate_index):
+        """TEST HOOK (thip_test_solver_pin_sweep_plan): the one-pass kernel's geometry for the stored form in use becomes the
+        candidate_index-th of the geometries the plan autotune would time (-1: the library's choice again); before the first run"""
+        lib.thip_test_solver_pin_sweep_plan(self.h, int(candidate_index))
+
     def set_sweep_min_bytes(self, nbytes):
         lib.thip_solver_set_sweep_min_bytes(self.h, int(nbytes))
 
