@@ -152,7 +152,7 @@ typedef struct thip_gemv_plan_rec {
     int32_t chunks2, cols_per_chunk2, reserved;
 } thip_gemv_plan_rec;
 
-#define THIP_TEST_E_GUARD 10901   /* thip_test_dual_gemv: a word behind the partial-sum scratch changed */
+#define THIP_TEST_E_GUARD 10901   /* thip_test_dual_gemv, thip_test_dual_gemv_multi: a word behind the partial-sum scratch changed */
 
 /* test entry point of the single-vector dual GEMV (thip_gemv.hip; tests/test_gpu_gemv_tilings.py): ONE pinned instance of the kernel
  * alone, its partial sums finished into out_n = A xn (m floats) and / or out_t = A^T xt (n floats), all on the device.
@@ -185,6 +185,45 @@ int thip_test_dual_gemv(const thip_gemv_test *t, thip_gemv_plan_rec *host_plan);
  * columns (0: it does not).  m_load is that of a matrix whose rows below m are not known to be zeros. */
 int thip_test_gemv_plan(size_t m, size_t n, int vw, int nj, int target_blocks, size_t col0, size_t col1,
                         thip_gemv_plan_rec *host_plan, size_t *host_scratch_floats, size_t *host_split_col);
+
+/* The planning of the multi-vector dual GEMV with nothing launched (needs no GPU and no thip_init): the plan the kernel instance
+ * NV = `instance` (2, 4 or 8) runs an m x n matrix under with the hint (nj, target_blocks) (0 / 0: none) -- vw = 4, nj (1 on NV = 8
+ * whatever the hint), ku = 8 / nj, tiles, chunks, cols_per_chunk, m_load = m rounded up to 4 -- and the floats
+ * dual_gemv_multi_scratch_floats(m, n) reserves per slot for any plan's partial sums.  THIP_E_INVALID: m or n = 0, an instance other
+ * than 2, 4, 8, a negative hint.  Either pointer may be NULL. */
+int thip_test_gemv_multi_plan(size_t m, size_t n, int instance, int nj, int target_blocks, thip_gemv_plan_rec *host_plan,
+                              size_t *host_scratch_floats);
+
+/* test entry point of the multi-vector dual GEMV (thip_gemv_multi.hip; tests/test_gpu_gemv_multi_tilings.py), the analogue of
+ * thip_test_dual_gemv: ONE pinned launch alone, its partial sums finished into out_n[i] = A xn[i] (m floats) and out_t[i] = A^T xt[i]
+ * (n floats) for the slots i < nv that are not stopped.
+ *   mat: device, column-major, lda = m, 16-byte aligned; streamed from a zero-padded copy when m % 16 != 0, exactly as the batch does;
+ *   nv = 2 .. 8; xn, xt, out_n, out_t: HOST arrays of nv DEVICE pointers; stopped (may be NULL): nv flags on the host -- slot i's stop
+ *     flag is set, its outputs are left as they are (all set: the kernel returns at entry);
+ *   nj, target_blocks >= 0: the tiling hint, any values (0 / 0: none -- the shape heuristic).
+ * Every slot's scratch has the batch's own size (the larger of the single-vector and the multi-vector scratch), is filled with NaNs
+ * beforehand (a sum that is consumed but was never written shows in the result) and has a guard tail behind it: THIP_TEST_E_GUARD when
+ * a tail changed; the padded copy has a tile of NaNs behind it.  THIP_E_INVALID, nothing launched: nv outside 2 .. 8, a null pointer, m or n = 0, a negative hint, a misaligned mat,
+ * more column chunks than a launch takes.  *host_plan (may be NULL): the plan that ran (zeros: nothing ran). */
+typedef struct thip_gemv_multi_test {
+    size_t m, n;
+    const float *mat;
+    int32_t nv, nj, target_blocks, reserved;
+    const float *const *xn, *const *xt;
+    float *const *out_n, *const *out_t;
+    const int32_t *stopped;
+} thip_gemv_multi_test;
+int thip_test_dual_gemv_multi(const thip_gemv_multi_test *t, thip_gemv_plan_rec *host_plan);
+
+/* TEST HOOK: pins the tiling of the multi-vector kernel instance NV = `instance` (2, 4 or 8) of a batch to the candidate_index-th of
+ * the plans its autotune times (gemv_multi_candidates), as if the autotune had picked it; -1: back to untuned (the shape heuristic).
+ * After thip_batch_init, before the first run.  THIP_E_INVALID: an index out of range, or a candidate with two row groups per lane for
+ * NV = 8, which the autotune never picks. */
+int thip_test_batch_pin_multi_plan(thip_batch *b, int instance, int candidate_index);
+
+/* TEST HOOK: the plan the most recent multi-vector launch of the kernel instance NV = `instance` of this batch ran under (zeros: that
+ * instance has not been launched). */
+int thip_test_batch_last_multi_plan(const thip_batch *b, int instance, thip_gemv_plan_rec *host_plan);
 
 /* TEST HOOK: pins the tiling of the dual GEMV for the stored form of A and the launch form (one launch per pass, or the column-split
  * pipeline) the next thip_solver_run will use to the candidate_index-th of the plans the autotune times, as if the autotune had picked

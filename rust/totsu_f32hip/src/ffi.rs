@@ -132,6 +132,16 @@ pub struct thip_gemv_test {
     pub col_split: usize,
 }
 
+#[repr(C)]
+pub struct thip_gemv_multi_test {
+    pub m: usize, pub n: usize,
+    pub mat: *const f32,
+    pub nv: i32, pub nj: i32, pub target_blocks: i32, pub reserved: i32,
+    pub xn: *const *const f32, pub xt: *const *const f32,
+    pub out_n: *const *mut f32, pub out_t: *const *mut f32,
+    pub stopped: *const i32,
+}
+
 pub enum thip_solver {}
 pub enum thip_batch {}
 pub enum thip_smallbatch {}
@@ -458,6 +468,11 @@ extern "C" {
     pub fn thip_test_gemv_plan(m: usize, n: usize, vw: c_int, nj: c_int, target_blocks: c_int, col0: usize, col1: usize,
                                host_plan: *mut thip_gemv_plan_rec, host_scratch_floats: *mut usize, host_split_col: *mut usize) -> c_int;
     pub fn thip_test_solver_pin_gemv_plan(s: *mut thip_solver, candidate_index: c_int) -> c_int;
+    pub fn thip_test_gemv_multi_plan(m: usize, n: usize, instance: c_int, nj: c_int, target_blocks: c_int,
+                                     host_plan: *mut thip_gemv_plan_rec, host_scratch_floats: *mut usize) -> c_int;
+    pub fn thip_test_dual_gemv_multi(t: *const thip_gemv_multi_test, host_plan: *mut thip_gemv_plan_rec) -> c_int;
+    pub fn thip_test_batch_pin_multi_plan(b: *mut thip_batch, instance: c_int, candidate_index: c_int) -> c_int;
+    pub fn thip_test_batch_last_multi_plan(b: *const thip_batch, instance: c_int, host_plan: *mut thip_gemv_plan_rec) -> c_int;
     pub fn thip_test_spin_allreduce(s: *mut thip_solver, latency_us: c_int) -> c_int;
     pub fn thip_test_sweep(t: *const thip_sweep_test, host_ms: *mut f32, host_info: *mut c_int) -> c_int;
     pub fn thip_test_sweep_plan(m: usize, n: usize, lda: usize, elem: c_int, cols_per_panel: c_int, gmul: c_int, force_members: c_int,

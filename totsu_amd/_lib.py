@@ -112,6 +112,12 @@ class GemvTest(C.Structure):
                [(k, C.c_int32) for k in ("do_n", "do_t", "abs_mode", "nj", "target_blocks", "stopped")] + [("col_split", C.c_size_t)]
 
 
+class GemvMultiTest(C.Structure):
+    _fields_ = [("m", C.c_size_t), ("n", C.c_size_t), ("mat", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("nv", "nj", "target_blocks", "reserved")] + \
+               [(k, C.POINTER(C.c_void_p)) for k in ("xn", "xt", "out_n", "out_t")] + [("stopped", C.POINTER(C.c_int32))]
+
+
 TEST_E_GUARD = 10901
 BATCH_MAX, BATCH_GROUP_DEFAULT = 64, 8
 SMALLBATCH_MAX_DIM, SMALLBATCH_MAX_AREA, SMALLBATCH_MAX_PROB, SMALLBATCH_LDS_MAX = 1024, 24576, 1048576, 163840
@@ -266,6 +272,10 @@ PROTOTYPES = {
     "thip_test_dual_gemv": (_i, [C.POINTER(GemvTest), C.POINTER(GemvPlanRec)]),
     "thip_test_gemv_plan": (_i, [_sz, _sz, _i, _i, _i, _sz, _sz, C.POINTER(GemvPlanRec), C.POINTER(_sz), C.POINTER(_sz)]),
     "thip_test_solver_pin_gemv_plan": (_i, [_vp, _i]),
+    "thip_test_gemv_multi_plan": (_i, [_sz, _sz, _i, _i, _i, C.POINTER(GemvPlanRec), C.POINTER(_sz)]),
+    "thip_test_dual_gemv_multi": (_i, [C.POINTER(GemvMultiTest), C.POINTER(GemvPlanRec)]),
+    "thip_test_batch_pin_multi_plan": (_i, [_vp, _i, _i]),
+    "thip_test_batch_last_multi_plan": (_i, [_vp, _i, C.POINTER(GemvPlanRec)]),
     "thip_test_sweep_plan": (_i, [_sz, _sz, _sz, _i, _i, _i, _i, C.POINTER(SweepPlanRec), C.POINTER(SweepPlanRec), C.POINTER(_i)]),
     "thip_test_solver_pin_sweep_plan": (_i, [_vp, _i]),
     "thip_prof_enable": (_i, [_i]),

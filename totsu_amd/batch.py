@@ -262,6 +262,18 @@ class BatchSolver:
                       for q, nv in ((1, 2), (2, 4), (3, 8))}
         return d
 
+    def pin_multi_plan(self, instance, candidate_index):
+        """TEST HOOK (thip_test_batch_pin_multi_plan): the tiling of the multi-vector kernel instance NV = 2, 4 or 8 pinned to a
+        candidate of its autotune (-1: untuned again); after init, before the first run"""
+        lib.thip_test_batch_pin_multi_plan(self.h, int(instance), int(candidate_index))
+
+    def last_multi_plan(self, instance):
+        """TEST HOOK (thip_test_batch_last_multi_plan): the plan record of the latest launch of that kernel instance, as a dict
+        (all zeros: not launched yet)"""
+        rec = _lib.GemvPlanRec()
+        lib.thip_test_batch_last_multi_plan(self.h, int(instance), C.byref(rec))
+        return {k: getattr(rec, k) for k, _ in rec._fields_}
+
     def solve(self, poll_every=16):
         """Solver::solve semantics per instance: the list of (x, y), or a SolverError for an instance that did not converge"""
         out = []

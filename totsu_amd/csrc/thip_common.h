@@ -237,7 +237,7 @@ int finalize_partials(hipStream_t st, size_t n, const float *part, int np, size_
 // that share A).  Slot i: xn[i] (n_col) / xt[i] (n_row) in, its partial sums into scratch[i] (scratch_floats each) as out[i] describes;
 // stop[i] (may be NULL) != 0: the slot is skipped; the launch returns at entry once every slot is stopped.  The kernel instances are
 // NV = 2, 4, 8: nv runs on the smallest that holds it, the unused slots multiply nothing.  A must allow whole 16-byte loads
-// (DenseA::vec_ok, and n_row % 4 == 0 or pad_zero).
+// (DenseA::vec_ok, and n_row % 4 == 0 or pad_zero).  plan_out (may be NULL): the plan the launch ran under, for the test hooks.
 constexpr int GEMV_MULTI_MAX = 8;
 struct MultiTab { const float *xn[GEMV_MULTI_MAX]; const float *xt[GEMV_MULTI_MAX]; float *scr[GEMV_MULTI_MAX]; const int *stop[GEMV_MULTI_MAX]; };
 int gemv_multi_instance(int nv);                              // 1 (the single-vector kernel), 2, 4 or 8
@@ -245,7 +245,7 @@ const GemvHint *gemv_multi_candidates(int *count);            // plans worth tim
 size_t dual_gemv_multi_scratch_floats(size_t n_row, size_t n_col);      // per slot, whatever the plan
 int dual_gemv_multi_partials(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A, int nv, const float *const *xn,
                              const float *const *xt, float *const *scratch, size_t scratch_floats, const int *const *stop,
-                             GemvPartials *out, const GemvHint *hint = nullptr);
+                             GemvPartials *out, const GemvHint *hint = nullptr, thip_gemv_plan_rec *plan_out = nullptr);
 
 // thip_sweep.hip: one pass over A per iteration (THIP_SCHED_SWEEP)
 constexpr int SW_SPIN_MAX = 2000000;       // polls of a gather before a workgroup gives up (~2-4 s)

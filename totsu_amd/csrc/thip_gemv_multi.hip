@@ -20,6 +20,7 @@
 #include "thip_gemv_reduce.h"
 
 #include <algorithm>
+#include <vector>
 
 using namespace thip;
 
@@ -183,6 +184,16 @@ MPlan multi_plan(size_t n_row, size_t n_col, int inst, const GemvHint *hint)
     return p;
 }
 
+// the plan as the test hooks report it (thip_gemv_plan_rec: rows per load, row groups per lane, columns per unrolled step, the grid)
+void multi_plan_record(const MPlan &p, thip_gemv_plan_rec *r)
+{
+    *r = thip_gemv_plan_rec{};
+    r->vw = VW; r->nj = p.nj; r->ku = 8 / p.nj; r->tiles = p.tiles; r->chunks = p.chunks; r->cols_per_chunk = p.cpc;
+    r->m_load = p.m_load;
+}
+
+bool multi_dims_ok(size_t n_row, size_t n_col) { return n_row <= 0x7fffffffull - 8192 && n_col <= 0x7fffffffull; }
+
 }  // namespace
 
 namespace thip {
@@ -215,12 +226,12 @@ size_t dual_gemv_multi_scratch_floats(size_t n_row, size_t n_col)
 
 int dual_gemv_multi_partials(hipStream_t st, size_t n_row, size_t n_col, const DenseA &A, int nv, const float *const *xn,
                              const float *const *xt, float *const *scratch, size_t scratch_floats, const int *const *stop,
-                             GemvPartials *out, const GemvHint *hint)
+                             GemvPartials *out, const GemvHint *hint, thip_gemv_plan_rec *plan_out)
 {
     if (nv < 2 || nv > GEMV_MULTI_MAX) return fail(THIP_E_INVALID, "a multi-vector launch takes 2 .. 8 vector pairs", __FILE__, __LINE__);
     for (int i = 0; i < nv; ++i) out[i] = GemvPartials{};
     if (n_row == 0 || n_col == 0) return 0;
-    if (n_row > 0x7fffffffull - 8192 || n_col > 0x7fffffffull) return fail(THIP_E_INVALID, "matrix dimension > 2^31", __FILE__, __LINE__);
+    if (!multi_dims_ok(n_row, n_col)) return fail(THIP_E_INVALID, "matrix dimension > 2^31", __FILE__, __LINE__);
     if (A.kind != THIP_A_F32 || !A.vec_ok() || A.lda < n_row)
         return fail(THIP_E_INVALID, "the multi-vector product streams an f32 matrix with 16-byte aligned columns", __FILE__, __LINE__);
     if (n_row % VW != 0 && !(A.pad_zero && A.lda >= round_up(n_row, VW)))
@@ -248,6 +259,7 @@ int dual_gemv_multi_partials(hipStream_t st, size_t n_row, size_t n_col, const D
     else THIP_MULTI_LAUNCH(8, 1, 8);
 #undef THIP_MULTI_LAUNCH
     THIP_LAUNCH_CHECK();
+    if (plan_out) multi_plan_record(p, plan_out);
     return 0;
 }
 
@@ -318,6 +330,97 @@ int thip_test_gemv_multi(size_t m, size_t n, const float *mat, int nv, const flo
     if (e1) hipEventDestroy(e1);
     hipFree(pad); hipFree(scr); hipFree(flags);
     if (host_ms) *host_ms = best;
+    return rc;
+}
+
+// TEST HOOK (totsu_f32hip_test.h): the planning of the multi-vector kernel with nothing launched
+int thip_test_gemv_multi_plan(size_t m, size_t n, int instance, int nj, int target_blocks, thip_gemv_plan_rec *host_plan,
+                              size_t *host_scratch_floats)
+{
+    if (m == 0 || n == 0 || !multi_dims_ok(m, n) || !(instance == 2 || instance == 4 || instance == 8) || nj < 0 || target_blocks < 0)
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    const GemvHint hint{ nj, target_blocks };
+    const MPlan p = multi_plan(m, n, instance, (nj > 0 || target_blocks > 0) ? &hint : nullptr);
+    if (host_plan) multi_plan_record(p, host_plan);
+    if (host_scratch_floats) *host_scratch_floats = dual_gemv_multi_scratch_floats(m, n);
+    return 0;
+}
+
+// TEST HOOK (totsu_f32hip_test.h): one pinned launch of the multi-vector kernel alone, every slot's scratch the batch's own size,
+// NaNs beforehand and a guard tail behind it
+int thip_test_dual_gemv_multi(const thip_gemv_multi_test *t, thip_gemv_plan_rec *host_plan)
+{
+    THIP_NEED_INIT();
+    if (host_plan) *host_plan = thip_gemv_plan_rec{};
+    if (!t || !t->mat || !t->xn || !t->xt || !t->out_n || !t->out_t || t->nv < 2 || t->nv > GEMV_MULTI_MAX || t->m == 0 || t->n == 0
+        || !multi_dims_ok(t->m, t->n) || t->nj < 0 || t->target_blocks < 0 || ((uintptr_t)t->mat & 15u) != 0)
+        return fail(THIP_E_INVALID, "bad argument", __FILE__, __LINE__);
+    const int nv = t->nv;
+    for (int i = 0; i < nv; ++i)
+        if (!t->xn[i] || !t->xt[i] || !t->out_n[i] || !t->out_t[i])
+            return fail(THIP_E_INVALID, "null vector in a multi-vector launch", __FILE__, __LINE__);
+    const size_t m = t->m, n = t->n;
+    const GemvHint hint{ t->nj, t->target_blocks };
+    const GemvHint *h = (t->nj > 0 || t->target_blocks > 0) ? &hint : nullptr;
+    // the batch's own allocation per slot (batch_create_impl) -- what the launch is about to need is refused here, not after it
+    const size_t per = std::max(dual_gemv_scratch_floats(m, n), dual_gemv_multi_scratch_floats(m, n));
+    {
+        const MPlan p = multi_plan(m, n, gemv_multi_instance(nv), h);
+        if (p.chunks > 65535) return fail(THIP_E_INVALID, "too many column chunks for one launch", __FILE__, __LINE__);
+        if ((size_t)p.chunks * p.strideN + (size_t)p.tiles * p.strideT > per) return fail(THIP_E_WORK, "gemv scratch too small", __FILE__, __LINE__);
+    }
+    constexpr size_t GUARD = 256, PAD_TAIL = 2 * BLK * VW;
+    constexpr unsigned NAN_WORD = 0x7fc00abcu, GUARD_WORD = 0x5a5a5a5au;
+    const size_t slot = round_up(per, 4) + GUARD;          // [0, per) the scratch, [per, slot) its guard tail
+    hipStream_t st = ctx().stream;
+    float *pad = nullptr, *scr = nullptr;
+    int *flags = nullptr;
+    DenseA A = dense_f32(t->mat, m);
+    thip_gemv_plan_rec rec{};
+    // (one exit: everything allocated here is released whatever fails)
+    auto body = [&]() -> int {
+        if (m % 16 != 0) {
+            // the stored form the batch object streams, with a tile of NaNs behind it: a load that strays past the copy stays inside
+            // this allocation and shows in the result
+            const size_t ld = round_up(m, 16);
+            THIP_TRY(hipMalloc((void **)&pad, (ld * n + PAD_TAIL) * sizeof(float)));
+            THIP_TRY(hipMemsetAsync(pad, 0, ld * n * sizeof(float), st));
+            THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(pad + ld * n), (int)NAN_WORD, PAD_TAIL, st));
+            THIP_TRY(hipMemcpy2DAsync(pad, ld * sizeof(float), t->mat, m * sizeof(float), m * sizeof(float), n, hipMemcpyDeviceToDevice, st));
+            A = DenseA{ pad, ld, THIP_A_F32, nullptr, true };
+        }
+        THIP_TRY(hipMalloc((void **)&scr, slot * nv * sizeof(float)));
+        THIP_TRY(hipMalloc((void **)&flags, GEMV_MULTI_MAX * sizeof(int)));
+        int hf[GEMV_MULTI_MAX] = { 0 };
+        float *scrs[GEMV_MULTI_MAX];
+        const int *stops[GEMV_MULTI_MAX];
+        GemvPartials gp[GEMV_MULTI_MAX];
+        for (int i = 0; i < nv; ++i) {
+            hf[i] = (t->stopped && t->stopped[i]) ? 1 : 0;
+            scrs[i] = scr + (size_t)i * slot; stops[i] = flags + i;
+            THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)scrs[i], (int)NAN_WORD, per, st));
+            THIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(scrs[i] + per), (int)GUARD_WORD, slot - per, st));
+        }
+        THIP_TRY(hipMemcpyAsync(flags, hf, sizeof(hf), hipMemcpyHostToDevice, st));
+        THIP_RC(dual_gemv_multi_partials(st, m, n, A, nv, t->xn, t->xt, scrs, per, stops, gp, h, &rec));
+        for (int i = 0; i < nv; ++i) {
+            if (hf[i]) continue;          // a stopped slot leaves no sums: its outputs stay as they are
+            THIP_RC(finalize_partials(st, m, gp[i].partN, gp[i].nN, gp[i].strideN, 1.0f, 0.0f, t->out_n[i], nullptr));
+            THIP_RC(finalize_partials(st, n, gp[i].partT, gp[i].nT, gp[i].strideT, 1.0f, 0.0f, t->out_t[i], nullptr));
+        }
+        std::vector<unsigned> tail((slot - per) * nv);
+        for (int i = 0; i < nv; ++i)
+            THIP_TRY(hipMemcpyAsync(tail.data() + (size_t)i * (slot - per), scrs[i] + per, (slot - per) * sizeof(unsigned),
+                                    hipMemcpyDeviceToHost, st));
+        THIP_TRY(hipStreamSynchronize(st));
+        for (unsigned w : tail)
+            if (w != GUARD_WORD) return fail(THIP_TEST_E_GUARD, "a launch wrote behind a slot's gemv scratch", __FILE__, __LINE__);
+        return 0;
+    };
+    const int rc = body();
+    if (rc != 0) hipStreamSynchronize(st);
+    hipFree(pad); hipFree(scr); hipFree(flags);
+    if (host_plan) *host_plan = rec;
     return rc;
 }
 

@@ -22,6 +22,7 @@ struct thip_batch {
     float *rowabs = nullptr, *colabs = nullptr;
     size_t scr_floats = 0;               // GEMV scratch of every instance
     GemvPlan mplan[4];                   // tuned tilings of the multi-vector kernel, by instance: [1] NV = 2, [2] NV = 4, [3] NV = 8
+    thip_gemv_plan_rec last_mplan[4]{};  // what the latest launch of each instance ran under (thip_test_batch_last_multi_plan)
     int autotune = -1;                   // as thip_solver::autotune
     int max_group = THIP_BATCH_GROUP_DEFAULT;
     bool regroup = false;                // the launches follow the live set (thip_batch_set_regroup)
@@ -80,7 +81,8 @@ int batch_products(thip_batch *b, const int *idx, int members, int which, bool w
         scr[j] = s->gemv_scr; stop[j] = with_stop ? &s->dst->stop : nullptr;
     }
     prof_begin(st);
-    THIP_RC(dual_gemv_multi_partials(st, b->m, b->n, b->A(), members, xn, xt, scr, b->scr_floats, stop, gp, hint));
+    THIP_RC(dual_gemv_multi_partials(st, b->m, b->n, b->A(), members, xn, xt, scr, b->scr_floats, stop, gp, hint,
+                                     &b->last_mplan[plan_slot(gemv_multi_instance(members))]));
     prof_end(st);
     return 0;
 }
@@ -494,6 +496,28 @@ int thip_batch_info(const thip_batch *b, thip_batch_info_t *host_info)
         o.plan_blocks[q] = b->mplan[q].tuned ? b->mplan[q].hint.target_blocks : 0;
         o.plan_ms[q] = b->mplan[q].ms;
     }
+    return 0;
+}
+
+// TEST HOOK (totsu_f32hip_test.h): a candidate tiling of one kernel instance installed the way autotune_multi installs its pick
+int thip_test_batch_pin_multi_plan(thip_batch *b, int instance, int candidate_index)
+{
+    int nc = 0;
+    const GemvHint *c = gemv_multi_candidates(&nc);
+    if (!b || !b->inited || !(instance == 2 || instance == 4 || instance == 8) || candidate_index < -1 || candidate_index >= nc)
+        return fail(THIP_E_INVALID, "null or uninitialised batch, or no such instance or candidate plan", __FILE__, __LINE__);
+    if (candidate_index >= 0 && instance == 8 && c[candidate_index].nj != 1)
+        return fail(THIP_E_INVALID, "the NV = 8 instance holds one row group per lane: the autotune never picks this plan", __FILE__, __LINE__);
+    b->mplan[plan_slot(instance)] = candidate_index < 0 ? GemvPlan{} : GemvPlan{ c[candidate_index], true, 0.0f };
+    return 0;
+}
+
+// TEST HOOK (totsu_f32hip_test.h): the plan of the latest multi-vector launch of one kernel instance (zeros: none yet)
+int thip_test_batch_last_multi_plan(const thip_batch *b, int instance, thip_gemv_plan_rec *host_plan)
+{
+    if (!b || !host_plan || !(instance == 2 || instance == 4 || instance == 8))
+        return fail(THIP_E_INVALID, "null argument or no such instance", __FILE__, __LINE__);
+    *host_plan = b->last_mplan[plan_slot(instance)];
     return 0;
 }
 
