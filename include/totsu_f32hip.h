@@ -792,6 +792,77 @@ int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_col
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
 int thip_sparsebatch_destroy(thip_sparsebatch *h);
 
+/* ---------------------------------------------------------------------------------------------
+ * The RAGGED SPARSE batch: many conic programs in one batch, each with its own SPARSE A with its own pattern, its own n_p, m_p and
+ * its own cone layout (thip_raggedsparse.hip).  The ragged batch's lookup and the sparse batch's stored form together:
+ * one workgroup per running problem finds its problem in a table of descriptors and walks that problem's packed entries.  A
+ * problem's preconditioner, iterates and status are, bit for bit, those of a thip_sparsebatch that holds it alone at the same
+ * workgroup size.
+ * A problem is taken exactly when thip_sdpbatch_fits takes its (n_p, m_p, layout) and its capacity is at most m_p n_p.  Slot p
+ * reserves 16 cap_p + 4 (2 (m_p + n_p) + 4) bytes rounded up to 16 of the packed blobs; cap_p is the problem's own entry count unless
+ * host_nnz_cap gives more (NULL, or an entry of 0: the own count), so replace can hand the slot another pattern of at most cap_p
+ * entries.  The workgroup size is the sparse batch's rule on (n_p, m_p, cap_p): 256 threads when max(m_p, n_p) <= 1024 and
+ * cap_p <= 8192, else 1024 -- two classes, one launch per class and poll, a class's live list by descending entry count.  A problem
+ * is RESIDENT (its blob copied into LDS once per launch) exactly when the LDS map of thip_sdpbatch for it plus its capacity is at
+ * most 163 840 bytes -- per problem: resident and streamed members share a class and a launch -- and a class's LDS is the largest
+ * need of its members.  The state is packed, 6 n_p + 10 m_p floats each; identical layouts share one cone table.
+ * The arrays: the column pointers of all problems concatenated (n_p + 1 each, from 0), problem p's row indices and values the
+ * entries of host_rowidx / host_values from host_start[p] on; b, c and the row sums one device array per kind with per-problem
+ * offsets IN FLOATS, the cone segments concatenated, as in thip_raggedbatch_create.  Every problem's arrays are checked on the host
+ * (the refusals of thip_sparsebatch_create) before anything is allocated, and a refusal names the first problem refused.
+ * Lengths are the problem's own, as in the ragged batch.  1 <= n_prob <= 1 048 576.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_raggedsparse thip_raggedsparse;
+typedef struct thip_raggedsparse_class_t {
+    int32_t n_prob, live;             /* members; members RUNNING as of the last poll */
+    int32_t threads, lds_bytes;       /* of every workgroup of the class: 256 or 1024; the largest need of its members */
+    int64_t launches, workgroups;     /* issued by run / run_until_any since thip_raggedsparse_init */
+    int32_t n_resident, reserved;     /* members whose blob is read from LDS */
+} thip_raggedsparse_class_t;
+typedef struct thip_raggedsparse_info_t {
+    int32_t n_prob, live;
+    int32_t n_layouts, n_resident;    /* distinct (m, segments) tables; problems whose blob is read from LDS */
+    size_t  arena_bytes;              /* the problems' state, packed: 4 sum (6 n_p + 10 m_p) */
+    size_t  device_bytes;             /* everything this object allocated on the device, the blobs among it */
+    size_t  device_bytes_all;         /* the same, summed over every thip_raggedsparse alive in the process */
+    int64_t launches, workgroups;     /* summed over the classes */
+    size_t  a_bytes_per_iter;         /* bytes of A read from memory when every problem advances one iteration: twice the used
+                                         bytes of the blobs that are not resident */
+    int32_t max_psd_order, n_psd;     /* the largest PSD order of any problem; PSD cones, summed over the problems */
+    size_t  psd_lds_bytes;            /* the largest operand tail of any problem */
+    size_t  nnz_total;                /* entries held, summed over the slots */
+    size_t  blob_bytes;               /* the capacities the slots reserve, summed */
+    thip_raggedsparse_class_t cls[2]; /* the 256-thread class, the 1024-thread class */
+} thip_raggedsparse_info_t;
+/* the rules alone (needs no device): 0, or THIP_E_INVALID with the index of the first problem refused in *host_first_refused (-1:
+ * the refusal names no problem).  host_nnz_cap: the capacities (NULL: 0 entries each).  host_lds_bytes / host_threads /
+ * host_resident: n_prob entries, what one workgroup of the problem takes; each may be NULL */
+int thip_raggedsparse_fits(size_t n_prob, const size_t *host_n, const size_t *host_m, const size_t *host_nnz_cap,
+                           const size_t *host_n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                           int *host_first_refused, size_t *host_lds_bytes, int *host_threads, int *host_resident);
+int thip_raggedsparse_create(size_t n_prob, const size_t *host_n, const size_t *host_m, const int64_t *host_colptr,
+                             const int64_t *host_start, const int32_t *host_rowidx, const float *host_values,
+                             const size_t *host_nnz_cap, const float *dev_b, const int64_t *host_at_b, const float *dev_c,
+                             const int64_t *host_at_c, const float *dev_b_rowabs, const int64_t *host_at_rowabs,
+                             const size_t *host_n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                             const thip_param *par, thip_raggedsparse **out);
+int thip_raggedsparse_set_param(thip_raggedsparse *h, const thip_param *par);
+int thip_raggedsparse_init(thip_raggedsparse *h);
+int thip_raggedsparse_run(thip_raggedsparse *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_raggedsparse_run_until_any(thip_raggedsparse *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_raggedsparse_status(thip_raggedsparse *h, int i, thip_status *host_status);
+int thip_raggedsparse_solution(thip_raggedsparse *h, int i, float *host_x, float *host_y);
+int thip_raggedsparse_iterate(thip_raggedsparse *h, int i, float *host_x, float *host_y);
+int thip_raggedsparse_precond(thip_raggedsparse *h, int i, float *host_dp_tau, float *host_dp_sigma);
+/* slot i -- running or stopped -- takes the host CSC arrays of another problem of ITS shape and layout (any pattern of at most
+ * cap_i entries) and device b, c, row sums, and is initialised afresh; no other slot is touched, and a refusal leaves slot i as
+ * it was */
+int thip_raggedsparse_replace(thip_raggedsparse *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx,
+                              const float *host_values, const float *dev_vec_b, const float *dev_vec_c,
+                              const float *dev_vec_b_rowabs);
+int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info);
+int thip_raggedsparse_destroy(thip_raggedsparse *h);
+
 /* What THIS device streams: a bare non-temporal read of `bytes` at dev_ptr (device memory, 16-byte aligned -- e.g. the
  * solver's own A), best and average of `reps` timed launches per grid (HIP events).  bench.py prints it beside the
  * sweep's rate: the boxes of one pool differ by several percent, and a roofline fraction means little without it. */

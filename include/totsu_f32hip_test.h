@@ -274,6 +274,27 @@ int thip_test_sparsebatch_force_resident(thip_sparsebatch *h, int resident);
 int thip_test_sparsebatch_pack(size_t n, size_t m, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,
                                size_t nnz_cap, uint32_t *host_words, size_t cap_words, size_t *host_used_words, int *host_long);
 
+/* TEST HOOK: the workgroup size of a ragged sparse batch (thip_raggedsparse.hip): 256 or 1024 threads put every problem in that one
+ * class, 0 = by the sparse batch's rule.  Before thip_raggedsparse_init. */
+int thip_test_raggedsparse_force_threads(thip_raggedsparse *h, int threads);
+
+/* TEST HOOK: who of a ragged sparse batch reads its blob from LDS: 0 nobody, 1 everybody who fits (the rule).  Before
+ * thip_raggedsparse_init. */
+int thip_test_raggedsparse_force_resident(thip_raggedsparse *h, int resident);
+
+/* TEST HOOK: the plan thip_raggedsparse_create would make (needs no device) for problems of host_nnz[p] entries (NULL: the
+ * capacities) in slots of host_nnz_cap[p] (NULL or 0: the own count), a forced workgroup size (0: by the rule) and a forced residency
+ * (-1: the rule, 0, 1).  host_class[p]: 0 (256 threads) or 1 (1024); host_order: the 256-thread class's members in the order of its
+ * live list, then the 1024-thread class's; host_layout[p]: the index of problem p's cone table; host_arena_at[p]: where its state
+ * starts in the arena, in floats; host_blob_at[p]: where its blob starts, in bytes; host_lds_at[p]: where the resident copy lies in
+ * LDS, in floats; host_resident[p] -- n_prob entries each, any may be NULL.  host_info: the part of info() that needs no device
+ * (NULL: not wanted). */
+int thip_test_raggedsparse_plan(size_t n_prob, const size_t *host_n, const size_t *host_m, const size_t *host_nnz,
+                                const size_t *host_nnz_cap, const size_t *host_n_seg, const int32_t *host_seg_type,
+                                const int64_t *host_seg_len, int force_threads, int force_resident, int *host_class, int *host_order,
+                                int *host_layout, int64_t *host_arena_at, int64_t *host_blob_at, int *host_lds_at, int *host_resident,
+                                thip_raggedsparse_info_t *host_info);
+
 #ifdef __cplusplus
 }
 #endif

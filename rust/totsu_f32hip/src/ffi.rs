@@ -76,6 +76,25 @@ pub struct thip_sparsebatch_info_t {
 }
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
+pub struct thip_raggedsparse_class_t {
+    pub n_prob: i32, pub live: i32, pub threads: i32, pub lds_bytes: i32,
+    pub launches: i64, pub workgroups: i64,
+    pub n_resident: i32, pub reserved: i32,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct thip_raggedsparse_info_t {
+    pub n_prob: i32, pub live: i32, pub n_layouts: i32, pub n_resident: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub a_bytes_per_iter: usize,
+    pub max_psd_order: i32, pub n_psd: i32,
+    pub psd_lds_bytes: usize,
+    pub nnz_total: usize, pub blob_bytes: usize,
+    pub cls: [thip_raggedsparse_class_t; 2],
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
 pub struct thip_raggedbatch_class_t {
     pub n_prob: i32, pub live: i32, pub threads: i32, pub lds_bytes: i32,
     pub launches: i64, pub workgroups: i64,
@@ -149,6 +168,7 @@ pub enum thip_midbatch {}
 pub enum thip_sdpbatch {}
 pub enum thip_raggedbatch {}
 pub enum thip_sparsebatch {}
+pub enum thip_raggedsparse {}
 pub enum thip_sptile {}
 pub enum thip_sptile_builder {}
 pub type thip_allreduce_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, dev_buf: *mut f32, n: usize, stream: *mut c_void) -> c_int>;
@@ -430,6 +450,38 @@ extern "C" {
     pub fn thip_test_sparsebatch_pack(n: usize, m: usize, host_colptr: *const i64, host_rowidx: *const i32, host_values: *const f32,
                                       nnz_cap: usize, host_words: *mut u32, cap_words: usize, host_used_words: *mut usize,
                                       host_long: *mut c_int) -> c_int;
+    // sparse problems of different shapes and cone layouts in one batch (thip_raggedsparse.hip)
+    pub fn thip_raggedsparse_fits(n_prob: usize, host_n: *const usize, host_m: *const usize, host_nnz_cap: *const usize,
+                                  host_n_seg: *const usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                                  host_first_refused: *mut c_int, host_lds_bytes: *mut usize, host_threads: *mut c_int,
+                                  host_resident: *mut c_int) -> c_int;
+    pub fn thip_raggedsparse_create(n_prob: usize, host_n: *const usize, host_m: *const usize, host_colptr: *const i64,
+                                    host_start: *const i64, host_rowidx: *const i32, host_values: *const f32,
+                                    host_nnz_cap: *const usize, dev_b: *const f32, host_at_b: *const i64, dev_c: *const f32,
+                                    host_at_c: *const i64, dev_b_rowabs: *const f32, host_at_rowabs: *const i64,
+                                    host_n_seg: *const usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                                    par: *const thip_param, out: *mut *mut thip_raggedsparse) -> c_int;
+    pub fn thip_raggedsparse_set_param(h: *mut thip_raggedsparse, par: *const thip_param) -> c_int;
+    pub fn thip_raggedsparse_init(h: *mut thip_raggedsparse) -> c_int;
+    pub fn thip_raggedsparse_run(h: *mut thip_raggedsparse, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedsparse_run_until_any(h: *mut thip_raggedsparse, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedsparse_status(h: *mut thip_raggedsparse, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedsparse_solution(h: *mut thip_raggedsparse, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_raggedsparse_iterate(h: *mut thip_raggedsparse, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_raggedsparse_precond(h: *mut thip_raggedsparse, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_raggedsparse_replace(h: *mut thip_raggedsparse, i: c_int, host_colptr: *const i64, host_rowidx: *const i32,
+                                     host_values: *const f32, dev_vec_b: *const f32, dev_vec_c: *const f32,
+                                     dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_raggedsparse_info(h: *const thip_raggedsparse, host_info: *mut thip_raggedsparse_info_t) -> c_int;
+    pub fn thip_raggedsparse_destroy(h: *mut thip_raggedsparse) -> c_int;
+    pub fn thip_test_raggedsparse_force_threads(h: *mut thip_raggedsparse, threads: c_int) -> c_int;
+    pub fn thip_test_raggedsparse_force_resident(h: *mut thip_raggedsparse, resident: c_int) -> c_int;
+    pub fn thip_test_raggedsparse_plan(n_prob: usize, host_n: *const usize, host_m: *const usize, host_nnz: *const usize,
+                                       host_nnz_cap: *const usize, host_n_seg: *const usize, host_seg_type: *const i32,
+                                       host_seg_len: *const i64, force_threads: c_int, force_resident: c_int, host_class: *mut c_int,
+                                       host_order: *mut c_int, host_layout: *mut c_int, host_arena_at: *mut i64,
+                                       host_blob_at: *mut i64, host_lds_at: *mut c_int, host_resident: *mut c_int,
+                                       host_info: *mut thip_raggedsparse_info_t) -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

@@ -40,8 +40,14 @@ in LDS or in memory:
 
     sparsebatch_k and sparsebatch_init_k: the SDP batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
 
+The ragged sparse batch (thip_raggedsparse.hip, --family raggedsparse) is the sparse batch's iteration on a problem the workgroup
+looks up in a table, resident or streamed per problem:
+
+    raggedsparse_k and raggedsparse_init_k: the sparse batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
+
 usage: check_kernel_resources.py <remarks file> [--report]
-                                 [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch]"""
+                                 [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch|
+                                          raggedsparse]"""
 import re
 import sys
 
@@ -103,6 +109,8 @@ OWNBATCH = {
     "sdpbatch": (r"sdpbatch(_init|_project)?_k", ("sdpbatch_k", "sdpbatch_init_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
     "raggedbatch": (r"raggedbatch(_init)?_k", ("raggedbatch_k", "raggedbatch_init_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
     "sparsebatch": (r"sparsebatch(_init)?_k", ("sparsebatch_k", "sparsebatch_init_k"), 128, "sparse batch", "thip_sparsebatch.hip"),
+    "raggedsparse": (r"raggedsparse(_init)?_k", ("raggedsparse_k", "raggedsparse_init_k"), 128, "ragged sparse batch",
+                     "thip_raggedsparse.hip"),
 }
 
 

@@ -17,10 +17,11 @@ from .midbatch import MidBatchSolver, own_a_batch
 from .sdpbatch import SdpBatchSolver, conic_batch
 from .raggedbatch import RaggedBatchSolver, ragged_batch
 from .sparsebatch import SparseBatchSolver
+from .raggedsparse import RaggedSparseBatchSolver
 from .parallel import ShardedSolver, TorchComm, shard_segments
 from .sparse import SparseMatOp, SpTile
 
 __all__ = ["MatOp", "MatType", "Solver", "SolverError", "SolverParam", "F32HIP", "F32HIPSlice", "splitm",
            "ConeZero", "ConeRPos", "ConeSOC", "ConeRotSOC", "ConePSD", "MatBuild", "ProbLP", "ProbSOCP",
-           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "solve_many", "SmallBatchSolver", "MidBatchSolver", "own_a_batch", "SdpBatchSolver", "conic_batch", "RaggedBatchSolver", "ragged_batch", "SparseBatchSolver", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
+           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "solve_many", "SmallBatchSolver", "MidBatchSolver", "own_a_batch", "SdpBatchSolver", "conic_batch", "RaggedBatchSolver", "ragged_batch", "SparseBatchSolver", "RaggedSparseBatchSolver", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
            "shard_segments", "SparseMatOp", "SpTile"]

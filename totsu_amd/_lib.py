@@ -100,6 +100,18 @@ class RaggedBatchInfo(C.Structure):
                 ("cls", RaggedBatchClass * 2)]
 
 
+class RaggedSparseClass(C.Structure):
+    _fields_ = RaggedBatchClass._fields_ + [("n_resident", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RaggedSparseInfo(C.Structure):
+    _fields_ = [("n_prob", C.c_int32), ("live", C.c_int32), ("n_layouts", C.c_int32), ("n_resident", C.c_int32),
+                ("arena_bytes", C.c_size_t), ("device_bytes", C.c_size_t), ("device_bytes_all", C.c_size_t),
+                ("launches", C.c_int64), ("workgroups", C.c_int64), ("a_bytes_per_iter", C.c_size_t),
+                ("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t), ("nnz_total", C.c_size_t),
+                ("blob_bytes", C.c_size_t), ("cls", RaggedSparseClass * 2)]
+
+
 class GemvPlanRec(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("vw", "nj", "ku", "tiles", "chunks", "cols_per_chunk", "m_load", "chunks2",
                                          "cols_per_chunk2", "reserved")]
@@ -349,6 +361,30 @@ PROTOTYPES.update({
     "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
     "thip_test_sparsebatch_force_resident": (_i, [_vp, _i]),
     "thip_test_sparsebatch_pack": (_i, [_sz, _sz, _p64, _p32, fp, _sz, C.POINTER(C.c_uint32), _sz, _psz, C.POINTER(_i)]),
+})
+
+# the ragged sparse batch: the ragged batch's methods on host CSC arrays (totsu_amd/csrc/thip_raggedsparse.hip)
+_p = "thip_raggedsparse_"
+_pi = C.POINTER(_i)
+PROTOTYPES.update({
+    _p + "fits": (_i, [_sz, _psz, _psz, _psz, _psz, _p32, _p64, _pi, _psz, _pi, _pi]),
+    _p + "create": (_i, [_sz, _psz, _psz, _p64, _p64, _p32, fp, _psz, _vp, _p64, _vp, _p64, _vp, _p64, _psz, _p32, _p64,
+                         C.POINTER(Param), C.POINTER(_vp)]),
+    _p + "set_param": PROTOTYPES["thip_sdpbatch_set_param"],
+    _p + "init": PROTOTYPES["thip_sdpbatch_init"],
+    _p + "run": PROTOTYPES["thip_sdpbatch_run"],
+    _p + "run_until_any": PROTOTYPES["thip_sdpbatch_run_until_any"],
+    _p + "status": PROTOTYPES["thip_sdpbatch_status"],
+    _p + "solution": PROTOTYPES["thip_sdpbatch_solution"],
+    _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
+    _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
+    _p + "replace": PROTOTYPES["thip_sparsebatch_replace"],
+    _p + "info": (_i, [_vp, C.POINTER(RaggedSparseInfo)]),
+    _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
+    "thip_test_raggedsparse_force_threads": (_i, [_vp, _i]),
+    "thip_test_raggedsparse_force_resident": (_i, [_vp, _i]),
+    "thip_test_raggedsparse_plan": (_i, [_sz, _psz, _psz, _psz, _psz, _psz, _p32, _p64, _i, _i, _pi, _pi, _pi, _p64, _p64, _pi, _pi,
+                                         C.POINTER(RaggedSparseInfo)]),
 })
 
 _NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen"}

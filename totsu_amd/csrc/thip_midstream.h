@@ -1,10 +1,10 @@
 // thip_midstream.h -- what the batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
 // second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip; thip_raggedbatch.hip: the same on problems of
 // different shapes, through the locator seam of the bodies; thip_sparsebatch.hip: a sparse A held as packed entries, through the
-// matrix-policy seam): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
+// matrix-policy seam; thip_raggedsparse.hip: both seams at once): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
 // two passes per iteration, every vector in LDS -- with one hook in the block-cone phase between the two passes, the thread choice
 // and what they add to the info record.  The init kernel's body, the criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
-// Included once by each of the four translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// Included once by each of the five translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
 // A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when

@@ -18,13 +18,13 @@
 // mb_stride(n_p, m_p) floats of the arena each, packed; identical layouts (m, seg_type, seg_len) share one entry of the tables.
 // rb_plan is the single source of all of this and needs no device; a problem is taken exactly when sp_check takes it.
 //
-// This file: the two kernels, the plan, the handle and the C API.  The API bodies are thip_ownbatch.h's where a handle of one shape
+// This file: the two kernels, the plan, the handle and the C API (RbAt and the launches by class -- init, run -- are
+// thip_raggedhost.h's, one text with thip_raggedsparse.hip).  The API bodies are thip_ownbatch.h's where a handle of one shape
 // and a handle of many do the same thing (poll, status, replace, set_param, destroy; solution / iterate / precond through their
-// _at forms with the problem's own n, m and block); create, init, run and info are this family's own.
-#include "thip_sdpcones.h"
+// _at forms with the problem's own n, m and block); create and info are this family's own.
+#include "thip_raggedhost.h"
 
 #include <map>
-#include <string>
 #include <tuple>
 
 using namespace thip;
@@ -42,14 +42,6 @@ static_assert(sizeof(RbDesc) == 32, "RbDesc is copied as an array");
 
 // mb: the words every problem shares (cls, cones and arena are the tables' and the arena's bases; n, m, n_cones, stride unused)
 struct RbArgs { ObArgs mb; const RbDesc *desc; };
-
-// the seam's other side (ObUniform, thip_ownbatch.h): the problem and its block as read from the descriptor
-struct RbAt {
-    int p; float *ar;
-    __device__ __forceinline__ int problem(const ObArgs &) const { return p; }
-    __device__ __forceinline__ float *block(const ObArgs &, int) const { return ar; }
-    __device__ __forceinline__ int carried(const ObArgs &, int n, int m) const { return n + m; }      // mb_stride - (5 n + 9 m)
-};
 
 // the launch arguments a uniform batch of this workgroup's problem alone would have had
 __device__ __forceinline__ ObArgs rb_problem(const RbArgs &a, RbAt &at)
@@ -105,8 +97,6 @@ struct RbPlan {
     size_t lds[2] = { 0, 0 };
 };
 
-constexpr int RB_THREADS[2] = { 256, 1024 };
-
 // the class split and the order within a class; forced: 0, 256 or 1024
 void rb_classes(RbPlan &pl, int forced)
 {
@@ -121,15 +111,6 @@ void rb_classes(RbPlan &pl, int forced)
         std::stable_sort(pl.members[c].begin(), pl.members[c].end(), [&](int x, int y) {
             return pl.prob[(size_t)x].m * pl.prob[(size_t)x].n > pl.prob[(size_t)y].m * pl.prob[(size_t)y].n;
         });
-}
-
-// a refusal of problem p: the rule's own words behind the index
-int rb_refuse(size_t p, int rc, int *first_refused)
-{
-    if (first_refused) *first_refused = (int)p;
-    const std::string why = thip_last_error();
-    const std::string msg = "problem " + std::to_string(p) + ": " + why;
-    return fail(rc, msg.c_str(), __FILE__, __LINE__);
 }
 
 int rb_plan(size_t n_prob, const size_t *host_n, const size_t *host_m, const size_t *host_n_seg, const int32_t *seg_type,
@@ -205,7 +186,7 @@ RbArgs rb_args(const thip_raggedbatch *h)
 }
 
 // class c's kernel -- the init kernel or `steps` iterations -- on `count` problems: those of the list, or (live == NULL) first ..
-int rb_launch(const thip_raggedbatch *h, bool run, int c, unsigned count, int steps, const int *live, int first)
+int rg_launch(const thip_raggedbatch *h, bool run, int c, unsigned count, int steps, const int *live, int first)
 {
     RbArgs a = rb_args(h);
     a.mb.steps = steps; a.mb.live = live; a.mb.first = first;
@@ -220,63 +201,7 @@ int rb_launch_hook(const OwnBatch *ob, bool run, const ObArgs &a, unsigned count
     const thip_raggedbatch *h = static_cast<const thip_raggedbatch *>(ob);
     if (run || count != 1 || a.live || a.first < 0 || (size_t)a.first >= h->n_prob)
         return fail(THIP_E_INVALID, "a ragged batch launches by class", __FILE__, __LINE__);
-    return rb_launch(h, false, h->pl.prob[(size_t)a.first].cls, 1, 0, nullptr, a.first);
-}
-
-// where class c's list lies in live_dev
-size_t rb_list_at(const thip_raggedbatch *h, int c) { return c == 0 ? 0 : h->pl.members[0].size(); }
-
-// one launch per class with a member in lists[c] (which the launches read until the next synchronisation)
-int rb_launch_lists(thip_raggedbatch *h, bool run, int steps, const std::vector<int> *lists)
-{
-    hipStream_t st = ctx().stream;
-    for (int c = 0; c < 2; ++c) {
-        const std::vector<int> &l = lists[c];
-        if (l.empty()) continue;
-        int *dev = h->live_dev + rb_list_at(h, c);
-        THIP_TRY(hipMemcpyAsync(dev, l.data(), l.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        THIP_RC(rb_launch(h, run, c, (unsigned)l.size(), steps, dev, 0));
-        if (run) {
-            h->cl_launches[c] += 1; h->cl_workgroups[c] += (int64_t)l.size();
-            h->launches += 1; h->workgroups += (int64_t)l.size();
-        }
-    }
-    return 0;
-}
-
-int rb_init(thip_raggedbatch *h)
-{
-    THIP_NEED_INIT();
-    if (!h) return fail(THIP_E_INVALID, RB_TEXT.null_h, __FILE__, __LINE__);
-    THIP_RC(rb_launch_lists(h, false, 0, h->pl.members));
-    h->launches = h->workgroups = 0;
-    for (int c = 0; c < 2; ++c) { h->cl_launches[c] = h->cl_workgroups[c] = 0; h->cl_live[c].clear(); }
-    h->inited = true;
-    return ob_poll(h, nullptr);
-}
-
-int rb_run(thip_raggedbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status, bool until_any)
-{
-    THIP_NEED_INIT();
-    if (!h || !h->inited) return fail(THIP_E_INVALID, RB_TEXT.uninit, __FILE__, __LINE__);
-    if (poll_every <= 0) poll_every = 16;
-    THIP_RC(ob_poll(h, host_status));
-    const size_t live0 = h->live.size();
-    int64_t done = 0;
-    while (!h->live.empty() && (max_steps < 0 || done < max_steps) && !(until_any && h->live.size() < live0)) {
-        int64_t batch = poll_every;
-        if (max_steps >= 0 && done + batch > max_steps) batch = max_steps - done;
-        if (batch > 1 << 20) batch = 1 << 20;
-        for (int c = 0; c < 2; ++c) {       // the running members, in the class's order (its members are not contiguous in p)
-            h->cl_live[c].clear();
-            for (int p : h->pl.members[c])
-                if (h->hst[p].state == THIP_ST_RUNNING) h->cl_live[c].push_back(p);
-        }
-        THIP_RC(rb_launch_lists(h, true, (int)batch, h->cl_live));
-        done += batch;
-        THIP_RC(ob_poll(h, host_status));       // (synchronises: the lists the launches read are the host's to rewrite)
-    }
-    return 0;
+    return rg_launch(h, false, h->pl.prob[(size_t)a.first].cls, 1, 0, nullptr, a.first);
 }
 
 // problem i's block of the arena
@@ -399,11 +324,11 @@ int thip_raggedbatch_create(size_t n_prob, const size_t *host_n, const size_t *h
 }
 
 int thip_raggedbatch_set_param(thip_raggedbatch *h, const thip_param *par) { return ob_set_param(h, par); }
-int thip_raggedbatch_init(thip_raggedbatch *h) { return rb_init(h); }
+int thip_raggedbatch_init(thip_raggedbatch *h) { return rg_init(RB_TEXT, h); }
 int thip_raggedbatch_run(thip_raggedbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
-{ return rb_run(h, max_steps, poll_every, host_status, false); }
+{ return rg_run(RB_TEXT, h, max_steps, poll_every, host_status, false); }
 int thip_raggedbatch_run_until_any(thip_raggedbatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status)
-{ return rb_run(h, max_steps, poll_every, host_status, true); }
+{ return rg_run(RB_TEXT, h, max_steps, poll_every, host_status, true); }
 int thip_raggedbatch_status(thip_raggedbatch *h, int i, thip_status *host_status) { return ob_status(RB_FAMILY, h, i, host_status); }
 
 int thip_raggedbatch_solution(thip_raggedbatch *h, int i, float *host_x, float *host_y)

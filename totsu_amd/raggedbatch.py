@@ -99,12 +99,12 @@ def _info_dict(o):
     return d
 
 
-def pack(problems):
+def pack(problems, kinds=_KINDS):
     """where from_dense puts the host arrays of each kind (needs no GPU): {kind: (one float32 array, [offset in floats per problem;
     -1: the problem has none])}.  Every array starts at a multiple of 4 floats, so an A whose m_p is a multiple of 4 is read with
     16-byte loads.  Problems whose array of a kind is already a DeviceBuffer get offset None there"""
     out = {}
-    for kind in _KINDS:
+    for kind in kinds:
         parts, at, o = [], [], 0
         for d in problems:
             v = getattr(d, kind, None)
@@ -147,22 +147,7 @@ class RaggedBatchSolver(OwnBatchSolver):
         self.param = param or SolverParam()
         _lib.ensure_init()
         try:
-            packed = pack(problems)
-            base, ats = {}, {}
-            for kind in _KINDS:
-                buf, at = packed[kind]
-                dev = self._dev(buf) if buf.size else None
-                ptrs = [None if a == -1 else getattr(d, kind).ptr if a is None else dev.ptr + 4 * a for d, a in zip(problems, at)]
-                have = [p for p in ptrs if p is not None]
-                if not have:
-                    base[kind], ats[kind] = None, None
-                    continue
-                base[kind] = min(have)
-                for k, p in enumerate(ptrs):
-                    if p is not None and (p - base[kind]) % 4:
-                        raise ValueError("problem %d: %s lies at a misaligned float offset (%d bytes from the others of its kind)"
-                                         % (k, kind, p - base[kind]))
-                ats[kind] = np.array([-1 if p is None else (p - base[kind]) // 4 for p in ptrs], dtype=np.int64)
+            base, ats = self._upload(problems, _KINDS)
             _, n, m, ns, st, sl = _shape_arrays(problems)
             par = _c_param(self.param)
             h = C.c_void_p()
@@ -187,6 +172,27 @@ class RaggedBatchSolver(OwnBatchSolver):
         except Exception:
             self.destroy()
             raise
+
+    def _upload(self, problems, kinds):
+        """the host arrays of each kind packed and uploaded (the object owns them): ({kind: the lowest device address of the kind, or
+        None}, {kind: the problems' offsets from it in floats as an int64 array (-1: the problem has none), or None})"""
+        packed = pack(problems, kinds)
+        base, ats = {}, {}
+        for kind in kinds:
+            buf, at = packed[kind]
+            dev = self._dev(buf) if buf.size else None
+            ptrs = [None if a == -1 else getattr(d, kind).ptr if a is None else dev.ptr + 4 * a for d, a in zip(problems, at)]
+            have = [p for p in ptrs if p is not None]
+            if not have:
+                base[kind], ats[kind] = None, None
+                continue
+            base[kind] = min(have)
+            for k, p in enumerate(ptrs):
+                if p is not None and (p - base[kind]) % 4:
+                    raise ValueError("problem %d: %s lies at a misaligned float offset (%d bytes from the others of its kind)"
+                                     % (k, kind, p - base[kind]))
+            ats[kind] = np.array([-1 if p is None else (p - base[kind]) // 4 for p in ptrs], dtype=np.int64)
+        return base, ats
 
     @staticmethod
     def _check_lengths(what, n, m, mat_a, vec_b, vec_c, vec_b_rowabs):
