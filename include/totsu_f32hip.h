@@ -421,6 +421,14 @@ int thip_solver_set_param(thip_solver *s, const thip_param *par);
 int thip_solver_solution(thip_solver *s, float *host_x, float *host_y);
 /* raw iterate (x: n+2m+1, y: n+m+1, reference layout solver.rs:349-355), for parity tests */
 int thip_solver_iterate(thip_solver *s, float *host_x, float *host_y);
+/* After thip_solver_init: the solver goes on from the iterate (host_x, host_y) -- the layouts of thip_solver_iterate, of a RUNNING
+ * solver (a terminated one's x_x, x_y come back divided by tau) -- instead of x = 0, y = 0, tau = 1.  Uploads x_x, x_y, x_s, u, v, zeroes
+ * the Kahan terms, writes tau and kappa and resets the status block (iteration 0, RUNNING; norms and preconditioner stay); the
+ * carried schedules' A x_x, A^T x_y are recomputed by one pass over the stored form of A now in use, the one-pass schedule restarts
+ * from the iterate as a consistent one.  Any A: dense in any stored form, the two-CSR form, the tiled sparse copy.  Synchronous.
+ * THIP_E_INVALID: a null argument, a solver not initialised, an all-reduce or a column shard set (multi-GPU starts are not offered), a
+ * tau that is negative or not finite, a kappa that is positive or not finite. */
+int thip_solver_set_iterate(thip_solver *s, const float *host_x, const float *host_y);
 int thip_solver_precond(thip_solver *s, float *host_dp_tau, float *host_dp_sigma);
 int thip_solver_destroy(thip_solver *s);
 /* physical passes over A per iteration of the schedule in use, and bytes one pass reads */
@@ -523,6 +531,10 @@ int thip_batch_destroy(thip_batch *b);
  * synchronise), so the old b / c are no longer read once it has returned: the caller may free them AFTER the call returns, not
  * before.  THIP_E_INVALID: a null argument, no such slot, a batch that is not initialised. */
 int thip_batch_replace(thip_batch *b, int i, const float *dev_vec_b, const float *dev_vec_c);
+/* thip_solver_set_iterate of slot i, after thip_batch_init or thip_batch_replace; the slot is live again.  Its carried products cost
+ * one single-vector pass over A for that slot.  The iterations the slot had made stay in thip_batch_counters' instance_iterations, as a
+ * replaced occupant's do. */
+int thip_batch_set_iterate(thip_batch *b, int i, const float *host_x, const float *host_y);
 /* on = 1: at every poll the instances the host saw RUNNING are packed in ascending index order into groups of at most max_group
  * (thip_batch_live_grouping), so a pass costs ceil(live / max_group) launches; a group of k runs on the kernel instance of k
  * vectors, a group of one on the single-vector kernel.  thip_batch_init then tunes every kernel instance the batch can come to
@@ -592,6 +604,17 @@ int thip_smallbatch_precond(thip_smallbatch *h, int i, float *host_dp_tau, float
  * no other slot is touched */
 int thip_smallbatch_replace(thip_smallbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                             const float *dev_vec_b_rowabs);
+/* problems first .. first + count - 1 start from the given iterates instead of x = 0, y = 0, tau = 1: after thip_smallbatch_init or
+ * _replace, whose norms and preconditioner stay.  host_x: the problems' x one after another, n + 2 m + 1 floats each (x_x, x_y, x_s,
+ * tau); host_y: n + m + 1 each (u, v, kappa) -- the layout thip_smallbatch_iterate writes (of a RUNNING problem: a stopped one's
+ * x_x, x_y come back divided by tau).  The Kahan terms, r_tau and the criteria are zero, the iteration count 0, the problems RUNNING
+ * again; the streamed families form the carried pair A x_x, A^T x_y of the iterate.  One upload and one launch (one per workgroup-
+ * size class where the problems have their own shapes, every length then the problem's own); synchronous.  The iterates are packed into pinned host
+ * memory and uploaded to a staging buffer, both the handle's, grown to the largest call and freed by _destroy; the device one is counted
+ * in device_bytes.  THIP_E_INVALID: a null
+ * argument, a handle not initialised, a range outside the batch, count < 1, a tau that is negative or not finite, a kappa that is
+ * positive or not finite; every other entry is the caller's, as A, b and c are.  The same under every thip_*batch prefix */
+int thip_smallbatch_set_iterates(thip_smallbatch *h, int first, int count, const float *host_x, const float *host_y);
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
 int thip_smallbatch_destroy(thip_smallbatch *h);
 
@@ -633,6 +656,7 @@ int thip_midbatch_iterate(thip_midbatch *h, int i, float *host_x, float *host_y)
 int thip_midbatch_precond(thip_midbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
 int thip_midbatch_replace(thip_midbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                           const float *dev_vec_b_rowabs);
+int thip_midbatch_set_iterates(thip_midbatch *h, int first, int count, const float *host_x, const float *host_y);
 int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
@@ -674,6 +698,7 @@ int thip_sdpbatch_iterate(thip_sdpbatch *h, int i, float *host_x, float *host_y)
 int thip_sdpbatch_precond(thip_sdpbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
 int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                           const float *dev_vec_b_rowabs);
+int thip_sdpbatch_set_iterates(thip_sdpbatch *h, int first, int count, const float *host_x, const float *host_y);
 int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
@@ -732,6 +757,7 @@ int thip_raggedbatch_iterate(thip_raggedbatch *h, int i, float *host_x, float *h
 int thip_raggedbatch_precond(thip_raggedbatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
 int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                              const float *dev_vec_b_rowabs);
+int thip_raggedbatch_set_iterates(thip_raggedbatch *h, int first, int count, const float *host_x, const float *host_y);
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
 int thip_raggedbatch_destroy(thip_raggedbatch *h);
 
@@ -789,6 +815,7 @@ int thip_sparsebatch_precond(thip_sparsebatch *h, int i, float *host_dp_tau, flo
  * b, c, row sums, and is initialised afresh; no other slot is touched */
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx,
                              const float *host_values, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs);
+int thip_sparsebatch_set_iterates(thip_sparsebatch *h, int first, int count, const float *host_x, const float *host_y);
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
 int thip_sparsebatch_destroy(thip_sparsebatch *h);
 
@@ -860,6 +887,7 @@ int thip_raggedsparse_precond(thip_raggedsparse *h, int i, float *host_dp_tau, f
 int thip_raggedsparse_replace(thip_raggedsparse *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx,
                               const float *host_values, const float *dev_vec_b, const float *dev_vec_c,
                               const float *dev_vec_b_rowabs);
+int thip_raggedsparse_set_iterates(thip_raggedsparse *h, int first, int count, const float *host_x, const float *host_y);
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info);
 int thip_raggedsparse_destroy(thip_raggedsparse *h);
 

@@ -302,6 +302,7 @@ extern "C" {
     pub fn thip_solver_resume(s: *mut thip_solver) -> c_int;
     pub fn thip_solver_status(s: *mut thip_solver, host_status: *mut thip_status) -> c_int;
     pub fn thip_solver_iterate(s: *mut thip_solver, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_solver_set_iterate(s: *mut thip_solver, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_solver_precond(s: *mut thip_solver, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
     pub fn thip_solver_passes(s: *const thip_solver, host_passes: *mut c_int, host_bytes_per_pass: *mut usize) -> c_int;
     pub fn thip_solver_schedule_in_use(s: *mut thip_solver, host_schedule: *mut c_int) -> c_int;
@@ -331,6 +332,7 @@ extern "C" {
     pub fn thip_batch_grouping(n_inst: c_int, max_group: c_int, host_groups: *mut c_int, host_members: *mut c_int) -> c_int;
     pub fn thip_batch_destroy(b: *mut thip_batch) -> c_int;
     pub fn thip_batch_replace(b: *mut thip_batch, i: c_int, dev_vec_b: *const f32, dev_vec_c: *const f32) -> c_int;
+    pub fn thip_batch_set_iterate(b: *mut thip_batch, i: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_batch_set_regroup(b: *mut thip_batch, on: c_int) -> c_int;
     pub fn thip_batch_run_until_any(b: *mut thip_batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
     pub fn thip_batch_live_grouping(n_inst: c_int, max_group: c_int, host_live: *const c_int, host_groups: *mut c_int,
@@ -353,6 +355,7 @@ extern "C" {
     pub fn thip_smallbatch_precond(h: *mut thip_smallbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
     pub fn thip_smallbatch_replace(h: *mut thip_smallbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
                                    dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_smallbatch_set_iterates(h: *mut thip_smallbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_smallbatch_info(h: *const thip_smallbatch, host_info: *mut thip_smallbatch_info_t) -> c_int;
     pub fn thip_smallbatch_destroy(h: *mut thip_smallbatch) -> c_int;
     pub fn thip_test_smallbatch_force_threads(h: *mut thip_smallbatch, threads: c_int) -> c_int;
@@ -373,6 +376,7 @@ extern "C" {
     pub fn thip_midbatch_precond(h: *mut thip_midbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
     pub fn thip_midbatch_replace(h: *mut thip_midbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
                                  dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_midbatch_set_iterates(h: *mut thip_midbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_midbatch_info(h: *const thip_midbatch, host_info: *mut thip_midbatch_info_t) -> c_int;
     pub fn thip_midbatch_destroy(h: *mut thip_midbatch) -> c_int;
     pub fn thip_test_midbatch_force_threads(h: *mut thip_midbatch, threads: c_int) -> c_int;
@@ -393,6 +397,7 @@ extern "C" {
     pub fn thip_sdpbatch_precond(h: *mut thip_sdpbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
     pub fn thip_sdpbatch_replace(h: *mut thip_sdpbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
                                  dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_sdpbatch_set_iterates(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_sdpbatch_info(h: *const thip_sdpbatch, host_info: *mut thip_sdpbatch_info_t) -> c_int;
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
@@ -418,6 +423,7 @@ extern "C" {
     pub fn thip_raggedbatch_precond(h: *mut thip_raggedbatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
     pub fn thip_raggedbatch_replace(h: *mut thip_raggedbatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
                                     dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_raggedbatch_set_iterates(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_raggedbatch_info(h: *const thip_raggedbatch, host_info: *mut thip_raggedbatch_info_t) -> c_int;
     pub fn thip_raggedbatch_destroy(h: *mut thip_raggedbatch) -> c_int;
     pub fn thip_test_raggedbatch_force_threads(h: *mut thip_raggedbatch, threads: c_int) -> c_int;
@@ -443,6 +449,7 @@ extern "C" {
     pub fn thip_sparsebatch_replace(h: *mut thip_sparsebatch, i: c_int, host_colptr: *const i64, host_rowidx: *const i32,
                                     host_values: *const f32, dev_vec_b: *const f32, dev_vec_c: *const f32,
                                     dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_sparsebatch_set_iterates(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_sparsebatch_info(h: *const thip_sparsebatch, host_info: *mut thip_sparsebatch_info_t) -> c_int;
     pub fn thip_sparsebatch_destroy(h: *mut thip_sparsebatch) -> c_int;
     pub fn thip_test_sparsebatch_force_threads(h: *mut thip_sparsebatch, threads: c_int) -> c_int;
@@ -472,6 +479,7 @@ extern "C" {
     pub fn thip_raggedsparse_replace(h: *mut thip_raggedsparse, i: c_int, host_colptr: *const i64, host_rowidx: *const i32,
                                      host_values: *const f32, dev_vec_b: *const f32, dev_vec_c: *const f32,
                                      dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_raggedsparse_set_iterates(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_raggedsparse_info(h: *const thip_raggedsparse, host_info: *mut thip_raggedsparse_info_t) -> c_int;
     pub fn thip_raggedsparse_destroy(h: *mut thip_raggedsparse) -> c_int;
     pub fn thip_test_raggedsparse_force_threads(h: *mut thip_raggedsparse, threads: c_int) -> c_int;

@@ -237,6 +237,7 @@ PROTOTYPES = {
     "thip_solver_status": (_i, [_vp, C.POINTER(Status)]),
     "thip_solver_solution": (_i, [_vp, _vp, _vp]),
     "thip_solver_iterate": (_i, [_vp, _vp, _vp]),
+    "thip_solver_set_iterate": (_i, [_vp, _vp, _vp]),
     "thip_solver_precond": (_i, [_vp, _vp, _vp]),
     "thip_solver_destroy": (_i, [_vp]),
     "thip_solver_passes": (_i, [_vp, C.POINTER(_i), C.POINTER(_sz)]),
@@ -274,6 +275,7 @@ PROTOTYPES = {
     "thip_batch_grouping": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "thip_batch_destroy": (_i, [_vp]),
     "thip_batch_replace": (_i, [_vp, _i, _vp, _vp]),
+    "thip_batch_set_iterate": (_i, [_vp, _i, _vp, _vp]),
     "thip_batch_set_regroup": (_i, [_vp, _i]),
     "thip_batch_run_until_any": (_i, [_vp, C.c_int64, C.c_int64, C.POINTER(Status)]),
     "thip_batch_live_grouping": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -314,6 +316,7 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "iterate": (_i, [_vp, _i, _vp, _vp]),
         _p + "precond": (_i, [_vp, _i, _vp, _vp]),
         _p + "replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+        _p + "set_iterates": (_i, [_vp, _i, _i, _vp, _vp]),
         _p + "info": (_i, [_vp, C.POINTER(_info)]),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
@@ -335,6 +338,7 @@ PROTOTYPES.update({
     _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": PROTOTYPES["thip_sdpbatch_replace"],
+    _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
@@ -356,6 +360,7 @@ PROTOTYPES.update({
     _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": (_i, [_vp, _i, _p64, _p32, fp, _vp, _vp, _vp]),
+    _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "info": (_i, [_vp, C.POINTER(SparseBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
@@ -379,6 +384,7 @@ PROTOTYPES.update({
     _p + "iterate": PROTOTYPES["thip_sdpbatch_iterate"],
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": PROTOTYPES["thip_sparsebatch_replace"],
+    _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedSparseInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedsparse_force_threads": (_i, [_vp, _i]),

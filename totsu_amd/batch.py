@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib
-from .fused import Bf16Matrix, DeviceBuffer, FusedResult, _c_param
+from .fused import Bf16Matrix, DeviceBuffer, FusedResult, _c_param, _checked, _raw, _start_arrays
 from .solver import SolverError, SolverParam
 
 
@@ -37,9 +37,12 @@ def live_groups(live, max_group=_lib.BATCH_GROUP_DEFAULT):
     return out
 
 
-def stream_slots(batch, problems, poll_every=16):
+def stream_slots(batch, problems, poll_every=16, warm=False):
     """The slot-filling policy, over any object with n_inst / run_until_any / replace / solution (a BatchSolver, or a
-    stub of one).  The batch's slots hold
+    stub of one; warm=True also asks it for raw_iterate and replace(start=)).  warm=True: a refilled slot starts from the raw
+    iterate its previous occupant ended with when that occupant ended OK, and afresh otherwise -- the choice for a path or a sweep,
+    where the next problem is the last one slightly changed; order, laziness and results per problem are those of warm=False.
+    The batch's slots hold
     problems 0 .. n_inst - 1 when this starts; the (b, c) of the iterable `problems` -- lazy or unbounded -- are numbered on from
     n_inst.  Whenever run_until_any returns, every slot found stopped is read out and handed the next problem at once; yields
     (k, result, x, y) per finished problem k, in the order they finish.  Ends when the iterable is dry and every slot has stopped."""
@@ -62,7 +65,10 @@ def stream_slots(batch, problems, poll_every=16):
                 except StopIteration:
                     it = None
                 else:
-                    batch.replace(i, vec_b, vec_c)
+                    if warm and r.state == _lib.ST_OK:
+                        batch.replace(i, vec_b, vec_c, start=batch.raw_iterate(i))
+                    else:
+                        batch.replace(i, vec_b, vec_c)
                     occupant[i], nxt = nxt, nxt + 1
         for d in done:
             yield d
@@ -74,10 +80,12 @@ class ManyResults(list):
     info = None
 
 
-def solve_many(dense, vecs_b, vecs_c, slots=8, param=None, poll_every=16, **kw):
+def solve_many(dense, vecs_b, vecs_c, slots=8, param=None, poll_every=16, warm=False, **kw):
     """Any number (>= 1) of problems (vecs_b[k], vecs_c[k]) over the A and cones of `dense` (Prob*.dense(); its own b / c are not
     used), streamed through one BatchSolver of min(slots, len) slots (slots <= 64) with regroup=True.  Returns the list of
-    (FusedResult, x, y) IN INPUT ORDER (a ManyResults).  **kw: BatchSolver's (max_group, gemv_autotune)."""
+    (FusedResult, x, y) IN INPUT ORDER (a ManyResults).  warm=True: a refilled slot starts from the iterate its previous occupant
+    ended with (stream_slots) -- for problems given in an order in which neighbours are alike.  **kw: BatchSolver's (max_group,
+    gemv_autotune)."""
     vecs_b, vecs_c = list(vecs_b), list(vecs_c)
     if len(vecs_b) != len(vecs_c):
         raise ValueError("vecs_b and vecs_c differ in length: %d vs %d" % (len(vecs_b), len(vecs_c)))
@@ -90,7 +98,7 @@ def solve_many(dense, vecs_b, vecs_c, slots=8, param=None, poll_every=16, **kw):
     bt = BatchSolver.from_dense(dense, vecs_b[:s], vecs_c[:s], param, **kw)
     try:
         out = ManyResults([None] * len(vecs_b))
-        for k, r, x, y in bt.stream(zip(vecs_b[s:], vecs_c[s:]), poll_every):
+        for k, r, x, y in bt.stream(zip(vecs_b[s:], vecs_c[s:]), poll_every, warm=warm):
             out[k] = (r, x, y)
         out.counters, out.info = bt.counters(), bt.info()
     finally:
@@ -172,15 +180,18 @@ class BatchSolver:
         (self._owned if owned is None else owned).append(d)
         return d
 
-    def replace(self, i, vec_b, vec_c):
+    def replace(self, i, vec_b, vec_c, start=None):
         """slot i -- running or stopped -- takes the problem (vec_b, vec_c) (host arrays or DeviceBuffers) as a fresh init; no
-        other instance is touched.  What the batch had uploaded for the slot's previous problem is freed after the call."""
+        other instance is touched.  What the batch had uploaded for the slot's previous problem is freed after the call.
+        start: None, or the (x, y) the new problem starts from (replace, then set_iterate)."""
         if vec_b is None or vec_c is None:
             raise ValueError("replace: vec_b and vec_c are needed")
         if not 0 <= int(i) < self.n_inst:
             raise ValueError("replace: no slot %r in a batch of %d" % (i, self.n_inst))
         self._check_len("vec_b", vec_b, self.m)
         self._check_len("vec_c", vec_c, self.n)
+        if start is not None:
+            start = _start_arrays(self.n, self.m, *start)
         i, own = int(i), []
         try:
             db, dc = self._dev(vec_b, own), self._dev(vec_c, own)
@@ -193,6 +204,22 @@ class BatchSolver:
         self.vecs_b[i], self.vecs_c[i] = db, dc
         for d in old:
             d.free()
+        if start is not None:
+            _checked(lib.thip_batch_set_iterate, self.h, i, start[0].ctypes.data, start[1].ctypes.data)
+
+    def set_iterate(self, i, x, y):
+        """slot i goes on from the iterate (x, y) -- what iterate(i) returns for a running instance, or raw_iterate(i) for any --
+        instead of x = 0, y = 0, tau = 1: iteration 0, running, the compensation terms zero; b, c, the norms and the
+        preconditioner stay.  Costs one single-vector pass over A (the slot's carried products).  ValueError: a wrong length
+        (before anything is uploaded), a tau that is negative or not finite, a kappa that is positive or not finite."""
+        if not 0 <= int(i) < self.n_inst:
+            raise ValueError("set_iterate: no slot %r in a batch of %d" % (i, self.n_inst))
+        x, y = _start_arrays(self.n, self.m, x, y)
+        _checked(lib.thip_batch_set_iterate, self.h, int(i), x.ctypes.data, y.ctypes.data)
+
+    def raw_iterate(self, i):
+        """iterate(i) with the read-out's final scaling undone (FusedSolver.raw_iterate): what set_iterate expects from a finished solve"""
+        return _raw(self.iterate(i), self.status(i))
 
     def reinit(self):
         """thip_batch_init again: a fresh solve of every instance"""
@@ -215,10 +242,11 @@ class BatchSolver:
         lib.thip_batch_run_until_any(self.h, int(max_steps), int(poll_every), st)
         return [FusedResult(s) for s in st]
 
-    def stream(self, problems, poll_every=16):
+    def stream(self, problems, poll_every=16, warm=False):
         """generator: the batch's own problems (k = 0 .. n_inst - 1) and then those of the iterable `problems` of (b, c) (k counts
-        on), each slot refilled as soon as its problem has stopped; yields (k, FusedResult, x, y) as they finish (stream_slots)"""
-        return stream_slots(self, problems, poll_every)
+        on), each slot refilled as soon as its problem has stopped; yields (k, FusedResult, x, y) as they finish (stream_slots).
+        warm=True: a refilled slot starts from the iterate its previous occupant ended with"""
+        return stream_slots(self, problems, poll_every, warm=warm)
 
     def counters(self):
         """what run / run_until_any have issued since the last init: launches by kernel instance {1, 2, 4, 8}, passes over A,

@@ -25,6 +25,11 @@ __global__ __launch_bounds__(1024) void midbatch_init_k(const ObArgs a) { mb_ini
 
 __global__ __launch_bounds__(1024) void midbatch_k(const ObArgs a) { mb_iterate_body(a, MbNoPsd()); }
 
+// a problem starts from a given iterate (thip_midbatch_set_iterates): its own argument block, the iteration's by value
+struct MbStartArgs { ObArgs mb; ObStart s; };
+
+__global__ __launch_bounds__(1024) void midbatch_start_k(const MbStartArgs a) { mb_start_body(a.mb, ob_staged(a.s)); }
+
 const ObText MB_TEXT = { "mid batch not initialised", "null mid batch", "a mid batch holds 1 .. 1048576 problems",
                          "a mid batch takes no PSD segment", "the workgroup size is 256 or 1024 (0: by shape)",
                          "thip_test_midbatch_force_threads comes before thip_midbatch_init" };
@@ -50,8 +55,13 @@ int mb_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
     return ob_launch(h, run ? midbatch_k : midbatch_init_k, a, count);
 }
 
-ObFamily MB_FAMILY = { MB_TEXT, { 256, 1024, 0 }, true, mb_check, mb_threads_for, mb_lds_for, mb_stride, mb_launch,
-                       { (const void *)midbatch_k, (const void *)midbatch_init_k, nullptr } };
+int mb_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count)
+{
+    return ob_launch(h, midbatch_start_k, MbStartArgs{ a, s }, count);
+}
+
+ObFamily MB_FAMILY = { MB_TEXT, { 256, 1024, 0 }, true, mb_check, mb_threads_for, mb_lds_for, mb_stride, mb_launch, mb_start,
+                       { (const void *)midbatch_k, (const void *)midbatch_init_k, (const void *)midbatch_start_k, nullptr } };
 
 }  // namespace
 

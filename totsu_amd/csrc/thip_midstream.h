@@ -295,6 +295,41 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
     if (tid == 0) s.store(gst);
 }
 
+// a problem starts from a given iterate (thip_NAME_set_iterates): its workgroup loads the staged (x, y) at `it` into the map, forms the
+// carried pair of that iterate -- h = A x_x, g = A^T x_y, the call the iteration's second pass makes, so a run that is handed
+// its own iterate continues bit for bit -- and writes the mutable part of the arena (Kahan terms zero), the pair and the status
+// block.  The slot's data, the preconditioner and the norms stay as init left them.  AT, MAT: the seams of the two bodies above
+template <class AT = ObUniform, class MAT = MbDenseA>
+__device__ __forceinline__ void mb_start_body(const ObArgs &a, const float *it, const AT &at = AT(), const MAT &mat = MAT())
+{
+    const int p = at.problem(a);
+    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const MbMap L(n, m);
+    float *S = mb_lds;
+    float *const xx = S + L.xx, *const xy = S + L.xy, *const h = S + L.h, *const g = S + L.g;
+    const float *const x = it, *const y = it + n + 2 * m + 1;       // x_x x_y x_s tau | u v kappa
+    const SbSlot sl = a.slots[p];
+    const auto A = mat.open(sl.a, m, n, S);
+    for (int i = tid; i < n; i += T) {
+        xx[i] = x[i]; S[L.u + i] = y[i];
+        S[L.kx + i] = 0.0f; S[L.ku + i] = 0.0f;
+    }
+    for (int i = tid; i < m; i += T) {
+        xy[i] = x[n + i]; S[L.xs + i] = x[n + m + i]; S[L.v + i] = y[n + i];
+        S[L.ky + i] = 0.0f; S[L.ks + i] = 0.0f; S[L.kv + i] = 0.0f;
+    }
+    mat.template pass<false>(A, m, n, xx, xy, h, g, S + L.hp, S + L.gp);
+    float *const ar = at.block(a, p);
+    {
+        const int nmut = 4 * n + 6 * m;                    // the arena's order is the LDS order from xx on
+        for (int i = tid; i < nmut; i += T) ar[i] = xx[i];
+        float *const gcar = ar + 5 * n + 9 * m;
+        for (int i = tid; i < m; i += T) gcar[i] = h[i];
+        for (int i = tid; i < n; i += T) gcar[m + i] = g[i];
+    }
+    if (tid == 0) ob_start_status(a.st + p, x[n + 2 * m], y[n + m]);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 int mb_threads_for(size_t n, size_t m) { return n * m <= 8192 ? 256 : 1024; }

@@ -231,6 +231,27 @@ __device__ __forceinline__ void ob_status_eval(ObScalars &s, const ObLimits a, f
     s.state = o.state;
 }
 
+// where the iterates a start kernel hands to its problems lie (thip_NAME_set_iterates): workgroup k's begins at stage + at[k], or
+// (at == NULL: one shape) at stage + k * per.  A problem's part is x = (x_x, x_y, x_s, tau) and then y = (u, v, kappa), the layout
+// thip_NAME_iterate writes
+struct ObStart { const float *stage; const long long *at; long long per; };
+
+__device__ __forceinline__ const float *ob_staged(const ObStart &s)
+{
+    return s.stage + (s.at ? s.at[blockIdx.x] : (long long)blockIdx.x * s.per);
+}
+
+// the status block of a problem that starts from a given iterate (one thread): iteration 0, running, nothing judged yet.  What init
+// made of the problem's data -- the norms and the preconditioner's two scalars -- stays
+__device__ __forceinline__ void ob_start_status(SbStatus *g, float tau, float kappa)
+{
+    g->tau = tau; g->kappa = kappa; g->r_tau = 0.0f;
+    g->iter = 0; g->kind = 0;
+    g->cri[0] = g->cri[1] = g->cri[2] = 0.0f;
+    g->state = THIP_ST_RUNNING;
+    g->stop = 0;
+}
+
 __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,
                                  size_t m, size_t n)
 {
@@ -264,7 +285,8 @@ struct ObFamily {
     size_t (*lds_for)(size_t n, size_t m, int threads, const ObPsd &psd);
     size_t (*stride_for)(size_t n, size_t m);
     int (*launch)(const OwnBatch *h, bool run, const ObArgs &a, unsigned count);      // the init kernel or the iteration
-    const void *kernels[3];                 // every kernel that asks for more than 64 KiB of LDS
+    int (*start)(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count);      // the start kernel (NULL: by class)
+    const void *kernels[4];                 // every kernel that asks for more than 64 KiB of LDS
     size_t total = 0;                       // device memory held by every handle of the family
     std::once_flag attr_once;
     hipError_t attr_err = hipSuccess;
@@ -289,6 +311,8 @@ struct OwnBatch {
     bool inited = false;
     int64_t launches = 0, workgroups = 0;
     ObPsd psd;
+    // where set_iterates packs its iterates (pinned host memory) and where it uploads them: grown on demand, the handle's
+    void *stage = nullptr, *stage_host = nullptr; size_t stage_bytes = 0;
     std::vector<unsigned char> unaligned;   // (a family that streams A) per slot: the problem's A is not 16-byte aligned
     size_t n_unaligned = 0;                 // how many: decides the load path info() reports
 };
@@ -467,6 +491,8 @@ int ob_destroy(H *h)
     if (!h) return 0;
     if (ctx().inited) hipStreamSynchronize(ctx().stream);
     hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
+    hipFree(h->stage);
+    if (h->stage_host) hipHostFree(h->stage_host);
     if (h->hst) hipHostFree(h->hst);
     h->fam->total -= h->bytes;
     delete h;
@@ -612,6 +638,90 @@ int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, co
     return 0;
 }
 
+// tau and kappa of a start: the last entries of x and y
+int ob_start_scalars(const float *x, const float *y, size_t n, size_t m)
+{
+    const float tau = x[n + 2 * m], kappa = y[n + m];
+    if (!(tau >= 0.0f) || tau - tau != 0.0f) return fail(THIP_E_INVALID, "a start's tau is finite and not negative", __FILE__, __LINE__);
+    if (!(kappa <= 0.0f) || kappa - kappa != 0.0f) return fail(THIP_E_INVALID, "a start's kappa is finite and not positive", __FILE__, __LINE__);
+    return 0;
+}
+
+// every refusal of a start that needs no shape
+int ob_start_range(const ObFamily &f, const OwnBatch *h, int first, int count, const float *host_x, const float *host_y)
+{
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (!h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
+    if (!host_x || !host_y) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    if (count < 1 || first < 0 || (size_t)first + (size_t)count > h->n_prob)
+        return fail(THIP_E_INVALID, "no such range of problems", __FILE__, __LINE__);
+    return 0;
+}
+
+// `bytes` of staging for a start: a device buffer (counted in device_bytes) and its pinned twin on the host, both the handle's, freed
+// by destroy and grown to the largest call -- a start per slot, replace(start=) in a loop, pays no allocation, and the one upload
+// is a DMA from the memory the iterates were packed into.  *host: where the caller packs
+int ob_stage_reserve(OwnBatch *h, size_t bytes, void **host)
+{
+    if (h->stage_bytes < bytes) {
+        THIP_TRY(hipStreamSynchronize(ctx().stream));
+        THIP_TRY(hipFree(h->stage));
+        h->stage = nullptr;
+        if (h->stage_host) THIP_TRY(hipHostFree(h->stage_host));
+        h->stage_host = nullptr;
+        h->bytes -= h->stage_bytes; h->fam->total -= h->stage_bytes;
+        h->stage_bytes = 0;
+        THIP_TRY(hipHostMalloc(&h->stage_host, bytes, hipHostMallocDefault));
+        THIP_RC(ob_alloc(h, &h->stage, bytes));
+        h->stage_bytes = bytes;
+    }
+    *host = h->stage_host;
+    return 0;
+}
+
+// the `bytes` packed into the handle's pinned buffer up, `launch` (the start kernels on them), and the host's books: the problems
+// first .. first + count - 1 are running again, their status blocks fresh
+template <class LAUNCH>
+int ob_start_staged(OwnBatch *h, int first, int count, size_t bytes, const LAUNCH &launch)
+{
+    hipStream_t st = ctx().stream;
+    void *const stage = h->stage;
+    THIP_TRY(hipMemcpyAsync(stage, h->stage_host, bytes, hipMemcpyHostToDevice, st));
+    const int rc = launch(stage);
+    if (rc != 0) { hipStreamSynchronize(st); return rc; }      // (the copy may still be reading the pinned buffer)
+    THIP_TRY(hipMemcpyAsync(h->hst + first, h->dst + first, (size_t)count * sizeof(SbStatus), hipMemcpyDeviceToHost, st));
+    THIP_TRY(hipStreamSynchronize(st));
+    std::vector<int> merged;                                     // (the live list is sorted: the range goes in as one run)
+    merged.reserve(h->live.size() + (size_t)count);
+    for (int p : h->live) if (p < first) merged.push_back(p);
+    for (int p = first; p < first + count; ++p) merged.push_back(p);
+    for (int p : h->live) if (p >= first + count) merged.push_back(p);
+    h->live.swap(merged);
+    return 0;
+}
+
+// thip_NAME_set_iterates of a family of one shape: one upload, one launch
+int ob_set_iterates(const ObFamily &f, OwnBatch *h, int first, int count, const float *host_x, const float *host_y)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_start_range(f, h, first, count, host_x, host_y));
+    const size_t n = h->n, m = h->m, nx = n + 2 * m + 1, ny = n + m + 1, per = nx + ny;
+    for (int k = 0; k < count; ++k) THIP_RC(ob_start_scalars(host_x + (size_t)k * nx, host_y + (size_t)k * ny, n, m));
+    const size_t bytes = per * (size_t)count * sizeof(float);
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    float *const host = static_cast<float *>(pinned);
+    for (int k = 0; k < count; ++k) {
+        memcpy(host + (size_t)k * per, host_x + (size_t)k * nx, nx * sizeof(float));
+        memcpy(host + (size_t)k * per + nx, host_y + (size_t)k * ny, ny * sizeof(float));
+    }
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        ObArgs a = ob_args(h);
+        a.first = first;
+        return f.start(h, a, ObStart{ static_cast<const float *>(stage), nullptr, (long long)per }, (unsigned)count);
+    });
+}
+
 // the shape rules alone: the family's check (which fills *cones, *cls and *psd when they are given), its thread choice and the LDS of
 // one workgroup
 int ob_fits(const ObFamily &f, size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -730,6 +840,8 @@ int ob_force_threads(const ObFamily &f, OwnBatch *h, int threads)
     int thip_##NAME##_replace(thip_##NAME *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,        \
                               const float *dev_vec_b_rowabs)                                                                        \
     { return ob_replace(FAM, h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs); }                                            \
+    int thip_##NAME##_set_iterates(thip_##NAME *h, int first, int count, const float *host_x, const float *host_y)                  \
+    { return ob_set_iterates(FAM, h, first, count, host_x, host_y); }                                                               \
     int thip_##NAME##_info(const thip_##NAME *h, thip_##NAME##_info_t *host_info) { return ob_info_out(h, host_info, FILL()); }       \
     int thip_test_##NAME##_force_threads(thip_##NAME *h, int threads) { return ob_force_threads(FAM, h, threads); }                 \
     }

@@ -70,6 +70,16 @@ __global__ __launch_bounds__(1024) void raggedbatch_k(const RbArgs a)
     mb_iterate_body(b, SpCones{ (int)(MbMap(b.n, b.m).bytes(b.m) / sizeof(float)) }, at);
 }
 
+// a problem starts from a given iterate (thip_raggedbatch_set_iterates): one launch per class, the problems by list
+struct RbStartArgs { RbArgs rb; ObStart s; };
+
+__global__ __launch_bounds__(1024) void raggedbatch_start_k(const RbStartArgs a)
+{
+    RbAt at;
+    const ObArgs b = rb_problem(a.rb, at);
+    mb_start_body(b, ob_staged(a.s), at);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RB_TEXT = { "ragged batch not initialised", "null ragged batch", "a ragged batch holds 1 .. 1048576 problems", nullptr,
@@ -79,8 +89,8 @@ const ObText RB_TEXT = { "ragged batch not initialised", "null ragged batch", "a
 int rb_launch_hook(const OwnBatch *h, bool run, const ObArgs &a, unsigned count);
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
-ObFamily RB_FAMILY = { RB_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, rb_launch_hook,
-                       { (const void *)raggedbatch_k, (const void *)raggedbatch_init_k, nullptr } };
+ObFamily RB_FAMILY = { RB_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, rb_launch_hook, nullptr,
+                       { (const void *)raggedbatch_k, (const void *)raggedbatch_init_k, (const void *)raggedbatch_start_k, nullptr } };
 
 struct RbProb { size_t n, m, lds; int layout, cls; };
 
@@ -191,6 +201,16 @@ int rg_launch(const thip_raggedbatch *h, bool run, int c, unsigned count, int st
     RbArgs a = rb_args(h);
     a.mb.steps = steps; a.mb.live = live; a.mb.first = first;
     hipLaunchKernelGGL(run ? raggedbatch_k : raggedbatch_init_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// class c's start kernel on the `count` problems of the list, workgroup k's iterate at s.at[k]
+int rg_start(const thip_raggedbatch *h, int c, unsigned count, const int *live, const ObStart &s)
+{
+    RbStartArgs a{ rb_args(h), s };
+    a.rb.mb.live = live;
+    hipLaunchKernelGGL(raggedbatch_start_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
@@ -353,6 +373,9 @@ int thip_raggedbatch_precond(thip_raggedbatch *h, int i, float *host_dp_tau, flo
 int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                              const float *dev_vec_b_rowabs)
 { return ob_replace(RB_FAMILY, h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs); }
+
+int thip_raggedbatch_set_iterates(thip_raggedbatch *h, int first, int count, const float *host_x, const float *host_y)
+{ return rg_set_iterates(RB_FAMILY, h, first, count, host_x, host_y); }
 
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info) { return rb_info(h, host_info); }
 int thip_raggedbatch_destroy(thip_raggedbatch *h) { return rb_destroy(h); }

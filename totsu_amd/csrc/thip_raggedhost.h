@@ -93,4 +93,60 @@ int rg_run(const ObText &tx, H *h, int64_t max_steps, int64_t poll_every, thip_s
     return 0;
 }
 
+// thip_NAME_set_iterates of a handle that launches by class: every length is the problem's own.  One upload -- where each
+// workgroup's iterate lies (in floats from the first one), the classes' lists side by side, the iterates -- and one launch per class
+// with a member in the range
+template <class H>
+int rg_set_iterates(const ObFamily &f, H *h, int first, int count, const float *host_x, const float *host_y)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_start_range(f, h, first, count, host_x, host_y));
+    const size_t cnt = (size_t)count, head = cnt * sizeof(long long) + ((cnt + 1) & ~(size_t)1) * sizeof(int);
+    std::vector<long long> at_p(cnt);
+    std::vector<int> members[2];
+    size_t floats = 0;
+    {
+        const float *x = host_x, *y = host_y;
+        for (size_t k = 0; k < cnt; ++k) {
+            const auto &q = h->pl.prob[(size_t)first + k];
+            THIP_RC(ob_start_scalars(x, y, q.n, q.m));
+            at_p[k] = (long long)floats;
+            members[q.cls].push_back(first + (int)k);
+            floats += 2 * q.n + 3 * q.m + 2;
+            x += q.n + 2 * q.m + 1; y += q.n + q.m + 1;
+        }
+    }
+    const size_t bytes = head + floats * sizeof(float);
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    unsigned char *const host = static_cast<unsigned char *>(pinned);
+    long long *const at = reinterpret_cast<long long *>(host);
+    int *const list = reinterpret_cast<int *>(host + cnt * sizeof(long long));
+    float *const it = reinterpret_cast<float *>(host + head);
+    {
+        const float *x = host_x, *y = host_y;
+        for (size_t k = 0; k < cnt; ++k) {
+            const auto &q = h->pl.prob[(size_t)first + k];
+            const size_t nx = q.n + 2 * q.m + 1, ny = q.n + q.m + 1;
+            memcpy(it + at_p[k], x, nx * sizeof(float));
+            memcpy(it + at_p[k] + nx, y, ny * sizeof(float));
+            x += nx; y += ny;
+        }
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c)
+            for (int p : members[c]) { list[k] = p; at[k] = at_p[(size_t)(p - first)]; ++k; }
+    }
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        const unsigned char *const dev = static_cast<const unsigned char *>(stage);
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (members[c].empty()) continue;
+            const ObStart s{ reinterpret_cast<const float *>(dev + head), reinterpret_cast<const long long *>(dev) + k, 0 };
+            THIP_RC(rg_start(h, c, (unsigned)members[c].size(), reinterpret_cast<const int *>(dev + cnt * sizeof(long long)) + k, s));
+            k += members[c].size();
+        }
+        return 0;
+    });
+}
+
 }  // namespace

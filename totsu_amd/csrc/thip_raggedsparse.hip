@@ -85,6 +85,18 @@ __global__ __launch_bounds__(1024) void raggedsparse_k(const RsArgs a)
     mb_iterate_body(b, SpCones{ (int)(MbMap(b.n, b.m).bytes(b.m) / sizeof(float)) }, at, mat);
 }
 
+// a problem starts from a given iterate (thip_raggedsparse_set_iterates): one launch per class, the problems by list, each
+// resident or streamed as its descriptor says
+struct RsStartArgs { RsArgs rs; ObStart s; };
+
+__global__ __launch_bounds__(1024) void raggedsparse_start_k(const RsStartArgs a)
+{
+    RbAt at;
+    SpbA mat;
+    const ObArgs b = rs_problem(a.rs, at, mat);
+    mb_start_body(b, ob_staged(a.s), at, mat);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RS_TEXT = { "ragged sparse batch not initialised", "null ragged sparse batch", "a ragged sparse batch holds 1 .. 1048576 problems",
@@ -95,8 +107,8 @@ int rs_launch_hook(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
 int rs_threads_unused(size_t, size_t) { return 1024; }       // (the table's thread choice knows no capacity: rs_classes decides)
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
-ObFamily RS_FAMILY = { RS_TEXT, { 256, 1024, 0 }, false, sp_check, rs_threads_unused, sp_lds_for, mb_stride, rs_launch_hook,
-                       { (const void *)raggedsparse_k, (const void *)raggedsparse_init_k, nullptr } };
+ObFamily RS_FAMILY = { RS_TEXT, { 256, 1024, 0 }, false, sp_check, rs_threads_unused, sp_lds_for, mb_stride, rs_launch_hook, nullptr,
+                       { (const void *)raggedsparse_k, (const void *)raggedsparse_init_k, (const void *)raggedsparse_start_k, nullptr } };
 
 struct RsProb {
     size_t n, m, cap, nnz;                  // cap: the entries the slot can take; nnz: those it was planned with
@@ -261,6 +273,16 @@ int rg_launch(const thip_raggedsparse *h, bool run, int c, unsigned count, int s
     RsArgs a = rs_args(h);
     a.mb.steps = steps; a.mb.live = live; a.mb.first = first;
     hipLaunchKernelGGL(run ? raggedsparse_k : raggedsparse_init_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// class c's start kernel on the `count` problems of the list, workgroup k's iterate at s.at[k]
+int rg_start(const thip_raggedsparse *h, int c, unsigned count, const int *live, const ObStart &s)
+{
+    RsStartArgs a{ rs_args(h), s };
+    a.rs.mb.live = live;
+    hipLaunchKernelGGL(raggedsparse_start_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
@@ -482,6 +504,9 @@ int thip_raggedsparse_replace(thip_raggedsparse *h, int i, const int64_t *host_c
     h->slot_used[(size_t)i] = (uint32_t)used;
     return 0;
 }
+
+int thip_raggedsparse_set_iterates(thip_raggedsparse *h, int first, int count, const float *host_x, const float *host_y)
+{ return rg_set_iterates(RS_FAMILY, h, first, count, host_x, host_y); }
 
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info) { return rs_info(h, host_info); }
 int thip_raggedsparse_destroy(thip_raggedsparse *h) { return rs_destroy(h); }

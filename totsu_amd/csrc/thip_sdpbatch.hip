@@ -39,6 +39,11 @@ __global__ __launch_bounds__(1024) void sdpbatch_init_k(const ObArgs a) { mb_ini
 
 __global__ __launch_bounds__(1024) void sdpbatch_k(const SpArgs a) { mb_iterate_body(a.mb, SpCones{ a.tail }); }
 
+// a problem starts from a given iterate (thip_sdpbatch_set_iterates): no cone is projected, the launch keeps the family's LDS size
+struct SpStartArgs { ObArgs mb; ObStart s; };
+
+__global__ __launch_bounds__(1024) void sdpbatch_start_k(const SpStartArgs a) { mb_start_body(a.mb, ob_staged(a.s)); }
+
 // thip_test_sdpbatch_project: the projection alone, one workgroup per packed matrix.  LDS: [shd 64][operands]
 __global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, float *rx)
 {
@@ -54,8 +59,14 @@ int sp_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
     return ob_launch(h, sdpbatch_k, SpArgs{ a, (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float)) }, count);
 }
 
-ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch,
-                       { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k } };
+int sp_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count)
+{
+    return ob_launch(h, sdpbatch_start_k, SpStartArgs{ a, s }, count);
+}
+
+ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch, sp_start,
+                       { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k,
+                         (const void *)sdpbatch_start_k } };
 
 // thip_midbatch_info_t's fields, and the PSD cones'
 struct SpInfo {

@@ -237,6 +237,28 @@ __global__ __launch_bounds__(1024) void smallbatch_k(const SbArgs a)
     if (tid == 0) s.store(gst);
 }
 
+// a problem starts from a given iterate (thip_smallbatch_set_iterates).  The three-pass recurrence carries no products, so the
+// workgroup writes the mutable part of the arena -- xx u kx ku | xy xs v ky ks kv, the Kahan terms zero -- and the status block
+struct SbStartArgs { SbArgs sb; ObStart s; };
+
+__global__ __launch_bounds__(1024) void smallbatch_start_k(const SbStartArgs a)
+{
+    const int p = ob_problem(a.sb.live, a.sb.first);
+    const int n = a.sb.n, m = a.sb.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const float *const x = ob_staged(a.s), *const y = x + n + 2 * m + 1;      // x_x x_y x_s tau | u v kappa
+    float *const ar = a.sb.arena + (size_t)p * a.sb.stride;
+    float *const gy = ar + 4 * n;
+    for (int i = tid; i < n; i += T) {
+        ar[i] = x[i]; ar[n + i] = y[i];
+        ar[2 * n + i] = 0.0f; ar[3 * n + i] = 0.0f;
+    }
+    for (int i = tid; i < m; i += T) {
+        gy[i] = x[n + i]; gy[m + i] = x[n + m + i]; gy[2 * m + i] = y[n + i];
+        gy[3 * m + i] = 0.0f; gy[4 * m + i] = 0.0f; gy[5 * m + i] = 0.0f;
+    }
+    if (tid == 0) ob_start_status(a.sb.st + p, x[n + 2 * m], y[n + m]);
+}
+
 const ObText SB_TEXT = { "small batch not initialised", "null small batch", "a small batch holds 1 .. 1048576 problems",
                          "a small batch takes no PSD segment", "the workgroup size is 64, 256 or 1024 (0: by shape)",
                          "thip_test_smallbatch_force_threads comes before thip_smallbatch_init" };
@@ -262,17 +284,27 @@ size_t sb_lds_for(size_t n, size_t m, int threads, const ObPsd &)
     return SbMap((int)n, (int)m, sb_lda((int)m), threads).bytes((int)m);
 }
 
-int sb_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
+SbArgs sb_args(const ObArgs &a)
 {
     SbArgs b{};
     b.n = a.n; b.m = a.m; b.lda = sb_lda(a.m);
     static_cast<ObCounts &>(b) = a;
     static_cast<ObRest &>(b) = a;
-    return ob_launch(h, run ? smallbatch_k : smallbatch_init_k, b, count);
+    return b;
 }
 
-ObFamily SB_FAMILY = { SB_TEXT, { 64, 256, 1024 }, false, sb_check, sb_threads_for, sb_lds_for, sb_stride, sb_launch,
-                       { (const void *)smallbatch_k, (const void *)smallbatch_init_k, nullptr } };
+int sb_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
+{
+    return ob_launch(h, run ? smallbatch_k : smallbatch_init_k, sb_args(a), count);
+}
+
+int sb_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count)
+{
+    return ob_launch(h, smallbatch_start_k, SbStartArgs{ sb_args(a), s }, count);
+}
+
+ObFamily SB_FAMILY = { SB_TEXT, { 64, 256, 1024 }, false, sb_check, sb_threads_for, sb_lds_for, sb_stride, sb_launch, sb_start,
+                       { (const void *)smallbatch_k, (const void *)smallbatch_init_k, (const void *)smallbatch_start_k, nullptr } };
 
 }  // namespace
 

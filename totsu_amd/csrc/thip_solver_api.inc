@@ -421,6 +421,48 @@ int thip_solver_iterate(thip_solver *s, float *host_x, float *host_y)
     return 0;
 }
 
+// thip_solver_set_iterate / thip_batch_set_iterate: the solver goes on from the given iterate instead of x = 0, y = 0, tau = 1.  What
+// snapshot(s, true) restores is the list: x_x (into whichever buffer is the iterate's now), u, x_y x_s v, the Kahan terms (zero: a
+// start hands none over), the status block, and hP -- with gP, by one pass over the stored form of A now in use (rebuild_carried)
+// (*retired: the iteration count the solver had reached, which the start resets)
+static int solver_set_iterate(thip_solver *s, const float *host_x, const float *host_y, long long *retired = nullptr)
+{
+    THIP_NEED_INIT();
+    if (!s || !s->inited) return fail(THIP_E_INVALID, "solver not initialised", __FILE__, __LINE__);
+    if (!host_x || !host_y) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    if (s->allreduce != nullptr || s->col_shard)
+        return fail(THIP_E_INVALID, "a start iterate is for one GPU: not with an all-reduce or a column shard", __FILE__, __LINE__);
+    const size_t n = s->n, m = s->m;
+    const float tau = host_x[n + 2 * m], kappa = host_y[n + m];
+    if (!(tau >= 0.0f) || tau - tau != 0.0f) return fail(THIP_E_INVALID, "a start's tau is finite and not negative", __FILE__, __LINE__);
+    if (!(kappa <= 0.0f) || kappa - kappa != 0.0f) return fail(THIP_E_INVALID, "a start's kappa is finite and not positive", __FILE__, __LINE__);
+    hipStream_t st = ctx().stream;
+    THIP_RC(poll(s, nullptr));                   // (synchronises; the host copy of the status block, whose constant part stays)
+    if (retired) *retired = s->hst->iter;
+    THIP_RC(thip_h2d(s->xx, host_x, n));
+    THIP_RC(thip_h2d(s->xy, host_x + n, m));
+    THIP_RC(thip_h2d(s->xs, host_x + n + m, m));
+    THIP_RC(thip_h2d(s->u, host_y, n));
+    THIP_RC(thip_h2d(s->v, host_y + n, m));
+    THIP_TRY(hipMemsetAsync(s->kx_home, 0, s->kahan_n * sizeof(float), st));     // (kx ku ky ks kv and the sweep's kx2)
+    DevStatus d = *s->hst;
+    d.stop = 0; d.state = THIP_ST_RUNNING; d.kind = 0; d.xbuf = s->xbuf; d.iter = 0; d.fault = 0;
+    d.cri[0] = d.cri[1] = d.cri[2] = 0.0f;
+    d.tau = tau; d.kappa = kappa; d.r_tau = 0.0f;
+    *s->hst = d;
+    THIP_TRY(hipMemcpyAsync(s->dst, s->hst, sizeof(DevStatus), hipMemcpyHostToDevice, st));
+    THIP_TRY(hipStreamSynchronize(st));
+    s->finalized = false;
+    s->status_pending = false;
+    s->sw_first = true;                          // the given iterate is a consistent one: the next sweep step starts from it
+    s->snap_iter = -1;
+    THIP_RC(rebuild_carried(s));
+    THIP_TRY(hipStreamSynchronize(st));          // (the host arrays are the caller's, and so is the moment the start has landed)
+    return 0;
+}
+
+int thip_solver_set_iterate(thip_solver *s, const float *host_x, const float *host_y) { return solver_set_iterate(s, host_x, host_y); }
+
 int thip_solver_precond(thip_solver *s, float *host_dp_tau, float *host_dp_sigma)
 {
     THIP_NEED_INIT();

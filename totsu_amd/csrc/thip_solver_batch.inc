@@ -417,6 +417,20 @@ int thip_batch_replace(thip_batch *b, int i, const float *dev_vec_b, const float
     return 0;
 }
 
+// slot i goes on from the given iterate (after thip_batch_init / _replace): what thip_solver_set_iterate does to one solver, on the
+// slot's instance -- its carried products by ONE single-vector pass over A for that slot -- and the slot is live again
+int thip_batch_set_iterate(thip_batch *b, int i, const float *host_x, const float *host_y)
+{
+    THIP_NEED_INIT();
+    if (!b || !b->inited) return fail(THIP_E_INVALID, "batch not initialised", __FILE__, __LINE__);
+    if (i < 0 || (size_t)i >= b->inst.size()) return fail(THIP_E_INVALID, "no such instance", __FILE__, __LINE__);
+    long long retired = 0;                      // the iterations the slot had made count on, as a replaced occupant's do
+    THIP_RC(solver_set_iterate(b->inst[(size_t)i], host_x, host_y, &retired));
+    b->ctr.instance_iterations += retired;
+    if (!b->live[(size_t)i]) { b->live[(size_t)i] = 1; b->ctr.live += 1; }
+    return 0;
+}
+
 int thip_batch_live_grouping(int n_inst, int max_group, const int *host_live, int *host_groups, int *host_group_sizes, int *host_members)
 {
     if (n_inst < 1 || n_inst > THIP_BATCH_MAX || (max_group != 2 && max_group != 4 && max_group != 8) || !host_live || !host_groups)

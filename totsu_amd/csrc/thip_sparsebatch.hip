@@ -28,6 +28,14 @@ __global__ __launch_bounds__(1024) void sparsebatch_k(const SpbArgs a)
     mb_iterate_body(a.mb, SpCones{ a.tail }, ObUniform(), SpbA{ a.at, a.resident });
 }
 
+// a problem starts from a given iterate (thip_sparsebatch_set_iterates): the pair A x_x, A^T x_y from the blob, resident or streamed
+struct SpbStartArgs { ObArgs mb; int at, resident; ObStart s; };
+
+__global__ __launch_bounds__(1024) void sparsebatch_start_k(const SpbStartArgs a)
+{
+    mb_start_body(a.mb, ob_staged(a.s), ObUniform(), SpbA{ a.at, a.resident });
+}
+
 __global__ void sparsebatch_slots_k(SbSlot *slots, int n_prob, const unsigned *blobs, size_t cap_words)
 {
     for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < (size_t)n_prob; p += (size_t)gridDim.x * blockDim.x)
@@ -72,10 +80,17 @@ int spb_launch(const OwnBatch *ob, bool run, const ObArgs &a, unsigned count)
     return ob_launch(ob, run ? sparsebatch_k : sparsebatch_init_k, s, count);
 }
 
+int spb_start(const OwnBatch *ob, const ObArgs &a, const ObStart &s, unsigned count)
+{
+    const thip_sparsebatch *h = static_cast<const thip_sparsebatch *>(ob);
+    const int tail = (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float));
+    return ob_launch(ob, sparsebatch_start_k, SpbStartArgs{ a, tail + (int)(h->psd.tail_bytes / sizeof(float)), h->resident, s }, count);
+}
+
 int spb_threads_unused(size_t, size_t) { return 1024; }      // (the table's thread choice knows no nnz_cap: spb_plan decides)
 
-ObFamily SPB_FAMILY = { SPB_TEXT, { 256, 1024, 0 }, false, sp_check, spb_threads_unused, sp_lds_for, mb_stride, spb_launch,
-                        { (const void *)sparsebatch_k, (const void *)sparsebatch_init_k, nullptr } };
+ObFamily SPB_FAMILY = { SPB_TEXT, { 256, 1024, 0 }, false, sp_check, spb_threads_unused, sp_lds_for, mb_stride, spb_launch, spb_start,
+                        { (const void *)sparsebatch_k, (const void *)sparsebatch_init_k, (const void *)sparsebatch_start_k, nullptr } };
 
 // the rule (no device needed): sp_check's on (n, m, layout); the blob is resident when it fits behind the vectors and the PSD tail
 int spb_fits(size_t n, size_t m, size_t nnz_cap, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -211,6 +226,8 @@ int thip_sparsebatch_solution(thip_sparsebatch *h, int i, float *host_x, float *
 int thip_sparsebatch_iterate(thip_sparsebatch *h, int i, float *host_x, float *host_y) { return ob_iterate(SPB_FAMILY, h, i, host_x, host_y); }
 int thip_sparsebatch_precond(thip_sparsebatch *h, int i, float *host_dp_tau, float *host_dp_sigma)
 { return ob_precond(SPB_FAMILY, h, i, host_dp_tau, host_dp_sigma); }
+int thip_sparsebatch_set_iterates(thip_sparsebatch *h, int first, int count, const float *host_x, const float *host_y)
+{ return ob_set_iterates(SPB_FAMILY, h, first, count, host_x, host_y); }
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info) { return ob_info_out(h, host_info, SpbInfo()); }
 
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,

@@ -3,6 +3,7 @@ operators are dense matrices -- what `Solver::solve` (solver.rs:285-321) does, w
 the projections and the termination test on the GPU.  Takes the stacked dense description produced by
 `ProbLP/ProbSOCP/ProbSDP.dense()` or device buffers generated in place (bench)."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -116,6 +117,42 @@ class FusedResult:
         self.cri = (st.cri[0], st.cri[1], st.cri[2])
         self.tau, self.kappa = st.tau, st.kappa
         self.norm_b, self.norm_c = st.norm_b, st.norm_c
+
+
+def _start_scalars(x, y, what=""):
+    """ValueError unless tau (the last entry of x) is finite and not negative and kappa (the last of y) finite and not positive: what the
+    library refuses too, said before anything is replaced or uploaded"""
+    tau, kappa = float(x[-1]), float(y[-1])
+    if not (math.isfinite(tau) and tau >= 0.0):
+        raise ValueError("%sa start's tau is finite and not negative, not %r" % (what, tau))
+    if not (math.isfinite(kappa) and kappa <= 0.0):
+        raise ValueError("%sa start's kappa is finite and not positive, not %r" % (what, kappa))
+
+
+def _start_arrays(n, m, x, y):
+    """a start (x, y) as contiguous float32 arrays of the lengths iterate() returns, its tau and kappa admissible; ValueError otherwise"""
+    x, y = np.ascontiguousarray(x, dtype=np.float32).ravel(), np.ascontiguousarray(y, dtype=np.float32).ravel()
+    if x.size != n + 2 * m + 1 or y.size != n + m + 1:
+        raise ValueError("a start holds x of %d and y of %d entries (x_x x_y x_s tau | u v kappa), not %d and %d"
+                         % (n + 2 * m + 1, n + m + 1, x.size, y.size))
+    _start_scalars(x, y)
+    return x, y
+
+
+def _checked(fn, *a):
+    try:
+        fn(*a)
+    except _lib.ThipError as e:
+        if e.code == _lib.E_INVALID:
+            raise ValueError(str(e)) from None
+        raise
+
+
+def _raw(xy, st):
+    x, y = xy
+    if st.kind == 0 and st.state in (_lib.ST_OK, _lib.ST_EXCESS_ITER):
+        x[:y.size - 1] *= x[-1]
+    return x, y
 
 
 class FusedSolver:
@@ -312,6 +349,22 @@ class FusedSolver:
         y = np.empty(self.n + self.m + 1, dtype=np.float32)
         lib.thip_solver_iterate(self.h, x.ctypes.data, y.ctypes.data)
         return x, y
+
+    def set_iterate(self, x, y):
+        """the solver goes on from the iterate (x, y) -- what iterate() returns while it runs, or raw_iterate() at any time -- instead of
+        x = 0, y = 0, tau = 1: iteration 0, running, the compensation terms zero; the norms and the preconditioner stay.  Any
+        schedule and any stored form of A on one GPU (the carried products cost one pass over A).  ValueError: a wrong length
+        (before anything is uploaded), a tau that is negative or not finite, a kappa that is positive or not finite, a solver
+        with an all-reduce or a column shard."""
+        x, y = _start_arrays(self.n, self.m, x, y)
+        _checked(lib.thip_solver_set_iterate, self.h, x.ctypes.data, y.ctypes.data)
+
+    def raw_iterate(self):
+        """iterate() with the read-out's final scaling undone: a solve that stopped with kind 0 in state OK / ExcessIter has its
+        x_x and x_y returned divided by tau, and this multiplies them by tau again (exact to one rounding); while the solver runs
+        it is iterate() itself.  It is what set_iterate expects from a finished solve.  The iteration is positively homogeneous,
+        so any positive multiple of the whole (x, y) is an equally valid start."""
+        return _raw(self.iterate(), self.status())
 
     def precond(self):
         t = np.empty(self.n + 2 * self.m + 1, dtype=np.float32)

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib
-from .fused import DeviceBuffer, FusedResult, _c_param
+from .fused import DeviceBuffer, FusedResult, _c_param, _checked, _raw, _start_scalars
 from .solver import SolverError, SolverParam
 
 
@@ -139,11 +139,13 @@ class OwnBatchSolver:
         (self._owned if owned is None else owned).append(d)
         return d
 
-    def replace(self, i, mat_a, vec_b, vec_c, vec_b_rowabs=None):
+    def replace(self, i, mat_a, vec_b, vec_c, vec_b_rowabs=None, start=None):
         """slot i -- running or stopped -- takes the problem (mat_a, vec_b, vec_c[, vec_b_rowabs]) as a fresh init; no other slot
-        is touched.  What the object had uploaded for the slot's previous replacement is freed after the call."""
+        is touched.  What the object had uploaded for the slot's previous replacement is freed after the call.  start: None, or the
+        (x, y) the new problem starts from (replace, then set_iterate)."""
         if not 0 <= int(i) < self.n_prob:
             raise ValueError("replace: no slot %r in a batch of %d" % (i, self.n_prob))
+        start = self._start_of(i, start)
         for name, v, want in (("mat_a", mat_a, self.m * self.n), ("vec_b", vec_b, self.m), ("vec_c", vec_c, self.n),
                               ("vec_b_rowabs", vec_b_rowabs, self.m)):
             if v is None:
@@ -165,6 +167,68 @@ class OwnBatchSolver:
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()
+        self._started(i, start)
+
+    def _lengths(self, i):
+        """the lengths of problem i's x and y as iterate(i) returns them"""
+        return self.n + 2 * self.m + 1, self.n + self.m + 1
+
+    def _start_of(self, i, start):
+        """replace's start argument, checked before anything is uploaded: None, or (x, y) as float32 arrays"""
+        if start is None:
+            return None
+        x, y = start
+        return self._iterates(int(i), [x], [y])
+
+    def _started(self, i, start):
+        if start is not None:
+            self._set_checked(int(i), 1, *start)
+
+    def _iterates(self, first, xs, ys):
+        """(the xs one after another, the ys likewise) for the problems from `first` on, every length, tau and kappa checked
+        (ValueError) -- before replace(start=) touches the slot"""
+        xs, ys = list(xs), list(ys)
+        if len(xs) != len(ys) or not xs:
+            raise ValueError("set_iterates: %d x where there are %d y (one pair per problem, at least one)" % (len(xs), len(ys)))
+        if not 0 <= int(first) <= int(first) + len(xs) <= self.n_prob:
+            raise ValueError("set_iterates: no problems %r .. %r in a batch of %d" % (first, int(first) + len(xs) - 1, self.n_prob))
+        out_x, out_y = [], []
+        for k, (x, y) in enumerate(zip(xs, ys)):
+            x, y = np.ascontiguousarray(x, dtype=np.float32).ravel(), np.ascontiguousarray(y, dtype=np.float32).ravel()
+            nx, ny = self._lengths(int(first) + k)
+            if x.size != nx or y.size != ny:
+                raise ValueError("problem %d: a start holds x of %d and y of %d entries (x_x x_y x_s tau | u v kappa), not %d and %d"
+                                 % (int(first) + k, nx, ny, x.size, y.size))
+            _start_scalars(x, y, "problem %d: " % (int(first) + k))
+            out_x.append(x)
+            out_y.append(y)
+        return np.concatenate(out_x), np.concatenate(out_y)
+
+    def _set_checked(self, first, count, x, y):
+        _checked(self._c("set_iterates"), self.h, int(first), int(count), x.ctypes.data, y.ctypes.data)
+
+    def set_iterates(self, xs, ys, first=0):
+        """problems first, first + 1, .. start from the iterates (xs[k], ys[k]) -- each what iterate() returns for a running problem
+        or raw_iterate() for any, in the problem's own lengths -- instead of x = 0, y = 0, tau = 1: iteration 0, running, the
+        compensation terms zero; the problem's data, norms and preconditioner stay.  One upload and one launch (one per
+        workgroup-size class in a ragged batch) for all of them.  ValueError: a wrong length (before anything is uploaded), a tau
+        that is negative or not finite, a kappa that is positive or not finite."""
+        xs = list(xs)
+        x, y = self._iterates(first, xs, ys)
+        self._set_checked(first, len(xs), x, y)
+
+    def set_iterate(self, i, x, y):
+        """set_iterates for problem i alone"""
+        if not 0 <= int(i) < self.n_prob:
+            raise ValueError("set_iterate: no problem %r in a batch of %d" % (i, self.n_prob))
+        self.set_iterates([x], [y], first=int(i))
+
+    def raw_iterate(self, i):
+        """iterate(i) with the read-out's final scaling undone: a problem that stopped with kind 0 in state OK / ExcessIter has its
+        x_x and x_y returned divided by tau, and this multiplies them by tau again (exact to one rounding); for a running problem
+        it is iterate(i) itself.  It is what set_iterate / replace(start=) expect from a finished solve.  The iteration is
+        positively homogeneous, so any positive multiple of the whole (x, y) is an equally valid start."""
+        return _raw(self.iterate(i), self.status(i))
 
     def reinit(self):
         """the family's init again: a fresh solve of every problem"""

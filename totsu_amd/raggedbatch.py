@@ -125,8 +125,8 @@ def pack(problems, kinds=_KINDS):
 
 
 class RaggedBatchSolver(OwnBatchSolver):
-    """run / run_until_any / status / solution / iterate / precond / replace / reinit / set_param / info / solve / destroy of
-    OwnBatchSolver, on thip_raggedbatch_*, with every length the problem's own.  `shapes`: [(n_p, m_p)].  force_threads: test hook
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / precond / replace / reinit / set_param / info /
+    solve / destroy of OwnBatchSolver, on thip_raggedbatch_*, with every length the problem's own.  `shapes`: [(n_p, m_p)].  force_threads: test hook
     (256, 1024: every problem in that one class)."""
     _prefix, _force_hook, _what = "thip_raggedbatch_", "thip_test_raggedbatch_force_threads", "ragged"
 
@@ -211,13 +211,15 @@ class RaggedBatchSolver(OwnBatchSolver):
         """one problem per Prob*.dense() of the list -- any mix of ProbLP / SOCP / SDP / QP / QCQP, with and without vec_b_rowabs"""
         return cls(list(denses), param, **kw)
 
-    def replace(self, i, mat_a, vec_b, vec_c, vec_b_rowabs=None):
-        """slot i -- running or stopped -- takes new data of ITS shape and cone layout as a fresh init; no other slot is touched"""
+    def replace(self, i, mat_a, vec_b, vec_c, vec_b_rowabs=None, start=None):
+        """slot i -- running or stopped -- takes new data of ITS shape and cone layout as a fresh init; no other slot is touched.
+        start: None, or the (x, y) the new problem starts from (replace, then set_iterate)"""
         if not 0 <= int(i) < self.n_prob:
             raise ValueError("replace: no slot %r in a batch of %d" % (i, self.n_prob))
         i, own = int(i), []
         n, m = self.shapes[i]
         self._check_lengths("replace: ", n, m, mat_a, vec_b, vec_c, vec_b_rowabs)
+        start = self._start_of(i, start)
         try:
             da, db, dc = self._dev(mat_a, own), self._dev(vec_b, own), self._dev(vec_c, own)
             dr = None if vec_b_rowabs is None else self._dev(vec_b_rowabs, own)
@@ -229,6 +231,11 @@ class RaggedBatchSolver(OwnBatchSolver):
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()
+        self._started(i, start)
+
+    def _lengths(self, i):
+        n, m = self._shape(i)
+        return n + 2 * m + 1, n + m + 1
 
     def _pair(self, name, i, nx, ny):
         x = np.empty(nx, dtype=np.float32)

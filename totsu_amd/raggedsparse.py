@@ -135,8 +135,8 @@ def plan(problems, nnz_caps=None, force_threads=None, force_resident=None):
 
 
 class RaggedSparseBatchSolver(RaggedBatchSolver):
-    """run / run_until_any / status / solution / iterate / precond / replace / reinit / set_param / info / solve / destroy of
-    OwnBatchSolver, on thip_raggedsparse_*, with every length the problem's own.  `shapes`: [(n_p, m_p)]; `nnz_caps`: the entries
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / precond / replace / reinit / set_param / info /
+    solve / destroy of OwnBatchSolver, on thip_raggedsparse_*, with every length the problem's own.  `shapes`: [(n_p, m_p)]; `nnz_caps`: the entries
     each slot can take.  force_threads (256, 1024: every problem in that one class) and force_resident (0: nobody resident, 1:
     everybody who fits) are test hooks.
 
@@ -218,11 +218,13 @@ class RaggedSparseBatchSolver(RaggedBatchSolver):
         """one problem per Prob*.dense() of the list -- any mix of ProbLP / SOCP / SDP / QP / QCQP --, its A taken as the entries != 0"""
         return cls([SparseProblem.of_dense(d) for d in denses], param, **kw)
 
-    def replace(self, i, mat, vec_b, vec_c, vec_b_rowabs=None):
+    def replace(self, i, mat, vec_b, vec_c, vec_b_rowabs=None, start=None):
         """slot i -- running or stopped -- takes another problem of ITS shape and cone layout, mat of any pattern with at most
-        nnz_caps[i] entries, as a fresh init; no other slot is touched, and a refusal leaves the slot as it was"""
+        nnz_caps[i] entries, as a fresh init; no other slot is touched, and a refusal leaves the slot as it was.  start: None, or the
+        (x, y) the new problem starts from (replace, then set_iterate)"""
         if not 0 <= int(i) < self.n_prob:
             raise ValueError("replace: no slot %r in a batch of %d" % (i, self.n_prob))
+        start = self._start_of(i, start)
         i, own = int(i), []
         n, m = self.shapes[i]
         try:
@@ -244,6 +246,7 @@ class RaggedSparseBatchSolver(RaggedBatchSolver):
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()
+        self._started(i, start)
 
     def info(self):
         o = _lib.RaggedSparseInfo()

@@ -186,11 +186,13 @@ class SparseBatchSolver(OwnBatchSolver):
         r = None if d0.vec_b_rowabs is None else np.stack([np.asarray(d.vec_b_rowabs, f).ravel() for d in denses])
         return cls(d0.n, d0.m, mats, b, c, d0.seg_type, d0.seg_len, param, vecs_b_rowabs=r, **kw)
 
-    def replace(self, i, mat, vec_b, vec_c, vec_b_rowabs=None):
+    def replace(self, i, mat, vec_b, vec_c, vec_b_rowabs=None, start=None):
         """slot i -- running or stopped -- takes the problem (mat, vec_b, vec_c[, vec_b_rowabs]) as a fresh init, mat of any pattern
-        with at most nnz_cap entries; no other slot is touched"""
+        with at most nnz_cap entries; no other slot is touched.  start: None, or the (x, y) the new problem starts from (replace,
+        then set_iterate)"""
         if not 0 <= int(i) < self.n_prob:
             raise ValueError("replace: no slot %r in a batch of %d" % (i, self.n_prob))
+        start = self._start_of(i, start)
         cp, ri, va = csc_of(mat, self.n, self.m)
         if int(cp[-1]) > self.nnz_cap:
             raise ValueError("replace: the problem holds %d entries where nnz_cap is %d" % (int(cp[-1]), self.nnz_cap))
@@ -215,3 +217,4 @@ class SparseBatchSolver(OwnBatchSolver):
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()
+        self._started(i, start)
