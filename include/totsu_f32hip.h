@@ -615,6 +615,33 @@ int thip_smallbatch_replace(thip_smallbatch *h, int i, const float *dev_mat_a, c
  * argument, a handle not initialised, a range outside the batch, count < 1, a tau that is negative or not finite, a kappa that is
  * positive or not finite; every other entry is the caller's, as A, b and c are.  The same under every thip_*batch prefix */
 int thip_smallbatch_set_iterates(thip_smallbatch *h, int first, int count, const float *host_x, const float *host_y);
+/* problems first .. first + count - 1 take a new b and c (and the row sums that go with b) and KEEP their A, which stays where it is on
+ * the device: no pass of A through the host or the bus, one upload, one launch (one per workgroup-size class where the problems have
+ * their own shapes) and one read of the range's status blocks for all of them; synchronous.  host_b: the problems' b one after
+ * another, m floats each (every length the problem's own); host_c: n each.  host_b_rowabs: m floats for every problem of the range,
+ * or NULL: no problem has row sums (|b| is used, as where _create was given none).  host_has_rowabs: one byte per problem, 0: the
+ * problem's part of host_b_rowabs is ignored (|b|), or NULL: all of them count.
+ * keep_iterate == 0: each problem ends exactly as thip_smallbatch_replace(i, its present A, b, c, rowabs) leaves it, bit for bit --
+ * preconditioner, norms, the zero iterate, iteration 0, RUNNING.  keep_iterate != 0: the preconditioner and the norms of the new
+ * data, and the iterate as it lies in the arena kept -- x_x, x_y, x_s, tau | u, v, kappa without the read-out's scaling -- with
+ * the Kahan terms, r_tau and the criteria zero, iteration 0, RUNNING again whether it was running or had stopped (a tau of 0
+ * included): what _replace followed by _set_iterates on the problem's own raw iterate gives, without either upload.  The streamed
+ * families keep the carried pair A x_x, A^T x_y, which depends on neither b nor c.
+ * The first call that is taken allocates the handle's own store of b, c and row sums for the whole batch (2 m + n floats per problem,
+ * counted in device_bytes, freed by _destroy); the kernel copies each problem's part there and points the slot's b, c and row sums
+ * at it -- the slot's A pointer is not touched -- and a later _replace points the slot back at the caller's arrays.  The data is
+ * packed into the staging buffers of _set_iterates.  THIP_E_INVALID, before anything is allocated, uploaded or changed: a null
+ * handle, a handle not initialised, a range outside the batch, count < 1, a null host_b or host_c.  Values are not examined, as
+ * _replace examines none.  The same under every thip_*batch prefix */
+int thip_smallbatch_set_bc(thip_smallbatch *h, int first, int count, const float *host_b, const float *host_c,
+                           const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+/* thip_smallbatch_solution of the problems first .. first + count - 1 in one read-out: a kernel gathers their x_x and x_y from the arena
+ * into the staging buffer, one copy brings that down and one the range's status blocks, and the host applies the final 1/tau scaling
+ * to each problem's part as _solution does -- the same bits.  host_x: n floats per problem, one after another (every length the
+ * problem's own); host_y: m each; either may be NULL, and with both NULL only the statuses are read.  host_status: count entries or
+ * NULL.  THIP_E_INVALID: a null handle, a handle not initialised, a range outside the batch, count < 1.  The same under every
+ * thip_*batch prefix */
+int thip_smallbatch_solutions(thip_smallbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
 int thip_smallbatch_destroy(thip_smallbatch *h);
 
@@ -657,6 +684,9 @@ int thip_midbatch_precond(thip_midbatch *h, int i, float *host_dp_tau, float *ho
 int thip_midbatch_replace(thip_midbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                           const float *dev_vec_b_rowabs);
 int thip_midbatch_set_iterates(thip_midbatch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_midbatch_set_bc(thip_midbatch *h, int first, int count, const float *host_b, const float *host_c,
+                         const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_midbatch_solutions(thip_midbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
@@ -699,6 +729,9 @@ int thip_sdpbatch_precond(thip_sdpbatch *h, int i, float *host_dp_tau, float *ho
 int thip_sdpbatch_replace(thip_sdpbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                           const float *dev_vec_b_rowabs);
 int thip_sdpbatch_set_iterates(thip_sdpbatch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_sdpbatch_set_bc(thip_sdpbatch *h, int first, int count, const float *host_b, const float *host_c,
+                         const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_sdpbatch_solutions(thip_sdpbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
@@ -758,6 +791,9 @@ int thip_raggedbatch_precond(thip_raggedbatch *h, int i, float *host_dp_tau, flo
 int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
                              const float *dev_vec_b_rowabs);
 int thip_raggedbatch_set_iterates(thip_raggedbatch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_raggedbatch_set_bc(thip_raggedbatch *h, int first, int count, const float *host_b, const float *host_c,
+                            const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
 int thip_raggedbatch_destroy(thip_raggedbatch *h);
 
@@ -816,6 +852,9 @@ int thip_sparsebatch_precond(thip_sparsebatch *h, int i, float *host_dp_tau, flo
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx,
                              const float *host_values, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs);
 int thip_sparsebatch_set_iterates(thip_sparsebatch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_sparsebatch_set_bc(thip_sparsebatch *h, int first, int count, const float *host_b, const float *host_c,
+                            const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_sparsebatch_solutions(thip_sparsebatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
 int thip_sparsebatch_destroy(thip_sparsebatch *h);
 
@@ -888,6 +927,9 @@ int thip_raggedsparse_replace(thip_raggedsparse *h, int i, const int64_t *host_c
                               const float *host_values, const float *dev_vec_b, const float *dev_vec_c,
                               const float *dev_vec_b_rowabs);
 int thip_raggedsparse_set_iterates(thip_raggedsparse *h, int first, int count, const float *host_x, const float *host_y);
+int thip_raggedsparse_set_bc(thip_raggedsparse *h, int first, int count, const float *host_b, const float *host_c,
+                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_raggedsparse_solutions(thip_raggedsparse *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info);
 int thip_raggedsparse_destroy(thip_raggedsparse *h);
 

@@ -317,6 +317,8 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "precond": (_i, [_vp, _i, _vp, _vp]),
         _p + "replace": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
         _p + "set_iterates": (_i, [_vp, _i, _i, _vp, _vp]),
+        _p + "set_bc": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
+        _p + "solutions": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(Status)]),
         _p + "info": (_i, [_vp, C.POINTER(_info)]),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
@@ -339,6 +341,8 @@ PROTOTYPES.update({
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": PROTOTYPES["thip_sdpbatch_replace"],
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
+    _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
+    _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
@@ -361,6 +365,8 @@ PROTOTYPES.update({
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": (_i, [_vp, _i, _p64, _p32, fp, _vp, _vp, _vp]),
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
+    _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
+    _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "info": (_i, [_vp, C.POINTER(SparseBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
@@ -385,6 +391,8 @@ PROTOTYPES.update({
     _p + "precond": PROTOTYPES["thip_sdpbatch_precond"],
     _p + "replace": PROTOTYPES["thip_sparsebatch_replace"],
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
+    _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
+    _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedSparseInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedsparse_force_threads": (_i, [_vp, _i]),

@@ -30,6 +30,11 @@ struct MbStartArgs { ObArgs mb; ObStart s; };
 
 __global__ __launch_bounds__(1024) void midbatch_start_k(const MbStartArgs a) { mb_start_body(a.mb, ob_staged(a.s)); }
 
+// a problem takes a new (b, c) and keeps its A (thip_midbatch_set_bc)
+struct MbSetBcArgs { ObArgs mb; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void midbatch_setbc_k(const MbSetBcArgs a) { mb_setbc_body(a.mb, a.s); }
+
 const ObText MB_TEXT = { "mid batch not initialised", "null mid batch", "a mid batch holds 1 .. 1048576 problems",
                          "a mid batch takes no PSD segment", "the workgroup size is 256 or 1024 (0: by shape)",
                          "thip_test_midbatch_force_threads comes before thip_midbatch_init" };
@@ -60,8 +65,14 @@ int mb_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned coun
     return ob_launch(h, midbatch_start_k, MbStartArgs{ a, s }, count);
 }
 
-ObFamily MB_FAMILY = { MB_TEXT, { 256, 1024, 0 }, true, mb_check, mb_threads_for, mb_lds_for, mb_stride, mb_launch, mb_start,
-                       { (const void *)midbatch_k, (const void *)midbatch_init_k, (const void *)midbatch_start_k, nullptr } };
+int mb_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count)
+{
+    return ob_launch(h, midbatch_setbc_k, MbSetBcArgs{ a, s }, count);
+}
+
+ObFamily MB_FAMILY = { MB_TEXT, { 256, 1024, 0 }, true, mb_check, mb_threads_for, mb_lds_for, mb_stride, mb_launch, mb_start, mb_setbc,
+                       { (const void *)midbatch_k, (const void *)midbatch_init_k, (const void *)midbatch_start_k,
+                         (const void *)midbatch_setbc_k, nullptr } };
 
 }  // namespace
 

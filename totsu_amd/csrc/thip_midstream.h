@@ -190,6 +190,18 @@ __device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT(
     }, at);
 }
 
+// ob_init_body on a staged (b, c), the |A| sums from the same pass: a problem takes a new (b, c) and keeps the A its slot points at
+template <class AT = ObUniform, class MAT = MbDenseA>
+__device__ __forceinline__ void mb_setbc_body(const ObArgs &a, const ObSetBc &sb, const AT &at = AT(), const MAT &mat = MAT())
+{
+    const int n = a.n, m = a.m;
+    const MbMap L(n, m);
+    float *S = mb_lds;
+    ob_init_body(a, at.problem(a), L, S, [&](const float *A) {
+        mat.template pass<true>(mat.open(A, m, n, S), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
+    }, at, ObTakeBc{ sb });
+}
+
 // `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
 // (called by every thread, after the second-order cones; hp, gp and g are dead there).  AT: which problem and where its arena block
 // lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor).  MAT: the matrix policy (above)

@@ -4,6 +4,8 @@
 //           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
 //           functions of the iteration that do not touch A (block_sums; thip_step.h: the arithmetic every loop shares).  The two recurrences -- three passes
 //           from LDS, two carried passes from memory -- stay with their families.
+//           The init body takes its b, c and row sums from the slot (init, replace) or from a staging area (set_bc: ObTakeBc);
+//           ownbatch_gather_k collects a range's x_x and x_y for one read-out (solutions).
 //   host:   slots, arena, all 64-byte status blocks in one copy, the live list, replace as the init kernel on one slot, and the C
 //           API itself: a family is a table (ObFamily: its words, its shape rule, its thread choice, its LDS map's size, its
 //           kernels) and one OB_DEFINE_API line that emits its extern "C" entry points over the generic bodies below.
@@ -130,14 +132,26 @@ struct ObScalars {
 // precond_k / group_min_k.  L: the family's LDS map (sh, b, c, g, h, Ty, Ts are used), S: the LDS.  abs_sums() leaves the row sums
 // of |A| in S[L.h ..] and the column sums in S[L.g ..], visible to every thread on return.  product_group takes the minimum over
 // every block cone, second-order or PSD.  What the family carries in the arena behind the preconditioner (the stride says how
-// much) starts at zero: A 0, A^T 0
-template <class ARGS, class MAP, class SUMS, class AT = ObUniform>
-__device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L, float *S, const SUMS &abs_sums, const AT &at = AT())
+// much) starts at zero: A 0, A^T 0.
+// SRC: where b, c and the row sums come from and how the body ends.  ObSlotData, the init kernels': they are the slot's, the state
+// starts at zero.  ObTakeBc (below), the set_bc kernels': they lie in a staging area and go into the handle's store, the A is the one
+// the slot points at, and the iterate may stay -- one text, so a problem that takes a new (b, c) gets the |A| sums, the cone minima
+// and the norms by the instructions an init on that data runs
+struct ObSlotData {
+    __device__ __forceinline__ SbSlot data(const SbSlot &sl, int, int, int, int, int) const { return sl; }
+    __device__ __forceinline__ bool keeps() const { return false; }
+    __device__ __forceinline__ void point(const SbSlot *, int, int, int, const SbSlot &) const {}
+};
+
+template <class ARGS, class MAP, class SUMS, class AT = ObUniform, class SRC = ObSlotData>
+__device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L, float *S, const SUMS &abs_sums, const AT &at = AT(),
+                                             const SRC &src = SRC())
 {
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
     const SbSlot sl = a.slots[p];
-    for (int i = tid; i < m; i += T) S[L.b + i] = sl.b[i];
-    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
+    const SbSlot d = src.data(sl, p, n, m, T, tid);       // (a, b, c, rowabs as the body reads them)
+    for (int i = tid; i < m; i += T) S[L.b + i] = d.b[i];
+    for (int i = tid; i < n; i += T) S[L.c + i] = d.c[i];
     __syncthreads();
     float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };              // sum b^2, sum |b|, sum c^2, sum |c|
     for (int i = tid; i < m; i += T) { const float t = S[L.b + i]; q[0] = fmaf(t, t, q[0]); q[1] += fabsf(t); }
@@ -151,7 +165,7 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
         gTx[i] = 1.0f / fmaxf(t, a.eps_zero);
     }
     for (int i = tid; i < m; i += T) {
-        const float t = S[L.h + i] + (sl.rowabs ? sl.rowabs[i] : fabsf(S[L.b + i]));
+        const float t = S[L.h + i] + (d.rowabs ? d.rowabs[i] : fabsf(S[L.b + i]));
         S[L.Ty + i] = 1.0f / fmaxf(t, a.eps_zero);
         S[L.Ts + i] = 1.0f / fmaxf(1.0f, a.eps_zero);
         gSv[i] = 1.0f / fmaxf(t + 1.0f, a.eps_zero);
@@ -172,14 +186,22 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
     }
     __syncthreads();
     for (int i = tid; i < m; i += T) { gTy[i] = S[L.Ty + i]; gTs[i] = S[L.Ts + i]; }
-    for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
-    const int ncar = at.carried(a, n, m);
-    for (int i = tid; i < ncar; i += T) gcar[i] = 0.0f;
+    const bool keep = src.keeps();
+    if (!keep) {
+        for (int i = tid; i < 4 * n + 6 * m; i += T) ar[i] = 0.0f;      // init_vecs: x = 0, y = 0 (and the Kahan terms)
+        const int ncar = at.carried(a, n, m);
+        for (int i = tid; i < ncar; i += T) gcar[i] = 0.0f;
+    } else {                                // the iterate and what is carried behind the preconditioner stay: the Kahan terms alone
+        float *const gy = ar + 4 * n;
+        for (int i = tid; i < 2 * n; i += T) ar[2 * n + i] = 0.0f;          // kx ku
+        for (int i = tid; i < 3 * m; i += T) gy[3 * m + i] = 0.0f;          // ky ks kv
+    }
     if (tid == 0) {
         SbStatus s;
         s.stop = 0; s.state = THIP_ST_RUNNING; s.kind = 0; s.pad = 0; s.iter = 0;
         s.cri[0] = s.cri[1] = s.cri[2] = 0.0f;
         s.tau = 1.0f; s.kappa = 0.0f; s.r_tau = 0.0f;
+        if (keep) { s.tau = a.st[p].tau; s.kappa = a.st[p].kappa; }
         const float nb = sqrtf(q[0]), nc = sqrtf(q[2]);      // fr_norm (solver.rs:85-107)
         s.norm_b = sqrtf(nb * nb);
         s.norm_c = sqrtf(nc * nc);
@@ -187,6 +209,7 @@ __device__ __forceinline__ void ob_init_body(const ARGS &a, int p, const MAP &L,
         s.t_tau = 1.0f / fmaxf(tau_tau, a.eps_zero);
         s.s_kappa = 1.0f / fmaxf(tau_tau, a.eps_zero);
         a.st[p] = s;
+        src.point(a.slots, p, n, m, d);
     }
 }
 
@@ -252,6 +275,57 @@ __device__ __forceinline__ void ob_start_status(SbStatus *g, float tau, float ka
     g->stop = 0;
 }
 
+// what a set_bc kernel is handed beside the family's launch arguments (thip_NAME_set_bc).  s: where the workgroups' new data lies in
+// the staging area, as a start kernel's iterates do; a problem's part is one word (!= 0: row sums follow) and then b (m), c (n) and
+// the row sums that go with b (m; ignored when the word is 0).  store: the handle's own b / c / rowabs of every problem, problem p's
+// 2 m + n floats (b, c, rowabs) at store + store_at[p], or (store_at == NULL: one shape) at store + p * store_per.  keep: the
+// iterate stays
+struct ObSetBc { ObStart s; float *store; const long long *store_at; long long store_per; int keep; };
+
+// ob_init_body's SRC of a problem that takes a new (b, c) and keeps its A.  data: the workgroup copies its part of the staging area
+// into the problem's place in the store and the body reads the staged values (the same floats).  keeps: keep == 0 is init's ending.
+// keep != 0: the iterate as it lies in the arena stays -- x_x, x_y, x_s | u, v, and tau, kappa in the status block -- the Kahan
+// terms go to zero and the status is that of a start: iteration 0, running, nothing judged; what a streamed family carries, A x_x
+// and A^T x_y, stays too: it is a function of A and the iterate alone, the pair a start kernel would form again from them.
+// point (one thread, last): the slot's b, c, rowabs point into the store from now on; its A pointer is not touched
+struct ObTakeBc {
+    ObSetBc sb;
+    __device__ __forceinline__ float *place(int p) const { return sb.store + (sb.store_at ? sb.store_at[p] : (long long)p * sb.store_per); }
+    __device__ __forceinline__ SbSlot data(const SbSlot &sl, int p, int n, int m, int T, int tid) const
+    {
+        const float *const part = ob_staged(sb.s);
+        const bool has_r = reinterpret_cast<const int *>(part)[0] != 0;
+        const float *const nb = part + 1, *const nc = nb + m, *const nr = nc + n;
+        float *const kb = place(p), *const kc = kb + m, *const kr = kc + n;
+        for (int i = tid; i < m; i += T) { kb[i] = nb[i]; if (has_r) kr[i] = nr[i]; }
+        for (int i = tid; i < n; i += T) kc[i] = nc[i];
+        return SbSlot{ sl.a, nb, nc, has_r ? nr : nullptr };
+    }
+    __device__ __forceinline__ bool keeps() const { return sb.keep != 0; }
+    __device__ __forceinline__ void point(const SbSlot *slots, int p, int n, int m, const SbSlot &d) const
+    {
+        float *const kb = place(p);
+        SbSlot ns;
+        ns.a = d.a; ns.b = kb; ns.c = kb + m; ns.rowabs = d.rowabs ? kb + m + n : nullptr;
+        const_cast<SbSlot *>(slots)[p] = ns;
+    }
+};
+
+// x_x and x_y of the problems of a range from the arena into one buffer (thip_NAME_solutions): workgroup k serves problem first + k,
+// whose block begins at arena + at[4 k] and whose n, m are at[4 k + 1], at[4 k + 2]; its x_x then x_y go to out + at[4 k + 3].
+// at == NULL: one shape -- arena + (first + k) * stride, n, m, out + k * (n + m)
+struct ObGather { const float *arena; const long long *at; size_t stride; int n, m, first; float *out; };
+
+__global__ __launch_bounds__(256) void ownbatch_gather_k(const ObGather g)
+{
+    const long long k = blockIdx.x;
+    const float *ar = g.at ? g.arena + g.at[4 * k] : g.arena + (size_t)(g.first + k) * g.stride;
+    const int n = g.at ? (int)g.at[4 * k + 1] : g.n, m = g.at ? (int)g.at[4 * k + 2] : g.m;
+    float *out = g.out + (g.at ? g.at[4 * k + 3] : k * (long long)(n + m));
+    for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) out[i] = ar[i];
+    for (int i = (int)threadIdx.x; i < m; i += (int)blockDim.x) out[n + i] = ar[4 * n + i];
+}
+
 __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,
                                  size_t m, size_t n)
 {
@@ -286,7 +360,8 @@ struct ObFamily {
     size_t (*stride_for)(size_t n, size_t m);
     int (*launch)(const OwnBatch *h, bool run, const ObArgs &a, unsigned count);      // the init kernel or the iteration
     int (*start)(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count);      // the start kernel (NULL: by class)
-    const void *kernels[4];                 // every kernel that asks for more than 64 KiB of LDS
+    int (*setbc)(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count);      // the set_bc kernel (NULL: by class)
+    const void *kernels[5];                 // every kernel that asks for more than 64 KiB of LDS
     size_t total = 0;                       // device memory held by every handle of the family
     std::once_flag attr_once;
     hipError_t attr_err = hipSuccess;
@@ -313,6 +388,9 @@ struct OwnBatch {
     ObPsd psd;
     // where set_iterates packs its iterates (pinned host memory) and where it uploads them: grown on demand, the handle's
     void *stage = nullptr, *stage_host = nullptr; size_t stage_bytes = 0;
+    // the handle's own b / c / rowabs of every problem, allocated by the first set_bc: problem p's 2 m_p + n_p floats at bc_at[p]
+    // (bc_at_dev: the same on the device, for a handle of many shapes; NULL: p * (2 m + n))
+    float *bc_store = nullptr; long long *bc_at_dev = nullptr;
     std::vector<unsigned char> unaligned;   // (a family that streams A) per slot: the problem's A is not 16-byte aligned
     size_t n_unaligned = 0;                 // how many: decides the load path info() reports
 };
@@ -491,7 +569,7 @@ int ob_destroy(H *h)
     if (!h) return 0;
     if (ctx().inited) hipStreamSynchronize(ctx().stream);
     hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
-    hipFree(h->stage);
+    hipFree(h->stage); hipFree(h->bc_store); hipFree(h->bc_at_dev);
     if (h->stage_host) hipHostFree(h->stage_host);
     if (h->hst) hipHostFree(h->hst);
     h->fam->total -= h->bytes;
@@ -722,6 +800,127 @@ int ob_set_iterates(const ObFamily &f, OwnBatch *h, int first, int count, const 
     });
 }
 
+// every refusal of a set_bc that needs no shape
+int ob_setbc_range(const ObFamily &f, const OwnBatch *h, int first, int count, const float *host_b, const float *host_c)
+{
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (!h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
+    if (!host_b || !host_c) return fail(THIP_E_INVALID, "null b or c", __FILE__, __LINE__);
+    if (count < 1 || first < 0 || (size_t)first + (size_t)count > h->n_prob)
+        return fail(THIP_E_INVALID, "no such range of problems", __FILE__, __LINE__);
+    return 0;
+}
+
+// the handle's own b / c / rowabs store, allocated by the first set_bc that is taken: `floats` for the whole batch, and (at != NULL:
+// a handle of many shapes) where each problem's part begins
+int ob_setbc_store(OwnBatch *h, size_t floats, const std::vector<long long> *at)
+{
+    if (h->bc_store) return 0;
+    if (at) {                               // (the offsets first: the store, which says that both are there, comes last)
+        if (!h->bc_at_dev) THIP_RC(ob_alloc(h, (void **)&h->bc_at_dev, at->size() * sizeof(long long)));
+        THIP_TRY(hipMemcpy(h->bc_at_dev, at->data(), at->size() * sizeof(long long), hipMemcpyHostToDevice));
+    }
+    return ob_alloc(h, (void **)&h->bc_store, floats * sizeof(float));
+}
+
+// one problem's part of a set_bc upload at `to`, 1 + 2 m + n floats: the word, b, c and the row sums.  r: the problem's row sums or
+// NULL
+void ob_setbc_pack(float *to, size_t n, size_t m, const float *b, const float *c, const float *r)
+{
+    const int has = r != nullptr;
+    memcpy(to, &has, sizeof(int));
+    memcpy(to + 1, b, m * sizeof(float));
+    memcpy(to + 1 + m, c, n * sizeof(float));
+    if (r) memcpy(to + 1 + m + n, r, m * sizeof(float));
+    else memset(to + 1 + m + n, 0, m * sizeof(float));
+}
+
+// thip_NAME_set_bc of a family of one shape: one upload, one launch
+int ob_set_bc(const ObFamily &f, OwnBatch *h, int first, int count, const float *host_b, const float *host_c, const float *host_r,
+              const uint8_t *host_has, int keep)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_setbc_range(f, h, first, count, host_b, host_c));
+    const size_t n = h->n, m = h->m, per = 1 + 2 * m + n, bytes = per * (size_t)count * sizeof(float);
+    THIP_RC(ob_setbc_store(h, (2 * m + n) * h->n_prob, nullptr));
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    float *const host = static_cast<float *>(pinned);
+    for (int k = 0; k < count; ++k) {
+        const bool has = host_r && (!host_has || host_has[k]);
+        ob_setbc_pack(host + (size_t)k * per, n, m, host_b + (size_t)k * m, host_c + (size_t)k * n, has ? host_r + (size_t)k * m : nullptr);
+    }
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        ObArgs a = ob_args(h);
+        a.first = first;
+        const ObSetBc s{ ObStart{ static_cast<const float *>(stage), nullptr, (long long)per }, h->bc_store, nullptr,
+                         (long long)(2 * m + n), keep != 0 };
+        return f.setbc(h, a, s, (unsigned)count);
+    });
+}
+
+// thip_NAME_solutions: the gather kernel on the range into the staging buffer (`at`: the table of a handle of many shapes, which goes
+// up in front of it; empty: one shape), one copy of that buffer and one of the range's status blocks down, and ob_finalize on each
+// problem's part -- what thip_NAME_solution does to its three copies.  shape(p, &n, &m), block(p): problem p's shape and where its
+// block of the arena begins, in floats.  Both of host_x and host_y NULL: the status blocks alone
+template <class SHAPE, class BLOCK>
+int ob_solutions_t(const ObFamily &f, OwnBatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status, bool table,
+                   const SHAPE &shape, const BLOCK &block)
+{
+    THIP_NEED_INIT();
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (!h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
+    if (count < 1 || first < 0 || (size_t)first + (size_t)count > h->n_prob)
+        return fail(THIP_E_INVALID, "no such range of problems", __FILE__, __LINE__);
+    hipStream_t st = ctx().stream;
+    const size_t cnt = (size_t)count, head = table ? cnt * 4 * sizeof(long long) : 0;
+    const bool vectors = host_x || host_y;
+    size_t floats = 0;
+    if (vectors) {
+        for (size_t k = 0; k < cnt; ++k) { size_t n, m; shape(first + (int)k, &n, &m); floats += n + m; }
+        void *pinned = nullptr;
+        THIP_RC(ob_stage_reserve(h, head + std::max<size_t>(floats, 1) * sizeof(float), &pinned));
+        unsigned char *const dev = static_cast<unsigned char *>(h->stage);
+        ObGather g{ h->arena, nullptr, h->stride, (int)h->n, (int)h->m, first, reinterpret_cast<float *>(dev + head) };
+        if (table) {
+            long long *at = static_cast<long long *>(pinned);
+            size_t o = 0;
+            for (size_t k = 0; k < cnt; ++k) {
+                size_t n, m;
+                shape(first + (int)k, &n, &m);
+                at[4 * k] = block(first + (int)k); at[4 * k + 1] = (long long)n; at[4 * k + 2] = (long long)m; at[4 * k + 3] = (long long)o;
+                o += n + m;
+            }
+            THIP_TRY(hipMemcpyAsync(dev, pinned, head, hipMemcpyHostToDevice, st));
+            g.at = reinterpret_cast<const long long *>(dev);
+        }
+        hipLaunchKernelGGL(ownbatch_gather_k, dim3((unsigned)count), dim3(256), 0, st, g);
+        THIP_LAUNCH_CHECK();
+        THIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(pinned) + head, dev + head, floats * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    THIP_TRY(hipMemcpyAsync(h->hst + first, h->dst + first, cnt * sizeof(SbStatus), hipMemcpyDeviceToHost, st));
+    THIP_TRY(hipStreamSynchronize(st));
+    const float *got = vectors ? reinterpret_cast<const float *>(static_cast<unsigned char *>(h->stage_host) + head) : nullptr;
+    for (size_t k = 0; k < cnt; ++k) {
+        const SbStatus &s = h->hst[(size_t)first + k];
+        if (vectors) {
+            size_t n, m;
+            shape(first + (int)k, &n, &m);
+            if (host_x) { memcpy(host_x, got, n * sizeof(float)); ob_finalize(s, host_x, n); host_x += n; }
+            if (host_y) { memcpy(host_y, got + n, m * sizeof(float)); ob_finalize(s, host_y, m); host_y += m; }
+            got += n + m;
+        }
+        if (host_status) ob_status_out(s, host_status + k);
+    }
+    return 0;
+}
+
+int ob_solutions(const ObFamily &f, OwnBatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
+{
+    return ob_solutions_t(f, h, first, count, host_x, host_y, host_status, false,
+                          [&](int, size_t *n, size_t *m) { *n = h->n; *m = h->m; }, [](int) { return 0ll; });
+}
+
 // the shape rules alone: the family's check (which fills *cones, *cls and *psd when they are given), its thread choice and the LDS of
 // one workgroup
 int ob_fits(const ObFamily &f, size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -842,6 +1041,11 @@ int ob_force_threads(const ObFamily &f, OwnBatch *h, int threads)
     { return ob_replace(FAM, h, i, dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs); }                                            \
     int thip_##NAME##_set_iterates(thip_##NAME *h, int first, int count, const float *host_x, const float *host_y)                  \
     { return ob_set_iterates(FAM, h, first, count, host_x, host_y); }                                                               \
+    int thip_##NAME##_set_bc(thip_##NAME *h, int first, int count, const float *host_b, const float *host_c,                        \
+                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate)                          \
+    { return ob_set_bc(FAM, h, first, count, host_b, host_c, host_b_rowabs, host_has_rowabs, keep_iterate); }                       \
+    int thip_##NAME##_solutions(thip_##NAME *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)       \
+    { return ob_solutions(FAM, h, first, count, host_x, host_y, host_status); }                                                     \
     int thip_##NAME##_info(const thip_##NAME *h, thip_##NAME##_info_t *host_info) { return ob_info_out(h, host_info, FILL()); }       \
     int thip_test_##NAME##_force_threads(thip_##NAME *h, int threads) { return ob_force_threads(FAM, h, threads); }                 \
     }

@@ -80,6 +80,16 @@ __global__ __launch_bounds__(1024) void raggedbatch_start_k(const RbStartArgs a)
     mb_start_body(b, ob_staged(a.s), at);
 }
 
+// a problem takes a new (b, c) and keeps its A (thip_raggedbatch_set_bc): one launch per class, the problems by list
+struct RbSetBcArgs { RbArgs rb; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void raggedbatch_setbc_k(const RbSetBcArgs a)
+{
+    RbAt at;
+    const ObArgs b = rb_problem(a.rb, at);
+    mb_setbc_body(b, a.s, at);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RB_TEXT = { "ragged batch not initialised", "null ragged batch", "a ragged batch holds 1 .. 1048576 problems", nullptr,
@@ -90,7 +100,9 @@ int rb_launch_hook(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
 ObFamily RB_FAMILY = { RB_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, rb_launch_hook, nullptr,
-                       { (const void *)raggedbatch_k, (const void *)raggedbatch_init_k, (const void *)raggedbatch_start_k, nullptr } };
+                       nullptr,
+                       { (const void *)raggedbatch_k, (const void *)raggedbatch_init_k, (const void *)raggedbatch_start_k,
+                         (const void *)raggedbatch_setbc_k, nullptr } };
 
 struct RbProb { size_t n, m, lds; int layout, cls; };
 
@@ -211,6 +223,16 @@ int rg_start(const thip_raggedbatch *h, int c, unsigned count, const int *live, 
     RbStartArgs a{ rb_args(h), s };
     a.rb.mb.live = live;
     hipLaunchKernelGGL(raggedbatch_start_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// class c's set_bc kernel on the `count` problems of the list, workgroup k's data at s.s.at[k]
+int rg_setbc(const thip_raggedbatch *h, int c, unsigned count, const int *live, const ObSetBc &s)
+{
+    RbSetBcArgs a{ rb_args(h), s };
+    a.rb.mb.live = live;
+    hipLaunchKernelGGL(raggedbatch_setbc_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
@@ -376,6 +398,13 @@ int thip_raggedbatch_replace(thip_raggedbatch *h, int i, const float *dev_mat_a,
 
 int thip_raggedbatch_set_iterates(thip_raggedbatch *h, int first, int count, const float *host_x, const float *host_y)
 { return rg_set_iterates(RB_FAMILY, h, first, count, host_x, host_y); }
+
+int thip_raggedbatch_set_bc(thip_raggedbatch *h, int first, int count, const float *host_b, const float *host_c,
+                            const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate)
+{ return rg_set_bc(RB_FAMILY, h, first, count, host_b, host_c, host_b_rowabs, host_has_rowabs, keep_iterate); }
+
+int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
+{ return rg_solutions(RB_FAMILY, h, first, count, host_x, host_y, host_status); }
 
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info) { return rb_info(h, host_info); }
 int thip_raggedbatch_destroy(thip_raggedbatch *h) { return rb_destroy(h); }

@@ -149,4 +149,72 @@ int rg_set_iterates(const ObFamily &f, H *h, int first, int count, const float *
     });
 }
 
+// thip_NAME_set_bc of a handle that launches by class: every length is the problem's own.  One upload -- where each workgroup's
+// data lies (in floats from the first part), the classes' lists side by side, the parts -- and one launch per class with a member
+// in the range.  The handle's store is packed by problem, 2 m_p + n_p floats each
+template <class H>
+int rg_set_bc(const ObFamily &f, H *h, int first, int count, const float *host_b, const float *host_c, const float *host_r,
+              const uint8_t *host_has, int keep)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_setbc_range(f, h, first, count, host_b, host_c));
+    const size_t cnt = (size_t)count, head = cnt * sizeof(long long) + ((cnt + 1) & ~(size_t)1) * sizeof(int);
+    std::vector<long long> at_p(cnt);
+    std::vector<int> members[2];
+    size_t floats = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+        const auto &q = h->pl.prob[(size_t)first + k];
+        at_p[k] = (long long)floats;
+        members[q.cls].push_back(first + (int)k);
+        floats += 1 + 2 * q.m + q.n;
+    }
+    if (!h->bc_store) {
+        std::vector<long long> store_at(h->n_prob);
+        size_t total = 0;
+        for (size_t p = 0; p < h->n_prob; ++p) { store_at[p] = (long long)total; total += 2 * h->pl.prob[p].m + h->pl.prob[p].n; }
+        THIP_RC(ob_setbc_store(h, total, &store_at));
+    }
+    const size_t bytes = head + floats * sizeof(float);
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    unsigned char *const host = static_cast<unsigned char *>(pinned);
+    long long *const at = reinterpret_cast<long long *>(host);
+    int *const list = reinterpret_cast<int *>(host + cnt * sizeof(long long));
+    float *const parts = reinterpret_cast<float *>(host + head);
+    {
+        const float *b = host_b, *c = host_c, *r = host_r;
+        for (size_t k = 0; k < cnt; ++k) {
+            const auto &q = h->pl.prob[(size_t)first + k];
+            const bool has = host_r && (!host_has || host_has[k]);
+            ob_setbc_pack(parts + at_p[k], q.n, q.m, b, c, has ? r : nullptr);
+            b += q.m; c += q.n;
+            if (r) r += q.m;
+        }
+        size_t k = 0;
+        for (int c2 = 0; c2 < 2; ++c2)
+            for (int p : members[c2]) { list[k] = p; at[k] = at_p[(size_t)(p - first)]; ++k; }
+    }
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        const unsigned char *const dev = static_cast<const unsigned char *>(stage);
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (members[c].empty()) continue;
+            const ObSetBc s{ ObStart{ reinterpret_cast<const float *>(dev + head), reinterpret_cast<const long long *>(dev) + k, 0 },
+                             h->bc_store, h->bc_at_dev, 0, keep != 0 };
+            THIP_RC(rg_setbc(h, c, (unsigned)members[c].size(), reinterpret_cast<const int *>(dev + cnt * sizeof(long long)) + k, s));
+            k += members[c].size();
+        }
+        return 0;
+    });
+}
+
+// thip_NAME_solutions of a handle of many shapes: the gather kernel by a table of the range's blocks, shapes and places
+template <class H>
+int rg_solutions(const ObFamily &f, H *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
+{
+    return ob_solutions_t(f, h, first, count, host_x, host_y, host_status, true,
+                          [&](int p, size_t *n, size_t *m) { *n = h->pl.prob[(size_t)p].n; *m = h->pl.prob[(size_t)p].m; },
+                          [&](int p) { return (long long)h->pl.desc[(size_t)p].arena_at; });
+}
+
 }  // namespace

@@ -97,6 +97,18 @@ __global__ __launch_bounds__(1024) void raggedsparse_start_k(const RsStartArgs a
     mb_start_body(b, ob_staged(a.s), at, mat);
 }
 
+// a problem takes a new (b, c) and keeps its blob (thip_raggedsparse_set_bc): one launch per class, the problems by list, each
+// resident or streamed as its descriptor says
+struct RsSetBcArgs { RsArgs rs; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void raggedsparse_setbc_k(const RsSetBcArgs a)
+{
+    RbAt at;
+    SpbA mat;
+    const ObArgs b = rs_problem(a.rs, at, mat);
+    mb_setbc_body(b, a.s, at, mat);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RS_TEXT = { "ragged sparse batch not initialised", "null ragged sparse batch", "a ragged sparse batch holds 1 .. 1048576 problems",
@@ -108,7 +120,9 @@ int rs_threads_unused(size_t, size_t) { return 1024; }       // (the table's thr
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
 ObFamily RS_FAMILY = { RS_TEXT, { 256, 1024, 0 }, false, sp_check, rs_threads_unused, sp_lds_for, mb_stride, rs_launch_hook, nullptr,
-                       { (const void *)raggedsparse_k, (const void *)raggedsparse_init_k, (const void *)raggedsparse_start_k, nullptr } };
+                       nullptr,
+                       { (const void *)raggedsparse_k, (const void *)raggedsparse_init_k, (const void *)raggedsparse_start_k,
+                         (const void *)raggedsparse_setbc_k, nullptr } };
 
 struct RsProb {
     size_t n, m, cap, nnz;                  // cap: the entries the slot can take; nnz: those it was planned with
@@ -283,6 +297,16 @@ int rg_start(const thip_raggedsparse *h, int c, unsigned count, const int *live,
     RsStartArgs a{ rs_args(h), s };
     a.rs.mb.live = live;
     hipLaunchKernelGGL(raggedsparse_start_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// class c's set_bc kernel on the `count` problems of the list, workgroup k's data at s.s.at[k]
+int rg_setbc(const thip_raggedsparse *h, int c, unsigned count, const int *live, const ObSetBc &s)
+{
+    RsSetBcArgs a{ rs_args(h), s };
+    a.rs.mb.live = live;
+    hipLaunchKernelGGL(raggedsparse_setbc_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
@@ -507,6 +531,13 @@ int thip_raggedsparse_replace(thip_raggedsparse *h, int i, const int64_t *host_c
 
 int thip_raggedsparse_set_iterates(thip_raggedsparse *h, int first, int count, const float *host_x, const float *host_y)
 { return rg_set_iterates(RS_FAMILY, h, first, count, host_x, host_y); }
+
+int thip_raggedsparse_set_bc(thip_raggedsparse *h, int first, int count, const float *host_b, const float *host_c,
+                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate)
+{ return rg_set_bc(RS_FAMILY, h, first, count, host_b, host_c, host_b_rowabs, host_has_rowabs, keep_iterate); }
+
+int thip_raggedsparse_solutions(thip_raggedsparse *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
+{ return rg_solutions(RS_FAMILY, h, first, count, host_x, host_y, host_status); }
 
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info) { return rs_info(h, host_info); }
 int thip_raggedsparse_destroy(thip_raggedsparse *h) { return rs_destroy(h); }

@@ -44,6 +44,11 @@ struct SpStartArgs { ObArgs mb; ObStart s; };
 
 __global__ __launch_bounds__(1024) void sdpbatch_start_k(const SpStartArgs a) { mb_start_body(a.mb, ob_staged(a.s)); }
 
+// a problem takes a new (b, c) and keeps its A (thip_sdpbatch_set_bc): no cone is projected, the launch keeps the family's LDS size
+struct SpSetBcArgs { ObArgs mb; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void sdpbatch_setbc_k(const SpSetBcArgs a) { mb_setbc_body(a.mb, a.s); }
+
 // thip_test_sdpbatch_project: the projection alone, one workgroup per packed matrix.  LDS: [shd 64][operands]
 __global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, float *rx)
 {
@@ -64,9 +69,15 @@ int sp_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned coun
     return ob_launch(h, sdpbatch_start_k, SpStartArgs{ a, s }, count);
 }
 
-ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch, sp_start,
+int sp_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count)
+{
+    return ob_launch(h, sdpbatch_setbc_k, SpSetBcArgs{ a, s }, count);
+}
+
+// (the fifth entry of the table's kernels is this family's: the projection probe asks for the large LDS too)
+ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch, sp_start, sp_setbc,
                        { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k,
-                         (const void *)sdpbatch_start_k } };
+                         (const void *)sdpbatch_start_k, (const void *)sdpbatch_setbc_k } };
 
 // thip_midbatch_info_t's fields, and the PSD cones'
 struct SpInfo {

@@ -259,6 +259,21 @@ __global__ __launch_bounds__(1024) void smallbatch_start_k(const SbStartArgs a)
     if (tid == 0) ob_start_status(a.sb.st + p, x[n + 2 * m], y[n + m]);
 }
 
+// a problem takes a new (b, c) and keeps its A (thip_smallbatch_set_bc): ob_init_body on the staged data, the |A| sums from LDS
+struct SbSetBcArgs { SbArgs sb; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void smallbatch_setbc_k(const SbSetBcArgs a)
+{
+    const int n = a.sb.n, m = a.sb.m, lda = a.sb.lda;
+    const SbMap L(n, m, lda, (int)blockDim.x);
+    float *S = sb_lds;
+    ob_init_body(a.sb, ob_problem(a.sb.live, a.sb.first), L, S, [&](const float *src) {
+        load_a(src, S + L.A, m, n, lda);
+        __syncthreads();
+        products<true>(S + L.A, lda, m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.red);
+    }, ObUniform(), ObTakeBc{ a.s });
+}
+
 const ObText SB_TEXT = { "small batch not initialised", "null small batch", "a small batch holds 1 .. 1048576 problems",
                          "a small batch takes no PSD segment", "the workgroup size is 64, 256 or 1024 (0: by shape)",
                          "thip_test_smallbatch_force_threads comes before thip_smallbatch_init" };
@@ -303,8 +318,14 @@ int sb_start(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned coun
     return ob_launch(h, smallbatch_start_k, SbStartArgs{ sb_args(a), s }, count);
 }
 
-ObFamily SB_FAMILY = { SB_TEXT, { 64, 256, 1024 }, false, sb_check, sb_threads_for, sb_lds_for, sb_stride, sb_launch, sb_start,
-                       { (const void *)smallbatch_k, (const void *)smallbatch_init_k, (const void *)smallbatch_start_k, nullptr } };
+int sb_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count)
+{
+    return ob_launch(h, smallbatch_setbc_k, SbSetBcArgs{ sb_args(a), s }, count);
+}
+
+ObFamily SB_FAMILY = { SB_TEXT, { 64, 256, 1024 }, false, sb_check, sb_threads_for, sb_lds_for, sb_stride, sb_launch, sb_start, sb_setbc,
+                       { (const void *)smallbatch_k, (const void *)smallbatch_init_k, (const void *)smallbatch_start_k,
+                         (const void *)smallbatch_setbc_k, nullptr } };
 
 }  // namespace
 

@@ -36,6 +36,14 @@ __global__ __launch_bounds__(1024) void sparsebatch_start_k(const SpbStartArgs a
     mb_start_body(a.mb, ob_staged(a.s), ObUniform(), SpbA{ a.at, a.resident });
 }
 
+// a problem takes a new (b, c) and keeps its blob (thip_sparsebatch_set_bc): the |A| sums from the blob, resident or streamed
+struct SpbSetBcArgs { ObArgs mb; int at, resident; ObSetBc s; };
+
+__global__ __launch_bounds__(1024) void sparsebatch_setbc_k(const SpbSetBcArgs a)
+{
+    mb_setbc_body(a.mb, a.s, ObUniform(), SpbA{ a.at, a.resident });
+}
+
 __global__ void sparsebatch_slots_k(SbSlot *slots, int n_prob, const unsigned *blobs, size_t cap_words)
 {
     for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < (size_t)n_prob; p += (size_t)gridDim.x * blockDim.x)
@@ -89,8 +97,17 @@ int spb_start(const OwnBatch *ob, const ObArgs &a, const ObStart &s, unsigned co
 
 int spb_threads_unused(size_t, size_t) { return 1024; }      // (the table's thread choice knows no nnz_cap: spb_plan decides)
 
+int spb_setbc(const OwnBatch *ob, const ObArgs &a, const ObSetBc &s, unsigned count)
+{
+    const thip_sparsebatch *h = static_cast<const thip_sparsebatch *>(ob);
+    const int tail = (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float));
+    return ob_launch(ob, sparsebatch_setbc_k, SpbSetBcArgs{ a, tail + (int)(h->psd.tail_bytes / sizeof(float)), h->resident, s }, count);
+}
+
 ObFamily SPB_FAMILY = { SPB_TEXT, { 256, 1024, 0 }, false, sp_check, spb_threads_unused, sp_lds_for, mb_stride, spb_launch, spb_start,
-                        { (const void *)sparsebatch_k, (const void *)sparsebatch_init_k, (const void *)sparsebatch_start_k, nullptr } };
+                        spb_setbc,
+                        { (const void *)sparsebatch_k, (const void *)sparsebatch_init_k, (const void *)sparsebatch_start_k,
+                          (const void *)sparsebatch_setbc_k, nullptr } };
 
 // the rule (no device needed): sp_check's on (n, m, layout); the blob is resident when it fits behind the vectors and the PSD tail
 int spb_fits(size_t n, size_t m, size_t nnz_cap, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -228,6 +245,11 @@ int thip_sparsebatch_precond(thip_sparsebatch *h, int i, float *host_dp_tau, flo
 { return ob_precond(SPB_FAMILY, h, i, host_dp_tau, host_dp_sigma); }
 int thip_sparsebatch_set_iterates(thip_sparsebatch *h, int first, int count, const float *host_x, const float *host_y)
 { return ob_set_iterates(SPB_FAMILY, h, first, count, host_x, host_y); }
+int thip_sparsebatch_set_bc(thip_sparsebatch *h, int first, int count, const float *host_b, const float *host_c,
+                            const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate)
+{ return ob_set_bc(SPB_FAMILY, h, first, count, host_b, host_c, host_b_rowabs, host_has_rowabs, keep_iterate); }
+int thip_sparsebatch_solutions(thip_sparsebatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
+{ return ob_solutions(SPB_FAMILY, h, first, count, host_x, host_y, host_status); }
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info) { return ob_info_out(h, host_info, SpbInfo()); }
 
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,

@@ -45,6 +45,44 @@ def first_that_takes(families, n, m, seg_type, seg_len, refusal):
     raise ValueError(refusal % (m, n, last)) from None
 
 
+def pack_bc(n_prob, shape_of, vecs_b, vecs_c, vecs_b_rowabs=None, first=0):
+    """the arrays thip_NAME_set_bc takes (needs no handle and no GPU): (count, b, c, rowabs or None, has or None) for the problems
+    first, first + 1, .. of a batch of n_prob whose problem i has the shape shape_of(i) = (n_i, m_i).  b: every vecs_b[k] one after
+    another as float32, c likewise; rowabs: m floats for every problem (zeros where vecs_b_rowabs[k] is None), or None when
+    vecs_b_rowabs is None or every entry of it is; has: one byte per problem, 1 where the problem has row sums, or None when all or
+    none have.  ValueError: no problem, lists of different lengths, a range outside the batch, a vector of the wrong length (the
+    message names the problem)"""
+    vecs_b, vecs_c = list(vecs_b), list(vecs_c)
+    count, first = len(vecs_b), int(first)
+    if count < 1 or len(vecs_c) != count:
+        raise ValueError("set_bc: %d b where there are %d c (one pair per problem, at least one)" % (count, len(vecs_c)))
+    rows = [None] * count if vecs_b_rowabs is None else list(vecs_b_rowabs)
+    if len(rows) != count:
+        raise ValueError("set_bc: %d vecs_b_rowabs where there are %d b (one entry per problem, None: |b|)" % (len(rows), count))
+    if not 0 <= first <= first + count <= int(n_prob):
+        raise ValueError("set_bc: no problems %r .. %r in a batch of %d" % (first, first + count - 1, n_prob))
+    bs, cs, rs, has = [], [], [], np.zeros(count, dtype=np.uint8)
+    for k, (b, c, r) in enumerate(zip(vecs_b, vecs_c, rows)):
+        n, m = shape_of(first + k)
+        b, c = np.ascontiguousarray(b, dtype=np.float32).ravel(), np.ascontiguousarray(c, dtype=np.float32).ravel()
+        if b.size != m or c.size != n:
+            raise ValueError("problem %d: b holds %d and c %d entries where m = %d and n = %d are needed" % (first + k, b.size, c.size, m, n))
+        if r is None:
+            r = np.zeros(m, dtype=np.float32)
+        else:
+            r = np.ascontiguousarray(r, dtype=np.float32).ravel()
+            if r.size != m:
+                raise ValueError("problem %d: vec_b_rowabs holds %d entries where m = %d are needed" % (first + k, r.size, m))
+            has[k] = 1
+        bs.append(b)
+        cs.append(c)
+        rs.append(r)
+    b, c = np.concatenate(bs), np.concatenate(cs)
+    if not has.any():
+        return count, b, c, None, None
+    return count, b, c, np.concatenate(rs), None if has.all() else has
+
+
 class OwnBatchSolver:
     # what a family of own-A batches differs in (the subclasses set these)
     _prefix = _force_hook = _what = _Info = None
@@ -222,6 +260,53 @@ class OwnBatchSolver:
         if not 0 <= int(i) < self.n_prob:
             raise ValueError("set_iterate: no problem %r in a batch of %d" % (i, self.n_prob))
         self.set_iterates([x], [y], first=int(i))
+
+    def _nm(self, i):
+        """problem i's own (n, m)"""
+        return self.n, self.m
+
+    def set_bc(self, vecs_b, vecs_c, vecs_b_rowabs=None, first=0, keep_iterate=False):
+        """problems first, first + 1, .. take the new vecs_b[k], vecs_c[k] (lists or 2-D arrays of host vectors, each in the problem's
+        own m / n) and KEEP their A, which stays on the device: one upload, one launch (one per workgroup-size class in a ragged
+        batch) and one read of the status blocks for all of them.  vecs_b_rowabs: None, or a list whose entries may each be None
+        (|b| of the new b).  keep_iterate=False: each problem ends exactly as replace(i, its present A, b, c, rowabs) leaves it --
+        a fresh init, iteration 0, running.  keep_iterate=True: the preconditioner and norms of the new data, and the iterate as it
+        lies on the device kept (x_x x_y x_s tau | u v kappa, no read-out scaling; the compensation terms zero): iteration 0 and
+        running again, whether the problem was running or had stopped -- a warm start of every problem of the range without
+        reading an iterate out.  The first call allocates the batch's own store of b, c and row sums on the device (info()'s
+        device_bytes).  ValueError: a wrong length (before anything is uploaded; the message names the problem), a range outside
+        the batch."""
+        count, b, c, r, has = pack_bc(self.n_prob, self._nm, vecs_b, vecs_c, vecs_b_rowabs, first)
+        _checked(self._c("set_bc"), self.h, int(first), count, b.ctypes.data, c.ctypes.data, None if r is None else r.ctypes.data,
+                 None if has is None else has.ctypes.data, 1 if keep_iterate else 0)
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.n_prob - first if count is None else int(count)
+        if not (0 <= first and 1 <= count and first + count <= self.n_prob):
+            raise ValueError("no problems %r .. %r in a batch of %d" % (first, first + count - 1, self.n_prob))
+        return first, count
+
+    def solutions(self, first=0, count=None):
+        """[solution(i) for the problems first .. first + count - 1] (count None: to the end), bit for bit, in one read-out: a
+        kernel gathers every x and y of the range into one buffer, which comes down in one copy beside the status blocks"""
+        first, count = self._range(first, count)
+        shapes = [self._nm(first + k) for k in range(count)]
+        x = np.empty(sum(n for n, _ in shapes), dtype=np.float32)
+        y = np.empty(sum(m for _, m in shapes), dtype=np.float32)
+        _checked(self._c("solutions"), self.h, first, count, x.ctypes.data, y.ctypes.data, None)
+        out, ox, oy = [], 0, 0
+        for n, m in shapes:
+            out.append((x[ox:ox + n].copy(), y[oy:oy + m].copy()))
+            ox, oy = ox + n, oy + m
+        return out
+
+    def statuses(self, first=0, count=None):
+        """[status(i) for the problems first .. first + count - 1] (count None: to the end) from one copy of their status blocks"""
+        first, count = self._range(first, count)
+        st = (_lib.Status * count)()
+        _checked(self._c("solutions"), self.h, first, count, None, None, st)
+        return [FusedResult(s) for s in st]
 
     def raw_iterate(self, i):
         """iterate(i) with the read-out's final scaling undone: a problem that stopped with kind 0 in state OK / ExcessIter has its

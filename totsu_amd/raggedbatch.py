@@ -125,8 +125,8 @@ def pack(problems, kinds=_KINDS):
 
 
 class RaggedBatchSolver(OwnBatchSolver):
-    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / precond / replace / reinit / set_param / info /
-    solve / destroy of OwnBatchSolver, on thip_raggedbatch_*, with every length the problem's own.  `shapes`: [(n_p, m_p)].  force_threads: test hook
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / solutions / statuses / precond /
+    replace / reinit / set_param / info / solve / destroy of OwnBatchSolver, on thip_raggedbatch_*, with every length the problem's own.  `shapes`: [(n_p, m_p)].  force_threads: test hook
     (256, 1024: every problem in that one class)."""
     _prefix, _force_hook, _what = "thip_raggedbatch_", "thip_test_raggedbatch_force_threads", "ragged"
 
@@ -236,6 +236,10 @@ class RaggedBatchSolver(OwnBatchSolver):
     def _lengths(self, i):
         n, m = self._shape(i)
         return n + 2 * m + 1, n + m + 1
+
+    def _nm(self, i):
+        """(set_bc, solutions: every length is the problem's own)"""
+        return self.shapes[int(i)]
 
     def _pair(self, name, i, nx, ny):
         x = np.empty(nx, dtype=np.float32)
