@@ -642,6 +642,33 @@ int thip_smallbatch_set_bc(thip_smallbatch *h, int first, int count, const float
  * NULL.  THIP_E_INVALID: a null handle, a handle not initialised, a range outside the batch, count < 1.  The same under every
  * thip_*batch prefix */
 int thip_smallbatch_solutions(thip_smallbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+/* problems first .. first + count - 1 take NEW VALUES of A and keep their shape, cone layout, b, c and row sums (and, a sparse
+ * family, their pattern): a round of a successive linearisation, a time-varying model, a re-weighted relaxation in one call and
+ * one launch (one per workgroup-size class where the problems have their own shapes); synchronous.  host_values: the problems'
+ * values one after another.  A dense family (smallbatch, midbatch, sdpbatch, raggedbatch): the problem's own m n floats,
+ * column-major, as _create and _replace take them.  A sparse family (sparsebatch, raggedsparse): the values in the CSC order of the
+ * slot's PRESENT pattern, as many as the slot holds now -- the host_values a (colptr, rowidx, values) triple of that pattern would
+ * carry; explicit zeros stay entries.  host_counts: count entries, how many values each problem brings, or NULL: exactly what it
+ * needs; a count that differs from m n (dense) or from the slot's present entry count (sparse) is refused -- another pattern is
+ * _replace's.
+ * WHERE THE VALUES GO.  Dense: into the memory the slot's A pointer points at, OVERWRITTEN IN PLACE -- the buffer handed to _create
+ * or _replace is written by _set_a; the host copies straight to the slots' addresses, one copy per run of slots that lie one behind
+ * the other (a batch as created is one run); no second store of A is made, device_bytes does not grow and the alignment, so the
+ * 16-byte or 4-byte load path, is what it was.  Sparse: one upload of 4 bytes per entry into the staging buffers of _set_iterates,
+ * and a kernel writes both stored orders of each blob on the device (a launch of its own ahead of the next).
+ * keep_iterate == 0: each problem ends exactly as _replace(i, the new A, its present b, c, rowabs) leaves it, bit for bit.
+ * keep_iterate != 0: the preconditioner and the norms of the new data; x_x, x_y, x_s, tau | u, v, kappa stay as they lie in the
+ * arena, the Kahan terms, r_tau and the criteria are zero, iteration 0, RUNNING again whether the problem was running or had
+ * stopped; the streamed families form the carried pair A x_x, A^T x_y again from the new A.  For a running problem that is
+ * _replace(i, new A, ..) followed by _set_iterates on its own iterate, bit for bit.  b, c and the row sums are read where the slot
+ * points now -- the caller's arrays, or the handle's store after a _set_bc -- and never moved; _set_a(keep) followed by
+ * _set_bc(keep) is a round that moves all three.
+ * THIP_E_INVALID, before anything is uploaded or touched (every problem's readable state is unchanged): a null handle, a handle not
+ * initialised, a range outside the batch, count < 1, null values, a wrong count (the message names the problem), a value that is
+ * not finite.  Not done: values taken from device memory, a change of pattern (_replace).  The same under every thip_*batch
+ * prefix and thip_raggedsparse */
+int thip_smallbatch_set_a(thip_smallbatch *h, int first, int count, const float *host_values, const int64_t *host_counts,
+                          int keep_iterate);
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
 int thip_smallbatch_destroy(thip_smallbatch *h);
 
@@ -687,6 +714,7 @@ int thip_midbatch_set_iterates(thip_midbatch *h, int first, int count, const flo
 int thip_midbatch_set_bc(thip_midbatch *h, int first, int count, const float *host_b, const float *host_c,
                          const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_midbatch_solutions(thip_midbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_midbatch_set_a(thip_midbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
 int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
@@ -732,6 +760,7 @@ int thip_sdpbatch_set_iterates(thip_sdpbatch *h, int first, int count, const flo
 int thip_sdpbatch_set_bc(thip_sdpbatch *h, int first, int count, const float *host_b, const float *host_c,
                          const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_sdpbatch_solutions(thip_sdpbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_sdpbatch_set_a(thip_sdpbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
 int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
@@ -794,6 +823,7 @@ int thip_raggedbatch_set_iterates(thip_raggedbatch *h, int first, int count, con
 int thip_raggedbatch_set_bc(thip_raggedbatch *h, int first, int count, const float *host_b, const float *host_c,
                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_raggedbatch_set_a(thip_raggedbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
 int thip_raggedbatch_destroy(thip_raggedbatch *h);
 
@@ -855,6 +885,7 @@ int thip_sparsebatch_set_iterates(thip_sparsebatch *h, int first, int count, con
 int thip_sparsebatch_set_bc(thip_sparsebatch *h, int first, int count, const float *host_b, const float *host_c,
                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_sparsebatch_solutions(thip_sparsebatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_sparsebatch_set_a(thip_sparsebatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
 int thip_sparsebatch_destroy(thip_sparsebatch *h);
 
@@ -930,6 +961,7 @@ int thip_raggedsparse_set_iterates(thip_raggedsparse *h, int first, int count, c
 int thip_raggedsparse_set_bc(thip_raggedsparse *h, int first, int count, const float *host_b, const float *host_c,
                              const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_raggedsparse_solutions(thip_raggedsparse *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_raggedsparse_set_a(thip_raggedsparse *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info);
 int thip_raggedsparse_destroy(thip_raggedsparse *h);
 

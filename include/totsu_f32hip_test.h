@@ -268,6 +268,11 @@ int thip_test_sparsebatch_force_threads(thip_sparsebatch *h, int threads);
  * not fit beside the vectors).  Before thip_sparsebatch_init. */
 int thip_test_sparsebatch_force_resident(thip_sparsebatch *h, int resident);
 
+/* TEST HOOK: slot i's blob as it lies on the device (what thip_sparsebatch_create / _replace packed, or thip_sparsebatch_set_a
+ * scattered new values into): host_used_words receives the words it uses; host_words (may be NULL): cap_words words to receive them.
+ * THIP_E_INVALID: a null handle, no such problem, fewer words offered than used. */
+int thip_test_sparsebatch_blob(thip_sparsebatch *h, int i, uint32_t *host_words, size_t cap_words, size_t *host_used_words);
+
 /* TEST HOOK: the blob thip_sparsebatch_create would store for one problem given as host CSC arrays (needs no device), with every
  * refusal of the stored form (nnz_cap: 0 = m n).  host_used_words: the words the blob uses; host_words (may be NULL): cap_words words
  * to receive them; host_long (may be NULL): the row length above which a row is summed by a wave. */
@@ -277,6 +282,9 @@ int thip_test_sparsebatch_pack(size_t n, size_t m, const int64_t *host_colptr, c
 /* TEST HOOK: the workgroup size of a ragged sparse batch (thip_raggedsparse.hip): 256 or 1024 threads put every problem in that one
  * class, 0 = by the sparse batch's rule.  Before thip_raggedsparse_init. */
 int thip_test_raggedsparse_force_threads(thip_raggedsparse *h, int threads);
+
+/* TEST HOOK: thip_test_sparsebatch_blob for a ragged sparse batch. */
+int thip_test_raggedsparse_blob(thip_raggedsparse *h, int i, uint32_t *host_words, size_t cap_words, size_t *host_used_words);
 
 /* TEST HOOK: who of a ragged sparse batch reads its blob from LDS: 0 nobody, 1 everybody who fits (the rule).  Before
  * thip_raggedsparse_init. */

@@ -358,6 +358,7 @@ extern "C" {
     pub fn thip_smallbatch_set_iterates(h: *mut thip_smallbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_smallbatch_set_bc(h: *mut thip_smallbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_smallbatch_solutions(h: *mut thip_smallbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_smallbatch_set_a(h: *mut thip_smallbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_smallbatch_info(h: *const thip_smallbatch, host_info: *mut thip_smallbatch_info_t) -> c_int;
     pub fn thip_smallbatch_destroy(h: *mut thip_smallbatch) -> c_int;
     pub fn thip_test_smallbatch_force_threads(h: *mut thip_smallbatch, threads: c_int) -> c_int;
@@ -381,6 +382,7 @@ extern "C" {
     pub fn thip_midbatch_set_iterates(h: *mut thip_midbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_midbatch_set_bc(h: *mut thip_midbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_midbatch_solutions(h: *mut thip_midbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_midbatch_set_a(h: *mut thip_midbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_midbatch_info(h: *const thip_midbatch, host_info: *mut thip_midbatch_info_t) -> c_int;
     pub fn thip_midbatch_destroy(h: *mut thip_midbatch) -> c_int;
     pub fn thip_test_midbatch_force_threads(h: *mut thip_midbatch, threads: c_int) -> c_int;
@@ -404,6 +406,7 @@ extern "C" {
     pub fn thip_sdpbatch_set_iterates(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_sdpbatch_set_bc(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_sdpbatch_solutions(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sdpbatch_set_a(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_sdpbatch_info(h: *const thip_sdpbatch, host_info: *mut thip_sdpbatch_info_t) -> c_int;
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
@@ -432,6 +435,7 @@ extern "C" {
     pub fn thip_raggedbatch_set_iterates(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_raggedbatch_set_bc(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedbatch_solutions(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedbatch_set_a(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedbatch_info(h: *const thip_raggedbatch, host_info: *mut thip_raggedbatch_info_t) -> c_int;
     pub fn thip_raggedbatch_destroy(h: *mut thip_raggedbatch) -> c_int;
     pub fn thip_test_raggedbatch_force_threads(h: *mut thip_raggedbatch, threads: c_int) -> c_int;
@@ -460,10 +464,12 @@ extern "C" {
     pub fn thip_sparsebatch_set_iterates(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_sparsebatch_set_bc(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_sparsebatch_solutions(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_sparsebatch_set_a(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_sparsebatch_info(h: *const thip_sparsebatch, host_info: *mut thip_sparsebatch_info_t) -> c_int;
     pub fn thip_sparsebatch_destroy(h: *mut thip_sparsebatch) -> c_int;
     pub fn thip_test_sparsebatch_force_threads(h: *mut thip_sparsebatch, threads: c_int) -> c_int;
     pub fn thip_test_sparsebatch_force_resident(h: *mut thip_sparsebatch, resident: c_int) -> c_int;
+    pub fn thip_test_sparsebatch_blob(h: *mut thip_sparsebatch, i: c_int, host_words: *mut u32, cap_words: usize, host_used_words: *mut usize) -> c_int;
     pub fn thip_test_sparsebatch_pack(n: usize, m: usize, host_colptr: *const i64, host_rowidx: *const i32, host_values: *const f32,
                                       nnz_cap: usize, host_words: *mut u32, cap_words: usize, host_used_words: *mut usize,
                                       host_long: *mut c_int) -> c_int;
@@ -492,10 +498,12 @@ extern "C" {
     pub fn thip_raggedsparse_set_iterates(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
     pub fn thip_raggedsparse_set_bc(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedsparse_solutions(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_raggedsparse_set_a(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedsparse_info(h: *const thip_raggedsparse, host_info: *mut thip_raggedsparse_info_t) -> c_int;
     pub fn thip_raggedsparse_destroy(h: *mut thip_raggedsparse) -> c_int;
     pub fn thip_test_raggedsparse_force_threads(h: *mut thip_raggedsparse, threads: c_int) -> c_int;
     pub fn thip_test_raggedsparse_force_resident(h: *mut thip_raggedsparse, resident: c_int) -> c_int;
+    pub fn thip_test_raggedsparse_blob(h: *mut thip_raggedsparse, i: c_int, host_words: *mut u32, cap_words: usize, host_used_words: *mut usize) -> c_int;
     pub fn thip_test_raggedsparse_plan(n_prob: usize, host_n: *const usize, host_m: *const usize, host_nnz: *const usize,
                                        host_nnz_cap: *const usize, host_n_seg: *const usize, host_seg_type: *const i32,
                                        host_seg_len: *const i64, force_threads: c_int, force_resident: c_int, host_class: *mut c_int,

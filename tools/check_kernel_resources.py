@@ -45,6 +45,8 @@ looks up in a table, resident or streamed per problem:
 
     raggedsparse_k and raggedsparse_init_k: the sparse batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
 
+Each family's set_a kernel (*_seta_k; the sparse families' *_scatter_k too) is required and held to its family's bounds as well.
+
 usage: check_kernel_resources.py <remarks file> [--report]
                                  [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch|
                                           raggedsparse]"""
@@ -104,12 +106,12 @@ def check_gemv_multi(res):
 # the own-A batch families: kernel-name regex, the kernels that must be present, the VGPR cap (None: the occupancy bound alone),
 # the kernel's description and its source file for the message
 OWNBATCH = {
-    "smallbatch": (r"smallbatch(_init|_start)?_k", ("smallbatch_k", "smallbatch_init_k", "smallbatch_start_k"), None, "on-chip small-batch", "thip_smallbatch.hip"),
-    "midbatch": (r"midbatch(_init|_start)?_k", ("midbatch_k", "midbatch_init_k", "midbatch_start_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
-    "sdpbatch": (r"sdpbatch(_init|_project|_start)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
-    "raggedbatch": (r"raggedbatch(_init|_start)?_k", ("raggedbatch_k", "raggedbatch_init_k", "raggedbatch_start_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
-    "sparsebatch": (r"sparsebatch(_init|_start)?_k", ("sparsebatch_k", "sparsebatch_init_k", "sparsebatch_start_k"), 128, "sparse batch", "thip_sparsebatch.hip"),
-    "raggedsparse": (r"raggedsparse(_init|_start)?_k", ("raggedsparse_k", "raggedsparse_init_k", "raggedsparse_start_k"), 128, "ragged sparse batch",
+    "smallbatch": (r"smallbatch(_init|_start|_seta)?_k", ("smallbatch_k", "smallbatch_init_k", "smallbatch_start_k", "smallbatch_seta_k"), None, "on-chip small-batch", "thip_smallbatch.hip"),
+    "midbatch": (r"midbatch(_init|_start|_seta)?_k", ("midbatch_k", "midbatch_init_k", "midbatch_start_k", "midbatch_seta_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
+    "sdpbatch": (r"sdpbatch(_init|_project|_start|_seta)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k", "sdpbatch_seta_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
+    "raggedbatch": (r"raggedbatch(_init|_start|_seta)?_k", ("raggedbatch_k", "raggedbatch_init_k", "raggedbatch_start_k", "raggedbatch_seta_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
+    "sparsebatch": (r"sparsebatch(_init|_start|_seta|_scatter)?_k", ("sparsebatch_k", "sparsebatch_init_k", "sparsebatch_start_k", "sparsebatch_seta_k", "sparsebatch_scatter_k"), 128, "sparse batch", "thip_sparsebatch.hip"),
+    "raggedsparse": (r"raggedsparse(_init|_start|_seta|_scatter)?_k", ("raggedsparse_k", "raggedsparse_init_k", "raggedsparse_start_k", "raggedsparse_seta_k", "raggedsparse_scatter_k"), 128, "ragged sparse batch",
                      "thip_raggedsparse.hip"),
 }
 

@@ -319,6 +319,7 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "set_iterates": (_i, [_vp, _i, _i, _vp, _vp]),
         _p + "set_bc": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
         _p + "solutions": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(Status)]),
+        _p + "set_a": (_i, [_vp, _i, _i, _vp, _vp, _i]),
         _p + "info": (_i, [_vp, C.POINTER(_info)]),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
@@ -343,6 +344,7 @@ PROTOTYPES.update({
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
+    _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
@@ -367,10 +369,12 @@ PROTOTYPES.update({
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
+    _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
     _p + "info": (_i, [_vp, C.POINTER(SparseBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
     "thip_test_sparsebatch_force_resident": (_i, [_vp, _i]),
+    "thip_test_sparsebatch_blob": (_i, [_vp, _i, C.POINTER(C.c_uint32), _sz, _psz]),
     "thip_test_sparsebatch_pack": (_i, [_sz, _sz, _p64, _p32, fp, _sz, C.POINTER(C.c_uint32), _sz, _psz, C.POINTER(_i)]),
 })
 
@@ -393,10 +397,12 @@ PROTOTYPES.update({
     _p + "set_iterates": PROTOTYPES["thip_sdpbatch_set_iterates"],
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
+    _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedSparseInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedsparse_force_threads": (_i, [_vp, _i]),
     "thip_test_raggedsparse_force_resident": (_i, [_vp, _i]),
+    "thip_test_raggedsparse_blob": (_i, [_vp, _i, C.POINTER(C.c_uint32), _sz, _psz]),
     "thip_test_raggedsparse_plan": (_i, [_sz, _psz, _psz, _psz, _psz, _psz, _p32, _p64, _i, _i, _pi, _pi, _pi, _p64, _p64, _pi, _pi,
                                          C.POINTER(RaggedSparseInfo)]),
 })

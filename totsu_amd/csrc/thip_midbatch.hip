@@ -35,6 +35,11 @@ struct MbSetBcArgs { ObArgs mb; ObSetBc s; };
 
 __global__ __launch_bounds__(1024) void midbatch_setbc_k(const MbSetBcArgs a) { mb_setbc_body(a.mb, a.s); }
 
+// a problem's A has new values (thip_midbatch_set_a)
+struct MbSetAArgs { ObArgs mb; int keep; };
+
+__global__ __launch_bounds__(1024) void midbatch_seta_k(const MbSetAArgs a) { mb_seta_body(a.mb, a.keep); }
+
 const ObText MB_TEXT = { "mid batch not initialised", "null mid batch", "a mid batch holds 1 .. 1048576 problems",
                          "a mid batch takes no PSD segment", "the workgroup size is 256 or 1024 (0: by shape)",
                          "thip_test_midbatch_force_threads comes before thip_midbatch_init" };
@@ -70,9 +75,15 @@ int mb_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned coun
     return ob_launch(h, midbatch_setbc_k, MbSetBcArgs{ a, s }, count);
 }
 
+int mb_seta(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count)
+{
+    return ob_launch(h, midbatch_seta_k, MbSetAArgs{ a, s.keep }, count);
+}
+
 ObFamily MB_FAMILY = { MB_TEXT, { 256, 1024, 0 }, true, mb_check, mb_threads_for, mb_lds_for, mb_stride, mb_launch, mb_start, mb_setbc,
+                       mb_seta,
                        { (const void *)midbatch_k, (const void *)midbatch_init_k, (const void *)midbatch_start_k,
-                         (const void *)midbatch_setbc_k, nullptr } };
+                         (const void *)midbatch_setbc_k, (const void *)midbatch_seta_k, nullptr } };
 
 }  // namespace
 

@@ -342,6 +342,34 @@ __device__ __forceinline__ void mb_start_body(const ObArgs &a, const float *it, 
     if (tid == 0) ob_start_status(a.st + p, x[n + 2 * m], y[n + m]);
 }
 
+// a problem's A has new values (thip_NAME_set_a): ob_init_body on the slot's own b, c and row sums with the |A| sums from one pass
+// over the A that lies behind the slot's pointer now, the ending taken from the call (ObKeepA).  keep == 0: init's ending, the
+// carried pair zero.  keep != 0: the pair depends on A, so it is formed again from the iterate that stays in the arena -- x_x and
+// x_y into the map, then h = A x_x, g = A^T x_y by the call the iteration's second pass makes, as mb_start_body forms it (restated
+// here: that body is left as it compiles) -- and written behind the preconditioner.  The matrix is opened once, ahead of the body:
+// a resident blob stays in LDS for both passes (the body touches neither its place nor the PSD tail in front of it)
+template <class AT = ObUniform, class MAT = MbDenseA>
+__device__ __forceinline__ void mb_seta_body(const ObArgs &a, int keep, const AT &at = AT(), const MAT &mat = MAT())
+{
+    const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
+    const int p = at.problem(a);
+    const MbMap L(n, m);
+    float *S = mb_lds;
+    const auto A = mat.open(a.slots[p].a, m, n, S);
+    ob_init_body(a, p, L, S, [&](const float *) {
+        mat.template pass<true>(A, m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
+    }, at, ObKeepA{ keep });
+    if (keep == 0) return;                                  // (uniform: a launch argument)
+    float *const xx = S + L.xx, *const xy = S + L.xy, *const h = S + L.h, *const g = S + L.g;
+    float *const ar = at.block(a, p);
+    for (int i = tid; i < n; i += T) xx[i] = ar[i];         // (the body's keep ending writes the Kahan terms alone)
+    for (int i = tid; i < m; i += T) xy[i] = ar[4 * n + i];
+    mat.template pass<false>(A, m, n, xx, xy, h, g, S + L.hp, S + L.gp);
+    float *const gcar = ar + 5 * n + 9 * m;
+    for (int i = tid; i < m; i += T) gcar[i] = h[i];
+    for (int i = tid; i < n; i += T) gcar[m + i] = g[i];
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 int mb_threads_for(size_t n, size_t m) { return n * m <= 8192 ? 256 : 1024; }

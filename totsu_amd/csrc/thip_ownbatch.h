@@ -4,7 +4,8 @@
 //           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
 //           functions of the iteration that do not touch A (block_sums; thip_step.h: the arithmetic every loop shares).  The two recurrences -- three passes
 //           from LDS, two carried passes from memory -- stay with their families.
-//           The init body takes its b, c and row sums from the slot (init, replace) or from a staging area (set_bc: ObTakeBc);
+//           The init body takes its b, c and row sums from the slot (init, replace; set_a: ObKeepA, which may keep the iterate) or
+//           from a staging area (set_bc: ObTakeBc);
 //           ownbatch_gather_k collects a range's x_x and x_y for one read-out (solutions).
 //   host:   slots, arena, all 64-byte status blocks in one copy, the live list, replace as the init kernel on one slot, and the C
 //           API itself: a family is a table (ObFamily: its words, its shape rule, its thread choice, its LDS map's size, its
@@ -17,6 +18,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <stdio.h>
 #include <string.h>
 #include <vector>
 
@@ -311,6 +313,23 @@ struct ObTakeBc {
     }
 };
 
+// what a set_a kernel is handed beside the family's launch arguments (thip_NAME_set_a).  The dense families' new A is already where
+// the slot's `a` points when the kernel starts (the host copied it there) and s is unused; the sparse families' new values lie in the
+// staging area, workgroup k's at s.stage + s.at[k], and a scatter launch ahead of the kernel has written them into the blob.
+// keep: the iterate stays
+struct ObSetA { ObStart s; int keep; };
+
+// ob_init_body's SRC of a problem whose A has new values (the set_a kernels'): b, c and the row sums are the slot's, whatever it
+// points at now -- caller memory, or the handle's store after a set_bc -- read, never moved; the slot is not rewritten.  keeps: as
+// ObTakeBc's, taken from the call.  Unlike there the pair a streamed family carries depends on what changed: the kernel forms it
+// again behind the body (thip_midstream.h: mb_seta_body)
+struct ObKeepA {
+    int keep;
+    __device__ __forceinline__ SbSlot data(const SbSlot &sl, int, int, int, int, int) const { return sl; }
+    __device__ __forceinline__ bool keeps() const { return keep != 0; }
+    __device__ __forceinline__ void point(const SbSlot *, int, int, int, const SbSlot &) const {}
+};
+
 // x_x and x_y of the problems of a range from the arena into one buffer (thip_NAME_solutions): workgroup k serves problem first + k,
 // whose block begins at arena + at[4 k] and whose n, m are at[4 k + 1], at[4 k + 2]; its x_x then x_y go to out + at[4 k + 3].
 // at == NULL: one shape -- arena + (first + k) * stride, n, m, out + k * (n + m)
@@ -361,7 +380,9 @@ struct ObFamily {
     int (*launch)(const OwnBatch *h, bool run, const ObArgs &a, unsigned count);      // the init kernel or the iteration
     int (*start)(const OwnBatch *h, const ObArgs &a, const ObStart &s, unsigned count);      // the start kernel (NULL: by class)
     int (*setbc)(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count);      // the set_bc kernel (NULL: by class)
-    const void *kernels[5];                 // every kernel that asks for more than 64 KiB of LDS
+    // the set_a kernel (a sparse family: the scatter launch ahead of it; NULL: by class)
+    int (*seta)(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count);
+    const void *kernels[6];                 // every kernel that asks for more than 64 KiB of LDS
     size_t total = 0;                       // device memory held by every handle of the family
     std::once_flag attr_once;
     hipError_t attr_err = hipSuccess;
@@ -391,6 +412,11 @@ struct OwnBatch {
     // the handle's own b / c / rowabs of every problem, allocated by the first set_bc: problem p's 2 m_p + n_p floats at bc_at[p]
     // (bc_at_dev: the same on the device, for a handle of many shapes; NULL: p * (2 m + n))
     float *bc_store = nullptr; long long *bc_at_dev = nullptr;
+    // the host's mirror of every slot's `a` pointer (create, replace): where set_a of a dense family copies a problem's new A
+    // slot_base: the base of the allocation that pointer lies in (0: not asked yet; odd: the runtime does not know it, the slot is
+    // on its own) -- two slots whose A happen to lie one behind the other in DIFFERENT allocations are never served by one copy
+    std::vector<const float *> slot_a;
+    std::vector<uintptr_t> slot_base;
     std::vector<unsigned char> unaligned;   // (a family that streams A) per slot: the problem's A is not 16-byte aligned
     size_t n_unaligned = 0;                 // how many: decides the load path info() reports
 };
@@ -582,6 +608,9 @@ int ob_build(OwnBatch *h, const float *a, const float *b, const float *c, const 
 {
     hipStream_t st = ctx().stream;
     const size_t n_prob = h->n_prob, m = h->m;
+    h->slot_a.assign(n_prob, nullptr);
+    h->slot_base.assign(n_prob, 0);
+    for (size_t p = 0; a && p < n_prob; ++p) h->slot_a[p] = a + p * m * h->n;      // (ownbatch_slots_k's rule)
     THIP_RC(ob_alloc(h, (void **)&h->arena, h->stride * n_prob * sizeof(float)));
     THIP_RC(ob_alloc(h, (void **)&h->dst, n_prob * sizeof(SbStatus)));
     THIP_RC(ob_alloc(h, (void **)&h->slots, n_prob * sizeof(SbSlot)));
@@ -707,6 +736,7 @@ int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, co
     const auto at = std::lower_bound(h->live.begin(), h->live.end(), i);
     if (at == h->live.end() || *at != i) h->live.insert(at, i);
     THIP_RC(ob_status_one(h, i));
+    if (!h->slot_a.empty()) { h->slot_a[(size_t)i] = dev_mat_a; h->slot_base[(size_t)i] = 0; }
     if (f.streams) {
         const unsigned char un = ((uintptr_t)dev_mat_a & 15u) != 0;
         h->n_unaligned += un;
@@ -757,6 +787,22 @@ int ob_stage_reserve(OwnBatch *h, size_t bytes, void **host)
     return 0;
 }
 
+// the host's books behind the kernels that start problems again: the problems first .. first + count - 1 are running, their status
+// blocks fresh (synchronises)
+int ob_restarted(OwnBatch *h, int first, int count)
+{
+    hipStream_t st = ctx().stream;
+    THIP_TRY(hipMemcpyAsync(h->hst + first, h->dst + first, (size_t)count * sizeof(SbStatus), hipMemcpyDeviceToHost, st));
+    THIP_TRY(hipStreamSynchronize(st));
+    std::vector<int> merged;                                     // (the live list is sorted: the range goes in as one run)
+    merged.reserve(h->live.size() + (size_t)count);
+    for (int p : h->live) if (p < first) merged.push_back(p);
+    for (int p = first; p < first + count; ++p) merged.push_back(p);
+    for (int p : h->live) if (p >= first + count) merged.push_back(p);
+    h->live.swap(merged);
+    return 0;
+}
+
 // the `bytes` packed into the handle's pinned buffer up, `launch` (the start kernels on them), and the host's books: the problems
 // first .. first + count - 1 are running again, their status blocks fresh
 template <class LAUNCH>
@@ -767,15 +813,7 @@ int ob_start_staged(OwnBatch *h, int first, int count, size_t bytes, const LAUNC
     THIP_TRY(hipMemcpyAsync(stage, h->stage_host, bytes, hipMemcpyHostToDevice, st));
     const int rc = launch(stage);
     if (rc != 0) { hipStreamSynchronize(st); return rc; }      // (the copy may still be reading the pinned buffer)
-    THIP_TRY(hipMemcpyAsync(h->hst + first, h->dst + first, (size_t)count * sizeof(SbStatus), hipMemcpyDeviceToHost, st));
-    THIP_TRY(hipStreamSynchronize(st));
-    std::vector<int> merged;                                     // (the live list is sorted: the range goes in as one run)
-    merged.reserve(h->live.size() + (size_t)count);
-    for (int p : h->live) if (p < first) merged.push_back(p);
-    for (int p = first; p < first + count; ++p) merged.push_back(p);
-    for (int p : h->live) if (p >= first + count) merged.push_back(p);
-    h->live.swap(merged);
-    return 0;
+    return ob_restarted(h, first, count);
 }
 
 // thip_NAME_set_iterates of a family of one shape: one upload, one launch
@@ -857,6 +895,100 @@ int ob_set_bc(const ObFamily &f, OwnBatch *h, int first, int count, const float 
                          (long long)(2 * m + n), keep != 0 };
         return f.setbc(h, a, s, (unsigned)count);
     });
+}
+
+// every refusal of a set_a, before anything is uploaded or touched: the handle, the range, each problem's count (host_counts, or NULL:
+// the values are need(p) per problem, one after another) and every value finite (spb_validate's rule; an explicit zero is a value).
+// what: the family's words for what a problem's count is.  *total: the floats host_values holds
+constexpr const char *OB_SETA_DENSE = "its m n entries are needed";
+constexpr const char *OB_SETA_SPARSE = "its stored entries are needed (another pattern: _replace)";
+
+template <class NEED>
+int ob_seta_check(const ObFamily &f, const OwnBatch *h, int first, int count, const float *host_values, const int64_t *host_counts,
+                  const NEED &need, const char *what, size_t *total)
+{
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (!h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
+    if (count < 1 || first < 0 || (size_t)first + (size_t)count > h->n_prob)
+        return fail(THIP_E_INVALID, "no such range of problems", __FILE__, __LINE__);
+    char msg[160];
+    size_t sum = 0;
+    for (int k = 0; k < count; ++k) {
+        const size_t want = need(first + k);
+        if (host_counts && (host_counts[k] < 0 || (size_t)host_counts[k] != want)) {
+            snprintf(msg, sizeof(msg), "problem %d: %lld values of A where %zu, %s", first + k, (long long)host_counts[k], want, what);
+            return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+        }
+        sum += want;
+    }
+    if (sum && !host_values) return fail(THIP_E_INVALID, "null values of A", __FILE__, __LINE__);
+    const float *v = host_values;
+    for (int k = 0; k < count; ++k) {
+        const size_t want = need(first + k);
+        for (size_t e = 0; e < want; ++e)
+            if (v[e] - v[e] != 0.0f) {
+                snprintf(msg, sizeof(msg), "problem %d: a value of A is not finite", first + k);
+                return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+            }
+        v += want;
+    }
+    *total = sum;
+    return 0;
+}
+
+// the allocation slot p's A lies in, asked of the runtime once per slot and pointer
+uintptr_t ob_slot_base(OwnBatch *h, size_t p)
+{
+    if (h->slot_base[p] == 0) {
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<float *>(h->slot_a[p])) == hipSuccess && base && !((uintptr_t)base & 1u))
+            h->slot_base[p] = (uintptr_t)base;
+        else {
+            (void)hipGetLastError();
+            h->slot_base[p] = ((uintptr_t)p << 1) | 1u;
+        }
+    }
+    return h->slot_base[p];
+}
+
+// the new A of the problems first .. first + count - 1 of a dense family from the host straight to where their slots' `a` point, one
+// copy per run of slots that lie one behind the other in one allocation (a batch as created is one run).  floats(p): problem p's m n
+template <class FLOATS>
+int ob_seta_copy(OwnBatch *h, int first, int count, const float *host_values, const FLOATS &floats)
+{
+    hipStream_t st = ctx().stream;
+    const float *src = host_values;
+    for (int k = 0; k < count;) {
+        const float *const to = h->slot_a[(size_t)(first + k)];
+        size_t run = floats(first + k);
+        int j = k + 1;
+        while (j < count && h->slot_a[(size_t)(first + j)] == to + run && ob_slot_base(h, (size_t)(first + j)) == ob_slot_base(h, (size_t)(first + k))) {
+            run += floats(first + j);
+            ++j;
+        }
+        THIP_TRY(hipMemcpyAsync(const_cast<float *>(to), src, run * sizeof(float), hipMemcpyHostToDevice, st));
+        src += run;
+        k = j;
+    }
+    return 0;
+}
+
+// thip_NAME_set_a of a dense family of one shape: the copies, one launch
+int ob_set_a(const ObFamily &f, OwnBatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep)
+{
+    THIP_NEED_INIT();
+    const size_t per = h ? h->m * h->n : 0;
+    size_t total = 0;
+    THIP_RC(ob_seta_check(f, h, first, count, host_values, host_counts, [&](int) { return per; }, OB_SETA_DENSE, &total));
+    int rc = ob_seta_copy(h, first, count, host_values, [&](int) { return per; });
+    if (rc == 0) {
+        ObArgs a = ob_args(h);
+        a.first = first;
+        rc = f.seta(h, a, ObSetA{ ObStart{ nullptr, nullptr, 0 }, keep != 0 }, (unsigned)count);
+    }
+    if (rc != 0) { hipStreamSynchronize(ctx().stream); return rc; }      // (a copy may still be reading the caller's values)
+    return ob_restarted(h, first, count);
 }
 
 // thip_NAME_solutions: the gather kernel on the range into the staging buffer (`at`: the table of a handle of many shapes, which goes
@@ -1046,6 +1178,9 @@ int ob_force_threads(const ObFamily &f, OwnBatch *h, int threads)
     { return ob_set_bc(FAM, h, first, count, host_b, host_c, host_b_rowabs, host_has_rowabs, keep_iterate); }                       \
     int thip_##NAME##_solutions(thip_##NAME *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)       \
     { return ob_solutions(FAM, h, first, count, host_x, host_y, host_status); }                                                     \
+    int thip_##NAME##_set_a(thip_##NAME *h, int first, int count, const float *host_values, const int64_t *host_counts,             \
+                            int keep_iterate)                                                                                       \
+    { return ob_set_a(FAM, h, first, count, host_values, host_counts, keep_iterate); }                                              \
     int thip_##NAME##_info(const thip_##NAME *h, thip_##NAME##_info_t *host_info) { return ob_info_out(h, host_info, FILL()); }       \
     int thip_test_##NAME##_force_threads(thip_##NAME *h, int threads) { return ob_force_threads(FAM, h, threads); }                 \
     }

@@ -90,6 +90,16 @@ __global__ __launch_bounds__(1024) void raggedbatch_setbc_k(const RbSetBcArgs a)
     mb_setbc_body(b, a.s, at);
 }
 
+// a problem's A has new values (thip_raggedbatch_set_a): one launch per class, the problems by list
+struct RbSetAArgs { RbArgs rb; int keep; };
+
+__global__ __launch_bounds__(1024) void raggedbatch_seta_k(const RbSetAArgs a)
+{
+    RbAt at;
+    const ObArgs b = rb_problem(a.rb, at);
+    mb_seta_body(b, a.keep, at);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RB_TEXT = { "ragged batch not initialised", "null ragged batch", "a ragged batch holds 1 .. 1048576 problems", nullptr,
@@ -100,9 +110,9 @@ int rb_launch_hook(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
 ObFamily RB_FAMILY = { RB_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, rb_launch_hook, nullptr,
-                       nullptr,
+                       nullptr, nullptr,
                        { (const void *)raggedbatch_k, (const void *)raggedbatch_init_k, (const void *)raggedbatch_start_k,
-                         (const void *)raggedbatch_setbc_k, nullptr } };
+                         (const void *)raggedbatch_setbc_k, (const void *)raggedbatch_seta_k, nullptr } };
 
 struct RbProb { size_t n, m, lds; int layout, cls; };
 
@@ -237,6 +247,16 @@ int rg_setbc(const thip_raggedbatch *h, int c, unsigned count, const int *live, 
     return 0;
 }
 
+// class c's set_a kernel on the `count` problems of the list (their new A lies behind their slots' pointers already)
+int rg_seta(const thip_raggedbatch *h, int c, unsigned count, const int *live, const ObSetA &s)
+{
+    RbSetAArgs a{ rb_args(h), s.keep };
+    a.rb.mb.live = live;
+    hipLaunchKernelGGL(raggedbatch_seta_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
 // (ob_replace's init launch: one slot, by its class)
 int rb_launch_hook(const OwnBatch *ob, bool run, const ObArgs &a, unsigned count)
 {
@@ -309,8 +329,11 @@ int rb_create(size_t n_prob, const size_t *host_n, const size_t *host_m, const f
     h->par = *par;
     std::vector<SbSlot> slots(n_prob);
     h->unaligned.assign(n_prob, 0);
+    h->slot_a.assign(n_prob, nullptr);
+    h->slot_base.assign(n_prob, 0);
     for (size_t p = 0; p < n_prob; ++p) {
         slots[p] = SbSlot{ dev_a + at_a[p], dev_b + at_b[p], dev_c + at_c[p], (dev_r && at_r && at_r[p] >= 0) ? dev_r + at_r[p] : nullptr };
+        h->slot_a[p] = slots[p].a;
         h->unaligned[p] = ((uintptr_t)slots[p].a & 15u) != 0;
         h->n_unaligned += h->unaligned[p];
     }
@@ -405,6 +428,9 @@ int thip_raggedbatch_set_bc(thip_raggedbatch *h, int first, int count, const flo
 
 int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
 { return rg_solutions(RB_FAMILY, h, first, count, host_x, host_y, host_status); }
+
+int thip_raggedbatch_set_a(thip_raggedbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate)
+{ return rg_set_a_dense(RB_FAMILY, h, first, count, host_values, host_counts, keep_iterate); }
 
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info) { return rb_info(h, host_info); }
 int thip_raggedbatch_destroy(thip_raggedbatch *h) { return rb_destroy(h); }

@@ -208,6 +208,85 @@ int rg_set_bc(const ObFamily &f, H *h, int first, int count, const float *host_b
     });
 }
 
+// the classes' members among the problems first .. first + count - 1
+template <class H>
+void rg_members(const H *h, int first, int count, std::vector<int> *members)
+{
+    for (int k = 0; k < count; ++k) members[h->pl.prob[(size_t)(first + k)].cls].push_back(first + k);
+}
+
+// thip_NAME_set_a of a DENSE handle that launches by class: problem p's m_p n_p values go from the host straight behind the slot's
+// pointer (ob_seta_copy), the classes' lists into live_dev as a run's do -- nothing is allocated -- and one launch per class with a
+// member in the range runs rg_seta
+template <class H>
+int rg_set_a_dense(const ObFamily &f, H *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep)
+{
+    THIP_NEED_INIT();
+    auto need = [&](int p) { return h->pl.prob[(size_t)p].m * h->pl.prob[(size_t)p].n; };
+    size_t total = 0;
+    THIP_RC(ob_seta_check(f, h, first, count, host_values, host_counts, need, OB_SETA_DENSE, &total));
+    std::vector<int> members[2], list;                          // (list: read by its copy until ob_restarted synchronises)
+    rg_members(h, first, count, members);
+    for (int c = 0; c < 2; ++c) list.insert(list.end(), members[c].begin(), members[c].end());
+    hipStream_t st = ctx().stream;
+    auto go = [&]() -> int {
+        THIP_RC(ob_seta_copy(h, first, count, host_values, need));
+        THIP_TRY(hipMemcpyAsync(h->live_dev, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (members[c].empty()) continue;
+            THIP_RC(rg_seta(h, c, (unsigned)members[c].size(), h->live_dev + k, ObSetA{ ObStart{ nullptr, nullptr, 0 }, keep != 0 }));
+            k += members[c].size();
+        }
+        return 0;
+    };
+    const int rc = go();
+    if (rc != 0) { hipStreamSynchronize(st); return rc; }
+    return ob_restarted(h, first, count);
+}
+
+// thip_NAME_set_a of a SPARSE handle that launches by class: the values in the CSC order of each slot's present pattern, need(p) of
+// them.  One upload into the staging buffers -- where each workgroup's values lie (in floats from the first), the classes' lists side
+// by side, the values -- and per class with a member in the range rg_seta, which scatters them into the blobs first
+template <class H, class NEED>
+int rg_set_a_sparse(const ObFamily &f, H *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep,
+                    const NEED &need)
+{
+    THIP_NEED_INIT();
+    size_t total = 0;
+    THIP_RC(ob_seta_check(f, h, first, count, host_values, host_counts, need, OB_SETA_SPARSE, &total));
+    const size_t cnt = (size_t)count, head = cnt * sizeof(long long) + ((cnt + 1) & ~(size_t)1) * sizeof(int);
+    std::vector<long long> at_p(cnt);
+    std::vector<int> members[2];
+    rg_members(h, first, count, members);
+    size_t o = 0;
+    for (size_t k = 0; k < cnt; ++k) { at_p[k] = (long long)o; o += need(first + (int)k); }
+    const size_t bytes = head + total * sizeof(float);
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    unsigned char *const host = static_cast<unsigned char *>(pinned);
+    long long *const at = reinterpret_cast<long long *>(host);
+    int *const list = reinterpret_cast<int *>(host + cnt * sizeof(long long));
+    if (total) memcpy(host + head, host_values, total * sizeof(float));
+    {
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c)
+            for (int p : members[c]) { list[k] = p; at[k] = at_p[(size_t)(p - first)]; ++k; }
+    }
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        const unsigned char *const dev = static_cast<const unsigned char *>(stage);
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (members[c].empty()) continue;
+            const ObSetA s{ ObStart{ reinterpret_cast<const float *>(dev + head), reinterpret_cast<const long long *>(dev) + k, 0 },
+                            keep != 0 };
+            THIP_RC(rg_seta(h, c, (unsigned)members[c].size(), reinterpret_cast<const int *>(dev + cnt * sizeof(long long)) + k, s));
+            k += members[c].size();
+        }
+        return 0;
+    });
+}
+
 // thip_NAME_solutions of a handle of many shapes: the gather kernel by a table of the range's blocks, shapes and places
 template <class H>
 int rg_solutions(const ObFamily &f, H *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)

@@ -109,6 +109,27 @@ __global__ __launch_bounds__(1024) void raggedsparse_setbc_k(const RsSetBcArgs a
     mb_setbc_body(b, a.s, at, mat);
 }
 
+// a problem's A has new values in its present pattern (thip_raggedsparse_set_a): per class the scatter into the blobs in memory,
+// a launch of its own (thip_sparsepass.h says why), then init's body on each new blob, resident or streamed as the descriptor says
+struct RsScatterArgs { RsArgs rs; ObStart s; };
+
+__global__ __launch_bounds__(1024) void raggedsparse_scatter_k(const RsScatterArgs a)
+{
+    const int p = ob_problem(a.rs.mb.live, a.rs.mb.first);
+    const RsDesc d = a.rs.desc[p];
+    spb_scatter(const_cast<unsigned *>(reinterpret_cast<const unsigned *>(a.rs.mb.slots[p].a)), d.m, d.n, ob_staged(a.s));
+}
+
+struct RsSetAArgs { RsArgs rs; int keep; };
+
+__global__ __launch_bounds__(1024) void raggedsparse_seta_k(const RsSetAArgs a)
+{
+    RbAt at;
+    SpbA mat;
+    const ObArgs b = rs_problem(a.rs, at, mat);
+    mb_seta_body(b, a.keep, at, mat);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 
 const ObText RS_TEXT = { "ragged sparse batch not initialised", "null ragged sparse batch", "a ragged sparse batch holds 1 .. 1048576 problems",
@@ -120,9 +141,9 @@ int rs_threads_unused(size_t, size_t) { return 1024; }       // (the table's thr
 
 // the shape rule is the SDP batch's (sp_check); the launch hook serves ob_replace: the init kernel on one slot
 ObFamily RS_FAMILY = { RS_TEXT, { 256, 1024, 0 }, false, sp_check, rs_threads_unused, sp_lds_for, mb_stride, rs_launch_hook, nullptr,
-                       nullptr,
+                       nullptr, nullptr,
                        { (const void *)raggedsparse_k, (const void *)raggedsparse_init_k, (const void *)raggedsparse_start_k,
-                         (const void *)raggedsparse_setbc_k, nullptr } };
+                         (const void *)raggedsparse_setbc_k, (const void *)raggedsparse_seta_k, nullptr } };
 
 struct RsProb {
     size_t n, m, cap, nnz;                  // cap: the entries the slot can take; nnz: those it was planned with
@@ -307,6 +328,20 @@ int rg_setbc(const thip_raggedsparse *h, int c, unsigned count, const int *live,
     RsSetBcArgs a{ rs_args(h), s };
     a.rs.mb.live = live;
     hipLaunchKernelGGL(raggedsparse_setbc_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// class c's scatter (no LDS) and then its set_a kernel on the `count` problems of the list, workgroup k's values at s.s.at[k]
+int rg_seta(const thip_raggedsparse *h, int c, unsigned count, const int *live, const ObSetA &s)
+{
+    RsScatterArgs sc{ rs_args(h), s.s };
+    sc.rs.mb.live = live;
+    hipLaunchKernelGGL(raggedsparse_scatter_k, dim3(count), dim3((unsigned)RB_THREADS[c]), 0, ctx().stream, sc);
+    THIP_LAUNCH_CHECK();
+    RsSetAArgs a{ rs_args(h), s.keep };
+    a.rs.mb.live = live;
+    hipLaunchKernelGGL(raggedsparse_seta_k, dim3(count), dim3((unsigned)RB_THREADS[c]), h->pl.lds[c], ctx().stream, a);
     THIP_LAUNCH_CHECK();
     return 0;
 }
@@ -539,6 +574,12 @@ int thip_raggedsparse_set_bc(thip_raggedsparse *h, int first, int count, const f
 int thip_raggedsparse_solutions(thip_raggedsparse *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)
 { return rg_solutions(RS_FAMILY, h, first, count, host_x, host_y, host_status); }
 
+int thip_raggedsparse_set_a(thip_raggedsparse *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate)
+{
+    return rg_set_a_sparse(RS_FAMILY, h, first, count, host_values, host_counts, keep_iterate,
+                           [&](int p) { return h->pl.prob[(size_t)p].nnz; });
+}
+
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info) { return rs_info(h, host_info); }
 int thip_raggedsparse_destroy(thip_raggedsparse *h) { return rs_destroy(h); }
 
@@ -556,6 +597,20 @@ int thip_test_raggedsparse_force_resident(thip_raggedsparse *h, int resident)
     if (h->inited) return fail(THIP_E_INVALID, "thip_test_raggedsparse_force_resident comes before thip_raggedsparse_init", __FILE__, __LINE__);
     h->force_resident = resident;
     rs_classes(h->pl, h->forced, resident);
+    return 0;
+}
+
+int thip_test_raggedsparse_blob(thip_raggedsparse *h, int i, uint32_t *host_words, size_t cap_words, size_t *host_used_words)
+{
+    THIP_NEED_INIT();
+    if (!h || !host_used_words) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    if (i < 0 || (size_t)i >= h->n_prob) return fail(THIP_E_INVALID, "no such problem", __FILE__, __LINE__);
+    const size_t used = h->slot_used[(size_t)i];
+    *host_used_words = used;
+    if (!host_words) return 0;
+    if (cap_words < used) return fail(THIP_E_INVALID, "the blob holds more words than were offered", __FILE__, __LINE__);
+    THIP_TRY(hipStreamSynchronize(ctx().stream));
+    THIP_TRY(hipMemcpy(host_words, h->blobs + h->pl.desc[(size_t)i].blob_at, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -49,6 +49,11 @@ struct SpSetBcArgs { ObArgs mb; ObSetBc s; };
 
 __global__ __launch_bounds__(1024) void sdpbatch_setbc_k(const SpSetBcArgs a) { mb_setbc_body(a.mb, a.s); }
 
+// a problem's A has new values (thip_sdpbatch_set_a): no cone is projected, the launch keeps the family's LDS size
+struct SpSetAArgs { ObArgs mb; int keep; };
+
+__global__ __launch_bounds__(1024) void sdpbatch_seta_k(const SpSetAArgs a) { mb_seta_body(a.mb, a.keep); }
+
 // thip_test_sdpbatch_project: the projection alone, one workgroup per packed matrix.  LDS: [shd 64][operands]
 __global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, float *rx)
 {
@@ -74,10 +79,16 @@ int sp_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned coun
     return ob_launch(h, sdpbatch_setbc_k, SpSetBcArgs{ a, s }, count);
 }
 
-// (the fifth entry of the table's kernels is this family's: the projection probe asks for the large LDS too)
+int sp_seta(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count)
+{
+    return ob_launch(h, sdpbatch_seta_k, SpSetAArgs{ a, s.keep }, count);
+}
+
+// (the sixth entry of the table's kernels is this family's: the projection probe asks for the large LDS too)
 ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch, sp_start, sp_setbc,
+                       sp_seta,
                        { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k,
-                         (const void *)sdpbatch_start_k, (const void *)sdpbatch_setbc_k } };
+                         (const void *)sdpbatch_start_k, (const void *)sdpbatch_setbc_k, (const void *)sdpbatch_seta_k } };
 
 // thip_midbatch_info_t's fields, and the PSD cones'
 struct SpInfo {

@@ -274,6 +274,22 @@ __global__ __launch_bounds__(1024) void smallbatch_setbc_k(const SbSetBcArgs a)
     }, ObUniform(), ObTakeBc{ a.s });
 }
 
+// a problem's A has new values (thip_smallbatch_set_a): ob_init_body on the slot's own b, c and row sums, the |A| sums from LDS, the
+// ending taken from the call.  The three-pass recurrence carries no pair
+struct SbSetAArgs { SbArgs sb; int keep; };
+
+__global__ __launch_bounds__(1024) void smallbatch_seta_k(const SbSetAArgs a)
+{
+    const int n = a.sb.n, m = a.sb.m, lda = a.sb.lda;
+    const SbMap L(n, m, lda, (int)blockDim.x);
+    float *S = sb_lds;
+    ob_init_body(a.sb, ob_problem(a.sb.live, a.sb.first), L, S, [&](const float *src) {
+        load_a(src, S + L.A, m, n, lda);
+        __syncthreads();
+        products<true>(S + L.A, lda, m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.red);
+    }, ObUniform(), ObKeepA{ a.keep });
+}
+
 const ObText SB_TEXT = { "small batch not initialised", "null small batch", "a small batch holds 1 .. 1048576 problems",
                          "a small batch takes no PSD segment", "the workgroup size is 64, 256 or 1024 (0: by shape)",
                          "thip_test_smallbatch_force_threads comes before thip_smallbatch_init" };
@@ -323,9 +339,15 @@ int sb_setbc(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned coun
     return ob_launch(h, smallbatch_setbc_k, SbSetBcArgs{ sb_args(a), s }, count);
 }
 
+int sb_seta(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count)
+{
+    return ob_launch(h, smallbatch_seta_k, SbSetAArgs{ sb_args(a), s.keep }, count);
+}
+
 ObFamily SB_FAMILY = { SB_TEXT, { 64, 256, 1024 }, false, sb_check, sb_threads_for, sb_lds_for, sb_stride, sb_launch, sb_start, sb_setbc,
+                       sb_seta,
                        { (const void *)smallbatch_k, (const void *)smallbatch_init_k, (const void *)smallbatch_start_k,
-                         (const void *)smallbatch_setbc_k, nullptr } };
+                         (const void *)smallbatch_setbc_k, (const void *)smallbatch_seta_k, nullptr } };
 
 }  // namespace
 

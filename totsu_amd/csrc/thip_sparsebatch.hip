@@ -44,6 +44,23 @@ __global__ __launch_bounds__(1024) void sparsebatch_setbc_k(const SpbSetBcArgs a
     mb_setbc_body(a.mb, a.s, ObUniform(), SpbA{ a.at, a.resident });
 }
 
+// a problem's A has new values in its present pattern (thip_sparsebatch_set_a): the scatter into the blob in memory, a launch of its
+// own (thip_sparsepass.h says why), then init's body on the new blob, resident or streamed, and under keep the pair again
+struct SpbScatterArgs { ObArgs mb; ObStart s; };
+
+__global__ __launch_bounds__(1024) void sparsebatch_scatter_k(const SpbScatterArgs a)
+{
+    const int p = ob_problem(a.mb.live, a.mb.first);
+    spb_scatter(const_cast<unsigned *>(reinterpret_cast<const unsigned *>(a.mb.slots[p].a)), a.mb.m, a.mb.n, ob_staged(a.s));
+}
+
+struct SpbSetAArgs { ObArgs mb; int at, resident, keep; };
+
+__global__ __launch_bounds__(1024) void sparsebatch_seta_k(const SpbSetAArgs a)
+{
+    mb_seta_body(a.mb, a.keep, ObUniform(), SpbA{ a.at, a.resident });
+}
+
 __global__ void sparsebatch_slots_k(SbSlot *slots, int n_prob, const unsigned *blobs, size_t cap_words)
 {
     for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < (size_t)n_prob; p += (size_t)gridDim.x * blockDim.x)
@@ -104,10 +121,20 @@ int spb_setbc(const OwnBatch *ob, const ObArgs &a, const ObSetBc &s, unsigned co
     return ob_launch(ob, sparsebatch_setbc_k, SpbSetBcArgs{ a, tail + (int)(h->psd.tail_bytes / sizeof(float)), h->resident, s }, count);
 }
 
+// the scatter (no LDS) and then the set_a kernel
+int spb_seta(const OwnBatch *ob, const ObArgs &a, const ObSetA &s, unsigned count)
+{
+    const thip_sparsebatch *h = static_cast<const thip_sparsebatch *>(ob);
+    const int tail = (int)(MbMap((int)h->n, (int)h->m).bytes((int)h->m) / sizeof(float));
+    hipLaunchKernelGGL(sparsebatch_scatter_k, dim3(count), dim3((unsigned)h->threads), 0, ctx().stream, SpbScatterArgs{ a, s.s });
+    THIP_LAUNCH_CHECK();
+    return ob_launch(ob, sparsebatch_seta_k, SpbSetAArgs{ a, tail + (int)(h->psd.tail_bytes / sizeof(float)), h->resident, s.keep }, count);
+}
+
 ObFamily SPB_FAMILY = { SPB_TEXT, { 256, 1024, 0 }, false, sp_check, spb_threads_unused, sp_lds_for, mb_stride, spb_launch, spb_start,
-                        spb_setbc,
+                        spb_setbc, spb_seta,
                         { (const void *)sparsebatch_k, (const void *)sparsebatch_init_k, (const void *)sparsebatch_start_k,
-                          (const void *)sparsebatch_setbc_k, nullptr } };
+                          (const void *)sparsebatch_setbc_k, (const void *)sparsebatch_seta_k, nullptr } };
 
 // the rule (no device needed): sp_check's on (n, m, layout); the blob is resident when it fits behind the vectors and the PSD tail
 int spb_fits(size_t n, size_t m, size_t nnz_cap, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -252,6 +279,29 @@ int thip_sparsebatch_solutions(thip_sparsebatch *h, int first, int count, float 
 { return ob_solutions(SPB_FAMILY, h, first, count, host_x, host_y, host_status); }
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info) { return ob_info_out(h, host_info, SpbInfo()); }
 
+// one upload -- where each workgroup's values begin (the counts differ), then the values, 4 bytes per entry -- and two launches
+int thip_sparsebatch_set_a(thip_sparsebatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate)
+{
+    THIP_NEED_INIT();
+    size_t total = 0;
+    THIP_RC(ob_seta_check(SPB_FAMILY, h, first, count, host_values, host_counts, [&](int p) { return (size_t)h->slot_nnz[(size_t)p]; },
+                          OB_SETA_SPARSE, &total));
+    const size_t cnt = (size_t)count, head = cnt * sizeof(long long), bytes = head + total * sizeof(float);
+    void *pinned = nullptr;
+    THIP_RC(ob_stage_reserve(h, bytes, &pinned));
+    long long *const at = static_cast<long long *>(pinned);
+    size_t o = 0;
+    for (size_t k = 0; k < cnt; ++k) { at[k] = (long long)o; o += h->slot_nnz[(size_t)first + k]; }
+    if (total) memcpy(static_cast<unsigned char *>(pinned) + head, host_values, total * sizeof(float));
+    return ob_start_staged(h, first, count, bytes, [&](const void *stage) {
+        const unsigned char *const dev = static_cast<const unsigned char *>(stage);
+        ObArgs a = ob_args(h);
+        a.first = first;
+        const ObSetA s{ ObStart{ reinterpret_cast<const float *>(dev + head), reinterpret_cast<const long long *>(dev), 0 }, keep_iterate != 0 };
+        return SPB_FAMILY.seta(h, a, s, (unsigned)count);
+    });
+}
+
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,
                              const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
 {
@@ -285,6 +335,20 @@ int thip_test_sparsebatch_force_resident(thip_sparsebatch *h, int resident)
         return fail(THIP_E_INVALID, "the blob does not fit the LDS left beside the vectors: it cannot be resident", __FILE__, __LINE__);
     h->force_resident = resident;
     spb_plan(h);
+    return 0;
+}
+
+int thip_test_sparsebatch_blob(thip_sparsebatch *h, int i, uint32_t *host_words, size_t cap_words, size_t *host_used_words)
+{
+    THIP_NEED_INIT();
+    if (!h || !host_used_words) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    if (i < 0 || (size_t)i >= h->n_prob) return fail(THIP_E_INVALID, "no such problem", __FILE__, __LINE__);
+    const size_t used = h->slot_used[(size_t)i];
+    *host_used_words = used;
+    if (!host_words) return 0;
+    if (cap_words < used) return fail(THIP_E_INVALID, "the blob holds more words than were offered", __FILE__, __LINE__);
+    THIP_TRY(hipStreamSynchronize(ctx().stream));
+    THIP_TRY(hipMemcpy(host_words, h->blobs + (size_t)i * h->cap_words, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

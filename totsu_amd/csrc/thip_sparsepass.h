@@ -1,7 +1,8 @@
 // thip_sparsepass.h -- what the batches that hold each problem's own SPARSE A as packed entries share (thip_sparsebatch.hip: one
 // shape and one cone layout per batch; thip_raggedsparse.hip: every problem its own shape, layout and pattern): the blob's pass
 // (spb_half, spb_pass), the matrix policy of the shared bodies (SpbA; thip_midstream.h), and the host side of the stored form -- the
-// capacity of a slot, the thread rule, every refusal of a problem's CSC arrays (spb_validate) and the packing (spb_pack).  One text:
+// capacity of a slot, the thread rule, every refusal of a problem's CSC arrays (spb_validate) and the packing (spb_pack) -- and
+// spb_scatter, which gives a blob new values on the device where the pattern stays.  One text:
 // a problem's products are the same bits in either family.
 // Included once by each of the two translation units (on top of thip_sdpcones.h): everything here is internal to the one that
 // includes it.
@@ -110,6 +111,49 @@ struct SpbA {
         else spb_pass<ABS, false>(M.w, m, n, xn, xt, h, g);
     }
 };
+
+// new values into a blob whose pattern stays (thip_NAME_set_a), by one workgroup: w is the blob IN MEMORY, val the nnz new values in
+// the column order of its pattern.  The column order takes them as they come, ce[2 e] = val[e].  A row-order entry r of row i holds
+// the value of the entry (i, j = re[2 r + 1]), whose place in the column order is found by a binary search for i among the strictly
+// ascending rows of column j, ce[2 cptr[j] + 1 ..] -- re[2 r] = val[that place].  The rows are dealt as spb_half deals them: a row
+// of <= SPB_LONG entries to one lane, a row on the long list to one wave, lanes striding its entries.  Pointers, index words and the
+// long lists are read, never written; every value comes from val, none from the blob, so the two orders are written in any order and
+// no word written here is read here.  The result is, word for word, what spb_pack makes of the pattern with the new values.
+// The launch is its own, ahead of the kernel that reads the blob (the |A| pass of init, the copy into LDS): values stored by vector
+// stores here must not meet a scalar load of the same words that the compiler chose in the same kernel, and a kernel boundary makes
+// them visible to every later load of any kind -- one launch per call is the price
+__device__ __forceinline__ void spb_scatter(unsigned *w, int m, int n, const float *val)
+{
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = T >> 6;
+    const unsigned nnz = w[n];
+    const unsigned *const cptr = w;
+    unsigned *const ce = w + n + 1;
+    const unsigned *const rptr = ce + 2 * (size_t)nnz;
+    unsigned *const re = w + n + 1 + 2 * (size_t)nnz + m + 1;
+    const unsigned *const lists = re + 2 * (size_t)nnz;
+    const int nlr = (int)lists[0];
+    auto place = [&](unsigned r, unsigned i) {
+        const unsigned j = re[2 * r + 1];
+        const unsigned end = cptr[j + 1];
+        unsigned lo = cptr[j], hi = end;
+        while (lo < hi) {
+            const unsigned mid = lo + (hi - lo) / 2;
+            if (ce[2 * mid + 1] < i) lo = mid + 1; else hi = mid;
+        }
+        if (lo < end && ce[2 * lo + 1] == i) re[2 * r] = __float_as_uint(val[lo]);      // (always, in a blob spb_pack made)
+    };
+    for (int i = tid; i < m; i += T) {
+        const unsigned beg = rptr[i], end = rptr[i + 1];
+        if (end - beg > (unsigned)SPB_LONG) continue;
+        for (unsigned r = beg; r < end; ++r) place(r, (unsigned)i);
+    }
+    for (int k = wv; k < nlr; k += nw) {                          // (uniform per wave)
+        const unsigned i = lists[2 + k];
+        const unsigned beg = rptr[i], end = rptr[i + 1];
+        for (unsigned r = beg + (unsigned)lane; r < end; r += 64u) place(r, i);
+    }
+    for (unsigned e = (unsigned)tid; e < nnz; e += (unsigned)T) ce[2 * e] = __float_as_uint(val[e]);
+}
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------
 

@@ -83,6 +83,44 @@ def pack_bc(n_prob, shape_of, vecs_b, vecs_c, vecs_b_rowabs=None, first=0):
     return count, b, c, np.concatenate(rs), None if has.all() else has
 
 
+def pack_a(n_prob, size_of, mats_a, first=0, values_of=None):
+    """the arrays thip_NAME_set_a takes (needs no handle and no GPU): (count, values, counts) for the problems first, first + 1, ..
+    of a batch of n_prob whose problem i takes size_of(i) values -- m_i n_i of a dense A (column-major), the entries of a sparse
+    problem's present pattern (CSC order).  mats_a: one host array per problem, or a 2-D array of one row per problem.  values:
+    every problem's values one after another as float32; counts: how many each brings, int64.  values_of(i, item): what a family
+    makes of an item that is no plain array (a sparse family's triple or scipy matrix, whose pattern it compares).  ValueError,
+    all before anything is uploaded: no problem, a range outside the batch, a wrong length (the message names the problem), a
+    value that is not finite"""
+    first = int(first)
+    whole = mats_a if isinstance(mats_a, np.ndarray) and mats_a.ndim == 2 and mats_a.dtype != object else None
+    mats_a = list(mats_a)
+    count = len(mats_a)
+    if count < 1:
+        raise ValueError("set_a: no problem (one array of values per problem, at least one)")
+    if not 0 <= first <= first + count <= int(n_prob):
+        raise ValueError("set_a: no problems %r .. %r in a batch of %d" % (first, first + count - 1, n_prob))
+    if whole is not None and all(int(size_of(first + k)) == whole.shape[1] for k in range(count)):
+        with np.errstate(over="ignore"):    # one row per problem, every length right: one conversion and one check for all
+            v = np.ascontiguousarray(whole, dtype=np.float32)
+        if np.isfinite(v).all():
+            return count, v.ravel(), np.full(count, whole.shape[1], dtype=np.int64)
+    out = []
+    for k, a in enumerate(mats_a):
+        if values_of is not None:
+            a = values_of(first + k, a)
+        with np.errstate(over="ignore"):        # (a value too large for float32 becomes inf and is refused below)
+            a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+        want = int(size_of(first + k))
+        if a.size != want:
+            raise ValueError("problem %d: %d values of A where %d are needed%s"
+                             % (first + k, a.size, want, "" if values_of is None else " (the slot's entry count; another pattern is replace's)"))
+        if not np.isfinite(a).all():
+            raise ValueError("problem %d: a value of A is not finite" % (first + k))
+        out.append(a)
+    counts = np.array([a.size for a in out], dtype=np.int64)
+    return count, np.ascontiguousarray(np.concatenate(out), dtype=np.float32), counts
+
+
 class OwnBatchSolver:
     # what a family of own-A batches differs in (the subclasses set these)
     _prefix = _force_hook = _what = _Info = None
@@ -279,6 +317,30 @@ class OwnBatchSolver:
         count, b, c, r, has = pack_bc(self.n_prob, self._nm, vecs_b, vecs_c, vecs_b_rowabs, first)
         _checked(self._c("set_bc"), self.h, int(first), count, b.ctypes.data, c.ctypes.data, None if r is None else r.ctypes.data,
                  None if has is None else has.ctypes.data, 1 if keep_iterate else 0)
+
+    def _a_size(self, i):
+        """how many values problem i's A holds: m n here, the present pattern's entries in a sparse family"""
+        n, m = self._nm(i)
+        return n * m
+
+    _a_values = None        # (a sparse family: what it makes of a triple or a scipy matrix)
+
+    def set_a(self, mats_a, first=0, keep_iterate=False):
+        """problems first, first + 1, .. take NEW VALUES of A and keep their shape, cone layout, b, c and row sums: one call, one
+        launch (one per workgroup-size class in a ragged batch) and one read of the status blocks for all of them.  mats_a: one
+        host array per problem -- the problem's own m n floats, column-major, as replace takes them (a 2-D array of one row per
+        problem where the shapes are uniform); in a sparse family the values in the CSC order of the slot's present pattern, or a
+        (colptr, rowidx, values) triple or scipy.sparse matrix of exactly that pattern.  A dense A is OVERWRITTEN IN PLACE on the
+        device, in the memory the slot reads it from (the batch's own upload, or the DeviceBuffer the caller handed in); nothing
+        is allocated.  keep_iterate=False: each problem ends exactly as replace(i, new A, its present b, c, rowabs) leaves it.
+        keep_iterate=True: the preconditioner and norms of the new data and the iterate as it lies on the device kept (the
+        compensation terms zero; what a streamed family carries formed again): iteration 0 and running again, whether the problem
+        was running or had stopped; followed by set_bc(.., keep_iterate=True) it is a round that moves A, b and c.  b, c and the
+        row sums are the slot's present ones (after a set_bc: those).  ValueError, before anything is uploaded or touched: a wrong
+        length (the message names the problem), a value that is not finite, a range outside the batch, another pattern (that is
+        replace's)."""
+        count, v, counts = pack_a(self.n_prob, self._a_size, mats_a, first, self._a_values)
+        _checked(self._c("set_a"), self.h, int(first), count, v.ctypes.data, counts.ctypes.data, 1 if keep_iterate else 0)
 
     def _range(self, first, count):
         first = int(first)

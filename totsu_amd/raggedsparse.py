@@ -26,7 +26,7 @@ from ._lib import lib
 from .fused import DeviceBuffer, _c_param
 from .raggedbatch import RaggedBatchSolver, _info_dict, _ptrs, _shape_arrays
 from .solver import SolverParam
-from .sparsebatch import _P32, _P64, _PF, _value_errors, csc_of, csc_of_dense
+from .sparsebatch import _P32, _P64, _PF, SparseSetA, _pattern_of, _value_errors, csc_of, csc_of_dense
 
 _KINDS = ("vec_b", "vec_c", "vec_b_rowabs")
 _PSZ, _PI = C.POINTER(C.c_size_t), C.POINTER(C.c_int)
@@ -134,9 +134,9 @@ def plan(problems, nnz_caps=None, force_threads=None, force_resident=None):
     return _plan(problems, _nnz_of(problems), nnz_caps, force_threads, force_resident)
 
 
-class RaggedSparseBatchSolver(RaggedBatchSolver):
-    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / precond / replace / reinit / set_param / info /
-    solve / destroy of OwnBatchSolver, on thip_raggedsparse_*, with every length the problem's own.  `shapes`: [(n_p, m_p)]; `nnz_caps`: the entries
+class RaggedSparseBatchSolver(SparseSetA, RaggedBatchSolver):
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / set_a / solutions / precond / replace /
+    reinit / set_param / info / solve / destroy of OwnBatchSolver, on thip_raggedsparse_*, with every length the problem's own.  `shapes`: [(n_p, m_p)]; `nnz_caps`: the entries
     each slot can take.  force_threads (256, 1024: every problem in that one class) and force_resident (0: nobody resident, 1:
     everybody who fits) are test hooks.
 
@@ -167,6 +167,7 @@ class RaggedSparseBatchSolver(RaggedBatchSolver):
         for k, d in enumerate(problems):
             self._check_vectors("problem %d: " % k, d.n, d.m, d.vec_b, d.vec_c, getattr(d, "vec_b_rowabs", None))
         triples = _triples(problems)
+        self._patterns = [_pattern_of(t) for t in triples]
         counts = [int(t[0][-1]) for t in triples]
         _plan(problems, counts, caps, force_threads, force_resident)       # every refusal of the rule, before anything is uploaded
         self.shapes = [(int(d.n), int(d.m)) for d in problems]
@@ -243,6 +244,7 @@ class RaggedSparseBatchSolver(RaggedBatchSolver):
             for d in own:
                 d.free()
             raise
+        self._patterns[i] = _pattern_of((cp, ri, va))
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()

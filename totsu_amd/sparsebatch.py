@@ -108,9 +108,50 @@ def pack(n, m, mat, nnz_cap=0):
     return out, long_len.value
 
 
-class SparseBatchSolver(OwnBatchSolver):
-    """run / run_until_any / status / solution / iterate / precond / reinit / set_param / info / solve / destroy of OwnBatchSolver,
-    on thip_sparsebatch_*.  force_threads (256, 1024) and force_resident (0: read the entries from memory, 1: from LDS) are test
+def pattern_values(pattern, item, n, m, i):
+    """what set_a of a sparse family makes of one problem's item (needs no handle): a plain array of values is returned as it is;
+    a (colptr, rowidx, values) triple or a scipy.sparse matrix must have exactly `pattern` = (colptr, rowidx), slot i's present
+    one, and gives its values.  ValueError otherwise: another pattern is replace's"""
+    triple = isinstance(item, (tuple, list)) and len(item) == 3 and np.ndim(item[0]) == 1
+    if not triple and (isinstance(item, (tuple, list, np.ndarray)) or np.isscalar(item)):
+        return item
+    cp, ri, va = csc_of(item, n, m)
+    nnz = int(cp[-1])
+    if not (np.array_equal(cp, pattern[0]) and np.array_equal(ri[:nnz], pattern[1])):
+        raise ValueError("problem %d: the matrix has another pattern than the slot holds (%d entries against %d); set_a keeps the "
+                         "pattern -- use replace for another one" % (i, nnz, int(pattern[0][-1])))
+    return va[:nnz]
+
+
+def _pattern_of(triple):
+    cp, ri, _ = triple
+    return cp.copy(), ri[:int(cp[-1])].copy()
+
+
+class SparseSetA:
+    """set_a's sparse side, shared by SparseBatchSolver and RaggedSparseBatchSolver: `_patterns[i]`, slot i's (colptr, rowidx) as
+    of construction or its last replace, kept on the host for the comparison"""
+
+    def _a_size(self, i):
+        return int(self._patterns[int(i)][0][-1])
+
+    def _a_values(self, i, item):
+        n, m = self._nm(i)
+        return pattern_values(self._patterns[int(i)], item, n, m, int(i))
+
+    def blob(self, i):
+        """TEST HOOK: slot i's blob as it lies on the device, a uint32 array of the words it uses"""
+        fn = getattr(lib, "thip_test_%s_blob" % self._prefix[len("thip_"):-1])
+        used = C.c_size_t()
+        _value_errors(fn, self.h, int(i), None, 0, C.byref(used))
+        out = np.zeros(used.value, dtype=np.uint32)
+        _value_errors(fn, self.h, int(i), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(used))
+        return out
+
+
+class SparseBatchSolver(SparseSetA, OwnBatchSolver):
+    """run / run_until_any / status / solution / iterate / precond / set_iterate(s) / set_bc / set_a / solutions / reinit / set_param /
+    info / solve / destroy of OwnBatchSolver, on thip_sparsebatch_*.  force_threads (256, 1024) and force_resident (0: read the entries from memory, 1: from LDS) are test
     hooks.  info() adds nnz_cap, nnz_total, blob_bytes, resident and the PSD fields of the SDP batch; a_bytes_per_iter is 0 when
     resident."""
     _prefix, _force_hook, _what, _Info = "thip_sparsebatch_", "thip_test_sparsebatch_force_threads", "sparse", _lib.SparseBatchInfo
@@ -137,6 +178,7 @@ class SparseBatchSolver(OwnBatchSolver):
             if (got < want) if isinstance(arr, DeviceBuffer) else (got != want):
                 raise ValueError("%s: %d entries where %d problems x %d = %d are needed" % (name, got, self.n_prob, per, want))
         triples = [csc_of(mt, self.n, self.m) for mt in mats]
+        self._patterns = [_pattern_of(t) for t in triples]
         counts = [int(t[0][-1]) for t in triples]
         cap = 0 if nnz_cap is None else int(nnz_cap)
         if nnz_cap is not None:
@@ -214,6 +256,7 @@ class SparseBatchSolver(OwnBatchSolver):
             for d in own:
                 d.free()
             raise
+        self._patterns[i] = _pattern_of((cp, ri, va))
         old, self._slot_owned[i] = self._slot_owned.get(i, []), own
         for d in old:
             d.free()
