@@ -48,6 +48,9 @@ int  thip_init(int device);                        /* cuda_mgr.rs:30-60 */
 int  thip_shutdown(void);
 int  thip_device_count(int *host_count);
 int  thip_set_stream(void *hip_stream);            /* NULL = the context's own stream */
+/* (device memory handed to a call -- the dev_* arrays of create, replace and the thip_*batch _dev calls -- is read and written on
+ * this stream: a caller that produces it on another stream orders that work first, and reads what _solutions_dev wrote only after
+ * this stream reached the launch) */
 void *thip_get_stream(void);                       /* runs what is deferred first; NULL = that failed (thip_last_error) */
 int  thip_sync(void);                              /* SYNC */
 const char *thip_last_error(void);
@@ -669,6 +672,45 @@ int thip_smallbatch_solutions(thip_smallbatch *h, int first, int count, float *h
  * prefix and thip_raggedsparse */
 int thip_smallbatch_set_a(thip_smallbatch *h, int first, int count, const float *host_values, const int64_t *host_counts,
                           int keep_iterate);
+/* THE ROUND CALLS ON DEVICE MEMORY: _set_bc, _set_a, _set_iterates and _solutions for a caller whose round is produced, and whose
+ * answers are used, on the GPU.  Every dev_* argument is float32 device memory, packed problem after problem for the range first ..
+ * first + count - 1, each problem in its own lengths: the layouts the host calls take.  Each call is DEFINED by the host call it
+ * mirrors: handed the same floats, _set_bc_dev, _set_a_dev and _set_iterates_dev leave the range -- arena, preconditioner, carried
+ * pair, status blocks, slots, the handle's b / c store, the live list -- as the host call leaves it, bit for bit, for both values of
+ * keep_iterate, for running and stopped problems; _solutions_dev writes what _solutions returns, bit for bit.
+ * _set_bc_dev: dev_b_rowabs may be NULL; host_has_rowabs (HOST memory, one byte per problem) may be NULL; b and c are not examined.
+ * A kernel builds the staged form of the host call in the handle's staging buffer and the set_bc kernels run on it unchanged.
+ * _set_a_dev, a dense family: dev_values != NULL: the values are copied device to device, by one kernel launch for the whole range
+ * whatever allocations the slots lie in, into the memory each slot's A pointer points at (in place, nothing is allocated).
+ * dev_values == NULL: the caller has ALREADY rewritten A where the slots read it (the buffer handed to _create or _replace): nothing
+ * is copied, the handle only initialises again from what lies there -- the zero-copy form.  A dev_values that overlaps the A of a
+ * slot of the range is THIP_E_INVALID: the exact in-place form is written with NULL.  A sparse family: dev_values holds 4 bytes per
+ * stored entry in the CSC order of each slot's present pattern; the scatter kernel reads them where they lie, by a table of the
+ * host's record of the slots' counts, which is all that goes up; NULL is refused.  The tables of every call (a few dozen bytes per
+ * problem) and the verdict words lie in pinned host memory mapped for the device, so a dense _set_a_dev allocates no device memory.
+ * _set_iterates_dev: dev_x, dev_y as _set_iterates' host_x, host_y; a kernel copies them into the staged layout and the start
+ * kernels run on it unchanged.
+ * _solutions_dev: dev_x (n floats per problem), dev_y (m each), dev_state (one int32 per problem: its THIP_ST_* state); each may
+ * be NULL.  The final scaling is applied on the device -- rt = 1 / tau correctly rounded, then rt * v, when kind == 0 and the state
+ * is OK or ExcessIter, else the floats as they lie.  It DOES NOT SYNCHRONISE: it returns after the launch on the library's stream
+ * and copies nothing to the host (a batch of many shapes uploads one table with its first call, counted in device_bytes).
+ * REFUSALS, all THIP_E_INVALID with the batch bit-identical to the one before the call: a null handle, a handle not initialised,
+ * a range outside the batch, count < 1, a null array where one is needed, an array that is not 4-byte aligned; any input or output
+ * range that overlaps memory the handle owns (its arena, its staging buffers, its b / c store, a sparse family's blobs); and what
+ * the host calls find by scanning: a check kernel -- one launch, one verdict word per problem, written into pinned host memory and
+ * read by the host behind a synchronisation BEFORE any copy, scatter or set kernel is launched -- looks for a value of A that is not finite (the in-place form: in the slots'
+ * own A) and for a start's tau that is negative or not finite or kappa that is positive or not finite; the message names the first
+ * problem at fault.
+ * STREAM: everything is enqueued on the library's stream (thip_get_stream / thip_set_stream).  A caller that produces the data on
+ * another stream orders that work before the call (an event the library's stream waits for, or a synchronisation); the three
+ * _set_*_dev calls end with the read of the range's status blocks and so synchronise, as their host twins do.
+ * Not done: pinned-host inputs, asynchronous _set_* calls, BatchSolver (shared A).  The same under every thip_*batch prefix and
+ * thip_raggedsparse */
+int thip_smallbatch_set_bc_dev(thip_smallbatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_smallbatch_set_a_dev(thip_smallbatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_smallbatch_set_iterates_dev(thip_smallbatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_smallbatch_solutions_dev(thip_smallbatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_smallbatch_info(const thip_smallbatch *h, thip_smallbatch_info_t *host_info);
 int thip_smallbatch_destroy(thip_smallbatch *h);
 
@@ -715,6 +757,11 @@ int thip_midbatch_set_bc(thip_midbatch *h, int first, int count, const float *ho
                          const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_midbatch_solutions(thip_midbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_midbatch_set_a(thip_midbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_midbatch_set_bc_dev(thip_midbatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_midbatch_set_a_dev(thip_midbatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_midbatch_set_iterates_dev(thip_midbatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_midbatch_solutions_dev(thip_midbatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
@@ -761,6 +808,11 @@ int thip_sdpbatch_set_bc(thip_sdpbatch *h, int first, int count, const float *ho
                          const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_sdpbatch_solutions(thip_sdpbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_sdpbatch_set_a(thip_sdpbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_sdpbatch_set_bc_dev(thip_sdpbatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_sdpbatch_set_a_dev(thip_sdpbatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_sdpbatch_set_iterates_dev(thip_sdpbatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_sdpbatch_solutions_dev(thip_sdpbatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
@@ -824,6 +876,11 @@ int thip_raggedbatch_set_bc(thip_raggedbatch *h, int first, int count, const flo
                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_raggedbatch_set_a(thip_raggedbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_raggedbatch_set_bc_dev(thip_raggedbatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_raggedbatch_set_a_dev(thip_raggedbatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_raggedbatch_set_iterates_dev(thip_raggedbatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_raggedbatch_solutions_dev(thip_raggedbatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info);
 int thip_raggedbatch_destroy(thip_raggedbatch *h);
 
@@ -886,6 +943,11 @@ int thip_sparsebatch_set_bc(thip_sparsebatch *h, int first, int count, const flo
                             const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_sparsebatch_solutions(thip_sparsebatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_sparsebatch_set_a(thip_sparsebatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_sparsebatch_set_bc_dev(thip_sparsebatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_sparsebatch_set_a_dev(thip_sparsebatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_sparsebatch_set_iterates_dev(thip_sparsebatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_sparsebatch_solutions_dev(thip_sparsebatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_sparsebatch_info(const thip_sparsebatch *h, thip_sparsebatch_info_t *host_info);
 int thip_sparsebatch_destroy(thip_sparsebatch *h);
 
@@ -962,6 +1024,11 @@ int thip_raggedsparse_set_bc(thip_raggedsparse *h, int first, int count, const f
                              const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
 int thip_raggedsparse_solutions(thip_raggedsparse *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
 int thip_raggedsparse_set_a(thip_raggedsparse *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_raggedsparse_set_bc_dev(thip_raggedsparse *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_raggedsparse_set_a_dev(thip_raggedsparse *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_raggedsparse_set_iterates_dev(thip_raggedsparse *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_raggedsparse_solutions_dev(thip_raggedsparse *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info);
 int thip_raggedsparse_destroy(thip_raggedsparse *h);
 

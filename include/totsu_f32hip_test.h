@@ -303,6 +303,22 @@ int thip_test_raggedsparse_plan(size_t n_prob, const size_t *host_n, const size_
                                 int *host_layout, int64_t *host_arena_at, int64_t *host_blob_at, int *host_lds_at, int *host_resident,
                                 thip_raggedsparse_info_t *host_info);
 
+/* TEST HOOKS of the round calls on device memory (thip_NAME_set_bc_dev ..; h: a handle of any own-A batch family).
+ * _addresses reports ADDRESSES ONLY: host_addr[0 .. 2], host_bytes[0 .. 2] <- where the handle's arena, its device staging buffer
+ * and its b / c store lie and how many bytes each holds (0, 0: not allocated yet).
+ * _last_transfer: the bytes the last _dev call on the handle moved host -> device and device -> host (tables, verdict words, status
+ * blocks; a call that was refused early leaves zeros).
+ * _overlap: 1 when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte, else 0 -- the rule of the refusals (no device).
+ * _offsets: where each problem's part begins in the packed arrays of a range of `count` problems of the shapes host_n, host_m (no
+ * device): host_at holds 5 rows of count + 1 entries, in floats -- c / a solution's x (n each), b / row sums / a solution's y (m),
+ * an iterate's x (n + 2 m + 1), its y (n + m + 1), a dense A (m n); the last entry of a row is the array's length.
+ * _copy_chunk: the floats one workgroup of the dense copy kernel moves */
+int thip_test_ownbatch_addresses(void *h, uint64_t *host_addr, uint64_t *host_bytes);
+int thip_test_ownbatch_last_transfer(void *h, uint64_t *host_h2d_bytes, uint64_t *host_d2h_bytes);
+int thip_test_ownbatch_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
+int thip_test_ownbatch_offsets(size_t count, const size_t *host_n, const size_t *host_m, int64_t *host_at);
+int thip_test_ownbatch_copy_chunk(void);
+
 #ifdef __cplusplus
 }
 #endif

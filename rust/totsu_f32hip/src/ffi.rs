@@ -359,6 +359,10 @@ extern "C" {
     pub fn thip_smallbatch_set_bc(h: *mut thip_smallbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_smallbatch_solutions(h: *mut thip_smallbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_smallbatch_set_a(h: *mut thip_smallbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_smallbatch_set_bc_dev(h: *mut thip_smallbatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_smallbatch_set_a_dev(h: *mut thip_smallbatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_smallbatch_set_iterates_dev(h: *mut thip_smallbatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_smallbatch_solutions_dev(h: *mut thip_smallbatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_smallbatch_info(h: *const thip_smallbatch, host_info: *mut thip_smallbatch_info_t) -> c_int;
     pub fn thip_smallbatch_destroy(h: *mut thip_smallbatch) -> c_int;
     pub fn thip_test_smallbatch_force_threads(h: *mut thip_smallbatch, threads: c_int) -> c_int;
@@ -383,6 +387,10 @@ extern "C" {
     pub fn thip_midbatch_set_bc(h: *mut thip_midbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_midbatch_solutions(h: *mut thip_midbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_midbatch_set_a(h: *mut thip_midbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_midbatch_set_bc_dev(h: *mut thip_midbatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_midbatch_set_a_dev(h: *mut thip_midbatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_midbatch_set_iterates_dev(h: *mut thip_midbatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_midbatch_solutions_dev(h: *mut thip_midbatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_midbatch_info(h: *const thip_midbatch, host_info: *mut thip_midbatch_info_t) -> c_int;
     pub fn thip_midbatch_destroy(h: *mut thip_midbatch) -> c_int;
     pub fn thip_test_midbatch_force_threads(h: *mut thip_midbatch, threads: c_int) -> c_int;
@@ -407,6 +415,10 @@ extern "C" {
     pub fn thip_sdpbatch_set_bc(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_sdpbatch_solutions(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_sdpbatch_set_a(h: *mut thip_sdpbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_sdpbatch_set_bc_dev(h: *mut thip_sdpbatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_sdpbatch_set_a_dev(h: *mut thip_sdpbatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_sdpbatch_set_iterates_dev(h: *mut thip_sdpbatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_sdpbatch_solutions_dev(h: *mut thip_sdpbatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_sdpbatch_info(h: *const thip_sdpbatch, host_info: *mut thip_sdpbatch_info_t) -> c_int;
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
@@ -436,6 +448,10 @@ extern "C" {
     pub fn thip_raggedbatch_set_bc(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedbatch_solutions(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_raggedbatch_set_a(h: *mut thip_raggedbatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedbatch_set_bc_dev(h: *mut thip_raggedbatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedbatch_set_a_dev(h: *mut thip_raggedbatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedbatch_set_iterates_dev(h: *mut thip_raggedbatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_raggedbatch_solutions_dev(h: *mut thip_raggedbatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_raggedbatch_info(h: *const thip_raggedbatch, host_info: *mut thip_raggedbatch_info_t) -> c_int;
     pub fn thip_raggedbatch_destroy(h: *mut thip_raggedbatch) -> c_int;
     pub fn thip_test_raggedbatch_force_threads(h: *mut thip_raggedbatch, threads: c_int) -> c_int;
@@ -465,6 +481,10 @@ extern "C" {
     pub fn thip_sparsebatch_set_bc(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_sparsebatch_solutions(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_sparsebatch_set_a(h: *mut thip_sparsebatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_sparsebatch_set_bc_dev(h: *mut thip_sparsebatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_sparsebatch_set_a_dev(h: *mut thip_sparsebatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_sparsebatch_set_iterates_dev(h: *mut thip_sparsebatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_sparsebatch_solutions_dev(h: *mut thip_sparsebatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_sparsebatch_info(h: *const thip_sparsebatch, host_info: *mut thip_sparsebatch_info_t) -> c_int;
     pub fn thip_sparsebatch_destroy(h: *mut thip_sparsebatch) -> c_int;
     pub fn thip_test_sparsebatch_force_threads(h: *mut thip_sparsebatch, threads: c_int) -> c_int;
@@ -499,6 +519,10 @@ extern "C" {
     pub fn thip_raggedsparse_set_bc(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
     pub fn thip_raggedsparse_solutions(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
     pub fn thip_raggedsparse_set_a(h: *mut thip_raggedsparse, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedsparse_set_bc_dev(h: *mut thip_raggedsparse, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedsparse_set_a_dev(h: *mut thip_raggedsparse, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_raggedsparse_set_iterates_dev(h: *mut thip_raggedsparse, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_raggedsparse_solutions_dev(h: *mut thip_raggedsparse, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
     pub fn thip_raggedsparse_info(h: *const thip_raggedsparse, host_info: *mut thip_raggedsparse_info_t) -> c_int;
     pub fn thip_raggedsparse_destroy(h: *mut thip_raggedsparse) -> c_int;
     pub fn thip_test_raggedsparse_force_threads(h: *mut thip_raggedsparse, threads: c_int) -> c_int;
@@ -510,6 +534,11 @@ extern "C" {
                                        host_order: *mut c_int, host_layout: *mut c_int, host_arena_at: *mut i64,
                                        host_blob_at: *mut i64, host_lds_at: *mut c_int, host_resident: *mut c_int,
                                        host_info: *mut thip_raggedsparse_info_t) -> c_int;
+    pub fn thip_test_ownbatch_addresses(h: *mut c_void, host_addr: *mut u64, host_bytes: *mut u64) -> c_int;
+    pub fn thip_test_ownbatch_last_transfer(h: *mut c_void, host_h2d_bytes: *mut u64, host_d2h_bytes: *mut u64) -> c_int;
+    pub fn thip_test_ownbatch_overlap(a: u64, a_bytes: u64, b: u64, b_bytes: u64) -> c_int;
+    pub fn thip_test_ownbatch_offsets(count: usize, host_n: *const usize, host_m: *const usize, host_at: *mut i64) -> c_int;
+    pub fn thip_test_ownbatch_copy_chunk() -> c_int;
 
     pub fn thip_comm_unique_id(host_id128: *mut u8) -> c_int;
     pub fn thip_comm_init(rank: c_int, world: c_int, host_id128: *const u8) -> c_int;

@@ -47,6 +47,9 @@ looks up in a table, resident or streamed per problem:
 
 Each family's set_a kernel (*_seta_k; the sparse families' *_scatter_k too) is required and held to its family's bounds as well.
 
+Every family's translation unit also carries the four kernels of the round calls on device memory (thip_ownbatch.h: ownbatch_check_k,
+ownbatch_copy_a_k, ownbatch_stage_bc_k, ownbatch_gather_final_k): required, no scratch, at most 64 VGPRs, >= 4 waves per SIMD.
+
 usage: check_kernel_resources.py <remarks file> [--report]
                                  [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch|
                                           raggedsparse]"""
@@ -116,7 +119,38 @@ OWNBATCH = {
 }
 
 
+# the kernels of the round calls on device memory, one copy per family's translation unit (thip_ownbatch.h)
+DEVROUND = ("ownbatch_check_k", "ownbatch_copy_a_k", "ownbatch_stage_bc_k", "ownbatch_gather_final_k")
+DEVROUND_MAX_VGPRS = 64
+
+
+def check_devround(res):
+    bad, seen = [], set()
+    for name, r in sorted(res.items()):
+        m = re.search(r"ownbatch_(check|copy_a|stage_bc|gather_final)_k", name)
+        if not m or "scratch" not in r:
+            continue
+        seen.add(m.group(0))
+        ok = r["scratch"] == 0 and r.get("occupancy", 0) >= 4 and r.get("vgprs", 999) <= DEVROUND_MAX_VGPRS
+        if "--report" in sys.argv or not ok:
+            print("%s: %d VGPRs, %d spilled, scratch %d B/lane, %d waves/SIMD" % (name, r.get("vgprs", -1), r.get("vgpr_spill", -1),
+                                                                                 r["scratch"], r.get("occupancy", -1)))
+        if not ok:
+            bad.append(name)
+    if not set(DEVROUND) <= seen:
+        print("check_kernel_resources: %s not in the remarks (thip_ownbatch.h)" % " / ".join(sorted(set(DEVROUND) - seen)))
+        return 2
+    if bad:
+        print("check_kernel_resources: FAILED for %s: scratch in use, > %d VGPRs or < 4 waves/SIMD -- the kernels of the round calls on "
+              "device memory are plain copies and scans (thip_ownbatch.h)" % (bad, DEVROUND_MAX_VGPRS))
+        return 1
+    return 0
+
+
 def check_ownbatch(res, family):
+    rc = check_devround(res)
+    if rc:
+        return rc
     pat, need, max_vgprs, what, src = OWNBATCH[family]
     bad, seen = [], set()
     for name, r in sorted(res.items()):

@@ -320,6 +320,10 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "set_bc": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
         _p + "solutions": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(Status)]),
         _p + "set_a": (_i, [_vp, _i, _i, _vp, _vp, _i]),
+        _p + "set_bc_dev": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
+        _p + "set_a_dev": (_i, [_vp, _i, _i, _vp, _i]),
+        _p + "set_iterates_dev": (_i, [_vp, _i, _i, _vp, _vp]),
+        _p + "solutions_dev": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
         _p + "info": (_i, [_vp, C.POINTER(_info)]),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
@@ -345,6 +349,10 @@ PROTOTYPES.update({
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
+    _p + "set_bc_dev": PROTOTYPES["thip_sdpbatch_set_bc_dev"],
+    _p + "set_a_dev": PROTOTYPES["thip_sdpbatch_set_a_dev"],
+    _p + "set_iterates_dev": PROTOTYPES["thip_sdpbatch_set_iterates_dev"],
+    _p + "solutions_dev": PROTOTYPES["thip_sdpbatch_solutions_dev"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedbatch_force_threads": (_i, [_vp, _i]),
@@ -370,6 +378,10 @@ PROTOTYPES.update({
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
+    _p + "set_bc_dev": PROTOTYPES["thip_sdpbatch_set_bc_dev"],
+    _p + "set_a_dev": PROTOTYPES["thip_sdpbatch_set_a_dev"],
+    _p + "set_iterates_dev": PROTOTYPES["thip_sdpbatch_set_iterates_dev"],
+    _p + "solutions_dev": PROTOTYPES["thip_sdpbatch_solutions_dev"],
     _p + "info": (_i, [_vp, C.POINTER(SparseBatchInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_sparsebatch_force_threads": (_i, [_vp, _i]),
@@ -398,6 +410,10 @@ PROTOTYPES.update({
     _p + "set_bc": PROTOTYPES["thip_sdpbatch_set_bc"],
     _p + "solutions": PROTOTYPES["thip_sdpbatch_solutions"],
     _p + "set_a": PROTOTYPES["thip_sdpbatch_set_a"],
+    _p + "set_bc_dev": PROTOTYPES["thip_sdpbatch_set_bc_dev"],
+    _p + "set_a_dev": PROTOTYPES["thip_sdpbatch_set_a_dev"],
+    _p + "set_iterates_dev": PROTOTYPES["thip_sdpbatch_set_iterates_dev"],
+    _p + "solutions_dev": PROTOTYPES["thip_sdpbatch_solutions_dev"],
     _p + "info": (_i, [_vp, C.POINTER(RaggedSparseInfo)]),
     _p + "destroy": PROTOTYPES["thip_sdpbatch_destroy"],
     "thip_test_raggedsparse_force_threads": (_i, [_vp, _i]),
@@ -407,7 +423,18 @@ PROTOTYPES.update({
                                          C.POINTER(RaggedSparseInfo)]),
 })
 
-_NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen"}
+# the test hooks of the round calls on device memory, shared by the six own-A families (totsu_amd/csrc/thip_ownbatch.h)
+_pu64 = C.POINTER(_u64)
+PROTOTYPES.update({
+    "thip_test_ownbatch_addresses": (_i, [_vp, _pu64, _pu64]),
+    "thip_test_ownbatch_last_transfer": (_i, [_vp, _pu64, _pu64]),
+    "thip_test_ownbatch_overlap": (_i, [_u64, _u64, _u64, _u64]),
+    "thip_test_ownbatch_offsets": (_i, [_sz, _psz, _psz, _p64]),
+    "thip_test_ownbatch_copy_chunk": (_i, []),
+})
+
+_NOCHECK = {"thip_last_error", "thip_version", "thip_get_stream", "thip_map_eig_worklen", "thip_test_ownbatch_overlap",
+            "thip_test_ownbatch_copy_chunk"}
 
 _cdll = None
 

@@ -345,6 +345,118 @@ __global__ __launch_bounds__(256) void ownbatch_gather_k(const ObGather g)
     for (int i = (int)threadIdx.x; i < m; i += (int)blockDim.x) out[n + i] = ar[4 * n + i];
 }
 
+// ---- the round calls on device memory (thip_NAME_set_bc_dev / _set_a_dev / _set_iterates_dev / _solutions_dev) -------------------
+// Four kernels, each a launch of its own ahead of the family's set kernel: none writes a word that it or a kernel fused behind it
+// reads, so a store never meets a (possibly scalar) load of the same word without a kernel boundary between them.
+
+// one part of a range as the check and the copy kernels see it: n floats at src, which go to dst
+struct ObDevRow { const float *src; float *dst; long long n; };
+
+constexpr int OB_COPY_CHUNK = 4096;         // floats per workgroup of ownbatch_copy_a_k: 256 threads, four 16-byte moves each
+
+// the scan the host cannot make: one workgroup and one verdict word per problem.  mode 0: row k's n floats at src are finite (v - v
+// == 0; ob_seta_check's rule) or verdict[k] = 1.  mode 1: the float at src is a start's tau, the one at dst its kappa
+// (ob_start_scalars' rule): 1 for a tau that is negative or not finite, 2 for a kappa that is positive or not finite.  Every word
+// of the verdict is written
+__global__ __launch_bounds__(256) void ownbatch_check_k(const ObDevRow *rows, int mode, int *verdict)
+{
+    const ObDevRow r = rows[blockIdx.x];
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+    if (mode == 1) {                        // (uniform: the mode is an argument)
+        if (tid == 0) {
+            const float tau = r.src[0], kappa = r.dst[0];
+            int v = 0;
+            if (!(tau >= 0.0f) || tau - tau != 0.0f) v = 1;
+            else if (!(kappa <= 0.0f) || kappa - kappa != 0.0f) v = 2;
+            verdict[blockIdx.x] = v;
+        }
+        return;
+    }
+    int bad = 0;
+    long long done = 0;
+    if (((uintptr_t)r.src & 15u) == 0) {
+        const long long n4 = r.n >> 2;
+        const float4 *s4 = reinterpret_cast<const float4 *>(r.src);
+        for (long long i = tid; i < n4; i += T) {
+            const float4 v = s4[i];
+            bad |= (v.x - v.x != 0.0f) | (v.y - v.y != 0.0f) | (v.z - v.z != 0.0f) | (v.w - v.w != 0.0f);
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + tid; i < r.n; i += T) { const float v = r.src[i]; bad |= v - v != 0.0f; }
+    bad = __syncthreads_or(bad);
+    if (tid == 0) verdict[blockIdx.x] = bad != 0;
+}
+
+// the streaming copy: workgroup (k, j) moves floats j C .. of row k, C = OB_COPY_CHUNK, whatever allocations the rows lie in.  16-byte
+// loads and stores where both sides of the chunk are 16-byte aligned (a chunk is a multiple of 16 bytes, so every chunk of a row
+// is or none), 4-byte ones otherwise; the tail of the last chunk by 4-byte moves
+__global__ __launch_bounds__(256) void ownbatch_copy_a_k(const ObDevRow *rows)
+{
+    const ObDevRow r = rows[blockIdx.x];
+    const long long beg = (long long)blockIdx.y * OB_COPY_CHUNK;
+    if (beg >= r.n) return;
+    const int cnt = (int)(r.n - beg < OB_COPY_CHUNK ? r.n - beg : OB_COPY_CHUNK), tid = (int)threadIdx.x, T = (int)blockDim.x;
+    const float *s = r.src + beg;
+    float *d = r.dst + beg;
+    int done = 0;
+    if ((((uintptr_t)s | (uintptr_t)d) & 15u) == 0) {
+        const int n4 = cnt >> 2;
+        const float4 *s4 = reinterpret_cast<const float4 *>(s);
+        float4 *d4 = reinterpret_cast<float4 *>(d);
+        int i = tid;
+        for (; i + 3 * T < n4; i += 4 * T) {                     // (a full chunk: the thread's four loads in flight together)
+            const float4 a = s4[i], b = s4[i + T], c = s4[i + 2 * T], e = s4[i + 3 * T];
+            d4[i] = a; d4[i + T] = b; d4[i + 2 * T] = c; d4[i + 3 * T] = e;
+        }
+        for (; i < n4; i += T) d4[i] = s4[i];
+        done = n4 << 2;
+    }
+    for (int i = done + tid; i < cnt; i += T) d[i] = s[i];
+}
+
+// one problem's new b, c and row sums (r: NULL, none) into the staged form the set_bc kernels read (ob_setbc_pack's, at `to`)
+struct ObBcRow { const float *b, *c, *r; float *to; int n, m; };
+
+__global__ __launch_bounds__(256) void ownbatch_stage_bc_k(const ObBcRow *rows)
+{
+    const ObBcRow q = rows[blockIdx.x];
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+    if (tid == 0) reinterpret_cast<int *>(q.to)[0] = q.r != nullptr;
+    float *const b = q.to + 1, *const c = b + q.m, *const r = c + q.n;
+    for (int i = tid; i < q.m; i += T) { b[i] = q.b[i]; r[i] = q.r ? q.r[i] : 0.0f; }
+    for (int i = tid; i < q.n; i += T) c[i] = q.c[i];
+}
+
+// ownbatch_gather_k with ob_finalize's rule and the state word: problem first + k's x_x to x + its place, its x_y to y + its place,
+// its state to state[k] (each of x, y, state may be NULL).  at == NULL: one shape -- the places are k n and k m.  Else at holds, for
+// EVERY problem p of the batch, (block, n, m, the x's before p, the y's before p), and x0, y0 are those of `first`.  The scaling is
+// rt = 1 / tau, correctly rounded, then rt * v, when kind == 0 and the state is OK or ExcessIter; else the floats as they lie
+struct ObGatherDev {
+    const float *arena; const SbStatus *st; const long long *at; size_t stride; int n, m, first; long long x0, y0;
+    float *x, *y; int *state;
+};
+
+__global__ __launch_bounds__(256) void ownbatch_gather_final_k(const ObGatherDev g)
+{
+    const long long k = blockIdx.x, p = g.first + k;
+    const long long *const t = g.at ? g.at + 5 * p : nullptr;
+    const float *ar = t ? g.arena + t[0] : g.arena + (size_t)p * g.stride;
+    const int n = t ? (int)t[1] : g.n, m = t ? (int)t[2] : g.m;
+    const int state = g.st[p].state, kind = g.st[p].kind;
+    const bool scale = kind == 0 && (state == THIP_ST_OK || state == THIP_ST_EXCESS_ITER);
+    const float rt = scale ? __fdiv_rn(1.0f, g.st[p].tau) : 1.0f;
+    if (g.x) {
+        float *out = g.x + (t ? t[3] - g.x0 : k * (long long)n);
+        for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) out[i] = scale ? __fmul_rn(rt, ar[i]) : ar[i];
+    }
+    if (g.y) {
+        float *out = g.y + (t ? t[4] - g.y0 : k * (long long)m);
+        for (int i = (int)threadIdx.x; i < m; i += (int)blockDim.x) out[i] = scale ? __fmul_rn(rt, ar[4 * n + i]) : ar[4 * n + i];
+    }
+    if (g.state && threadIdx.x == 0) g.state[k] = state;
+}
+
 __global__ void ownbatch_slots_k(SbSlot *slots, int n_prob, const float *a, const float *b, const float *c, const float *rowabs,
                                  size_t m, size_t n)
 {
@@ -419,6 +531,15 @@ struct OwnBatch {
     std::vector<uintptr_t> slot_base;
     std::vector<unsigned char> unaligned;   // (a family that streams A) per slot: the problem's A is not 16-byte aligned
     size_t n_unaligned = 0;                 // how many: decides the load path info() reports
+    // every device allocation of the handle (ob_alloc): what no array handed to a _dev call may overlap
+    std::vector<std::pair<uintptr_t, size_t>> owned;
+    // a handle of many shapes: solutions_dev's table of every problem (block, n, m, x's before, y's before), made by its first call
+    long long *sol_at_dev = nullptr;
+    // the tables the kernels of a _dev call read and the verdict words its check kernel writes: pinned host memory mapped into the
+    // device's address space (tab_dev: the same bytes as the kernels address them), grown on demand -- NOT device memory, so that a
+    // call which moves A in place allocates none
+    void *tab_host = nullptr, *tab_dev = nullptr; size_t tab_bytes = 0;
+    size_t last_h2d = 0, last_d2h = 0;      // what the last _dev call moved between host and device (thip_test_ownbatch_last_transfer)
 };
 
 // the cone segments (no device needed).  On success *cones holds (beg, end, kind) per block cone -- kind 0: second-order, 1: rotated,
@@ -460,6 +581,7 @@ int ob_alloc(OwnBatch *h, void **p, size_t bytes)
 {
     THIP_TRY(hipMalloc(p, bytes));
     h->bytes += bytes; h->fam->total += bytes;
+    h->owned.emplace_back((uintptr_t)*p, bytes);
     return 0;
 }
 
@@ -595,8 +717,9 @@ int ob_destroy(H *h)
     if (!h) return 0;
     if (ctx().inited) hipStreamSynchronize(ctx().stream);
     hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
-    hipFree(h->stage); hipFree(h->bc_store); hipFree(h->bc_at_dev);
+    hipFree(h->stage); hipFree(h->bc_store); hipFree(h->bc_at_dev); hipFree(h->sol_at_dev);
     if (h->stage_host) hipHostFree(h->stage_host);
+    if (h->tab_host) hipHostFree(h->tab_host);
     if (h->hst) hipHostFree(h->hst);
     h->fam->total -= h->bytes;
     delete h;
@@ -774,6 +897,8 @@ int ob_stage_reserve(OwnBatch *h, size_t bytes, void **host)
     if (h->stage_bytes < bytes) {
         THIP_TRY(hipStreamSynchronize(ctx().stream));
         THIP_TRY(hipFree(h->stage));
+        h->owned.erase(std::remove_if(h->owned.begin(), h->owned.end(), [&](const std::pair<uintptr_t, size_t> &o) { return o.first == (uintptr_t)h->stage; }),
+                       h->owned.end());
         h->stage = nullptr;
         if (h->stage_host) THIP_TRY(hipHostFree(h->stage_host));
         h->stage_host = nullptr;
@@ -1053,6 +1178,404 @@ int ob_solutions(const ObFamily &f, OwnBatch *h, int first, int count, float *ho
                           [&](int, size_t *n, size_t *m) { *n = h->n; *m = h->m; }, [](int) { return 0ll; });
 }
 
+// ---- the round calls on device memory: the host side -----------------------------------------------------------------------------
+// Each is its host twin with the packing done by a kernel: the tables go up (a few dozen bytes per problem), the check kernel's
+// verdict comes down BEFORE anything is copied, scattered or set, the data moves device to device into the layout the host call
+// uploads, and the family's set kernel runs as it does there.
+
+// two ranges of bytes share one
+bool ob_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return na && nb && a < b + nb && b < a + na; }
+
+// the lengths of one problem's part in each packed array of a range: 0 c / a solution's x (n), 1 b / row sums / a solution's y (m),
+// 2 an iterate's x (n + 2 m + 1), 3 its y (n + m + 1), 4 a dense A (m n).  A range's array is its problems' parts one after another
+constexpr int OB_DEV_KINDS = 5;
+void ob_dev_lengths(size_t n, size_t m, long long *len)
+{
+    len[0] = (long long)n; len[1] = (long long)m; len[2] = (long long)(n + 2 * m + 1); len[3] = (long long)(n + m + 1);
+    len[4] = (long long)(m * n);
+}
+
+// an array handed to a _dev call holds floats and lies outside everything the handle owns
+int ob_dev_foreign(const OwnBatch *h, const void *p, size_t bytes, const char *what)
+{
+    char msg[160];
+    if ((uintptr_t)p & 3u) {
+        snprintf(msg, sizeof(msg), "%s: the arrays hold floats: 4-byte alignment", what);
+        return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+    }
+    for (const auto &o : h->owned)
+        if (p && ob_overlap((uintptr_t)p, bytes, o.first, o.second)) {
+            snprintf(msg, sizeof(msg), "%s overlaps memory the batch owns (its arena, its staging buffer, its store of b and c)", what);
+            return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+        }
+    return 0;
+}
+
+int ob_dev_range(const ObFamily &f, OwnBatch *h, int first, int count)
+{
+    if (!h) return fail(THIP_E_INVALID, f.text.null_h, __FILE__, __LINE__);
+    if (!h->inited) return fail(THIP_E_INVALID, f.text.uninit, __FILE__, __LINE__);
+    if (count < 1 || first < 0 || (size_t)first + (size_t)count > h->n_prob)
+        return fail(THIP_E_INVALID, "no such range of problems", __FILE__, __LINE__);
+    h->last_h2d = h->last_d2h = 0;
+    return 0;
+}
+
+// `bytes` of pinned, device-mapped host memory for a _dev call's tables and verdict words
+int ob_tab_reserve(OwnBatch *h, size_t bytes)
+{
+    if (h->tab_bytes >= bytes) return 0;
+    THIP_TRY(hipStreamSynchronize(ctx().stream));
+    if (h->tab_host) THIP_TRY(hipHostFree(h->tab_host));
+    h->tab_host = h->tab_dev = nullptr; h->tab_bytes = 0;
+    THIP_TRY(hipHostMalloc(&h->tab_host, bytes, hipHostMallocMapped));
+    THIP_TRY(hipHostGetDevicePointer(&h->tab_dev, h->tab_host, 0));
+    h->tab_bytes = bytes;
+    return 0;
+}
+
+// the buffers of a _dev call, each part a multiple of 16 bytes.  [verdict | tables] in the handle's pinned, device-mapped memory
+// (tab / tab_dev: as the host and as the kernels address it): one verdict word per problem, written by the check kernel and read by
+// the host behind a synchronisation, and the rows the new kernels read -- a few dozen bytes per problem over the bus, no device
+// memory.  [head | floats] in the staging buffers of the host calls (pin / dev): the layout the host twin uploads -- where each
+// workgroup's part lies and the classes' lists; the parts -- which the family's kernels read as they do there
+struct ObDevStage {
+    size_t verdict = 0, tables = 0, head = 0, floats = 0;
+    unsigned char *tab = nullptr, *tab_dev = nullptr, *pin = nullptr, *dev = nullptr;
+    static size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+    int reserve(OwnBatch *h)
+    {
+        verdict = up16(verdict); tables = up16(tables); head = up16(head); floats = up16(floats);
+        THIP_RC(ob_tab_reserve(h, std::max<size_t>(verdict + tables, 16)));
+        tab = static_cast<unsigned char *>(h->tab_host);
+        tab_dev = static_cast<unsigned char *>(h->tab_dev);
+        if (head + floats) {
+            void *p = nullptr;
+            THIP_RC(ob_stage_reserve(h, head + floats, &p));
+            pin = static_cast<unsigned char *>(p);
+            dev = static_cast<unsigned char *>(h->stage);
+        }
+        return 0;
+    }
+    unsigned char *rows() const { return tab + verdict; }                   // (the host's view of the tables)
+    const unsigned char *rows_dev() const { return tab_dev + verdict; }     // (the kernels')
+    size_t at_head() const { return 0; }
+    size_t at_floats() const { return head; }
+    // the head up; the tables are read where they lie
+    int upload(OwnBatch *h) const
+    {
+        h->last_h2d += tables;
+        if (head == 0) return 0;
+        THIP_TRY(hipMemcpyAsync(dev, pin, head, hipMemcpyHostToDevice, ctx().stream));
+        h->last_h2d += head;
+        return 0;
+    }
+    // the check kernel on the `count` rows at the tables' beginning and its verdict (synchronises): *row < 0, or the first row at
+    // fault and in *why its word
+    int check(OwnBatch *h, int count, int mode, int *row, int *why) const
+    {
+        hipStream_t st = ctx().stream;
+        hipLaunchKernelGGL(ownbatch_check_k, dim3((unsigned)count), dim3(256), 0, st, reinterpret_cast<const ObDevRow *>(rows_dev()), mode,
+                           reinterpret_cast<int *>(tab_dev));
+        THIP_LAUNCH_CHECK();
+        THIP_TRY(hipStreamSynchronize(st));
+        h->last_d2h += (size_t)count * sizeof(int);
+        *row = -1; *why = 0;
+        const volatile int *v = reinterpret_cast<const volatile int *>(tab);
+        for (int k = 0; k < count && *row < 0; ++k)
+            if (v[k] != 0) { *row = k; *why = v[k]; }
+        return 0;
+    }
+};
+
+// ownbatch_copy_a_k on the `count` rows at dev_rows, the longest of which holds `most` floats
+int ob_dev_copy(const ObDevRow *dev_rows, size_t count, size_t most)
+{
+    const size_t chunks = (most + OB_COPY_CHUNK - 1) / OB_COPY_CHUNK;
+    if (count == 0 || chunks == 0) return 0;
+    if (chunks > 65535) return fail(THIP_E_INVALID, "a problem's part is too long for one copy launch", __FILE__, __LINE__);
+    hipLaunchKernelGGL(ownbatch_copy_a_k, dim3((unsigned)count, (unsigned)chunks), dim3(256), 0, ctx().stream, dev_rows);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// what every set_*_dev ends with: the family's launches, then the host's books (synchronises)
+template <class LAUNCH>
+int ob_dev_finish(OwnBatch *h, int first, int count, const LAUNCH &launch)
+{
+    const int rc = launch();
+    if (rc != 0) { hipStreamSynchronize(ctx().stream); return rc; }
+    h->last_d2h += (size_t)count * sizeof(SbStatus);
+    return ob_restarted(h, first, count);
+}
+
+// thip_NAME_set_a_dev of a dense family.  floats(p): problem p's m n.  dev_values == NULL: the caller has rewritten A where the slots
+// read it, and the check kernel scans that.  launch(): the family's set_a kernel(s) on the range
+template <class FLOATS, class LAUNCH>
+int ob_set_a_dev_dense_t(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_values, const FLOATS &floats,
+                         const LAUNCH &launch)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    const size_t cnt = (size_t)count;
+    size_t total = 0, most = 0;
+    for (size_t k = 0; k < cnt; ++k) { const size_t w = floats(first + (int)k); total += w; most = std::max(most, w); }
+    if (dev_values) {
+        THIP_RC(ob_dev_foreign(h, dev_values, total * sizeof(float), "dev_values"));
+        for (size_t k = 0; k < cnt; ++k)
+            if (ob_overlap((uintptr_t)dev_values, total * sizeof(float), (uintptr_t)h->slot_a[(size_t)first + k],
+                           floats(first + (int)k) * sizeof(float)))
+                return fail(THIP_E_INVALID, "dev_values overlaps the A of a slot of the range (the in-place form: NULL)", __FILE__, __LINE__);
+    }
+    ObDevStage sg;
+    sg.verdict = cnt * sizeof(int); sg.tables = cnt * sizeof(ObDevRow);
+    THIP_RC(sg.reserve(h));
+    ObDevRow *rows = reinterpret_cast<ObDevRow *>(sg.rows());
+    const float *src = dev_values;
+    for (size_t k = 0; k < cnt; ++k) {
+        float *const to = const_cast<float *>(h->slot_a[(size_t)first + k]);
+        const size_t w = floats(first + (int)k);
+        rows[k] = ObDevRow{ dev_values ? src : to, to, (long long)w };
+        src += w;
+    }
+    THIP_RC(sg.upload(h));
+    int row, why;
+    THIP_RC(sg.check(h, count, 0, &row, &why));
+    if (row >= 0) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "problem %d: a value of A is not finite", first + row);
+        return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+    }
+    if (dev_values) THIP_RC(ob_dev_copy(reinterpret_cast<const ObDevRow *>(sg.rows_dev()), cnt, most));
+    return ob_dev_finish(h, first, count, launch);
+}
+
+int ob_set_a_dev(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_values, int keep)
+{
+    const size_t per = h ? h->m * h->n : 0;
+    return ob_set_a_dev_dense_t(f, h, first, count, dev_values, [&](int) { return per; }, [&]() {
+        ObArgs a = ob_args(h);
+        a.first = first;
+        return f.seta(h, a, ObSetA{ ObStart{ nullptr, nullptr, 0 }, keep != 0 }, (unsigned)count);
+    });
+}
+
+// thip_NAME_set_a_dev of a sparse family: the values stay where the caller holds them, need(p) per problem one after another, and
+// the scatter kernel reads them there.  head: the bytes of the host twin's head; fill(pin_head, at_p): writes it, at_p[k] being where
+// problem first + k's values begin (in floats); launch(dev_head): the scatter and the set_a kernel(s) with ObStart{ dev_values, .. }
+template <class NEED, class FILL, class LAUNCH>
+int ob_set_a_dev_sparse_t(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_values, const NEED &need, size_t head,
+                          const FILL &fill, const LAUNCH &launch)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    if (!dev_values)
+        return fail(THIP_E_INVALID, "null values of A: a sparse batch is handed its values (the in-place form is a dense batch's)", __FILE__,
+                    __LINE__);
+    const size_t cnt = (size_t)count;
+    std::vector<long long> at_p(cnt);
+    size_t total = 0;
+    for (size_t k = 0; k < cnt; ++k) { at_p[k] = (long long)total; total += need(first + (int)k); }
+    THIP_RC(ob_dev_foreign(h, dev_values, total * sizeof(float), "dev_values"));
+    ObDevStage sg;
+    sg.verdict = cnt * sizeof(int); sg.tables = cnt * sizeof(ObDevRow); sg.head = head;
+    THIP_RC(sg.reserve(h));
+    ObDevRow *rows = reinterpret_cast<ObDevRow *>(sg.rows());
+    for (size_t k = 0; k < cnt; ++k) rows[k] = ObDevRow{ dev_values + at_p[k], nullptr, (long long)need(first + (int)k) };
+    fill(sg.pin + sg.at_head(), at_p);
+    THIP_RC(sg.upload(h));
+    int row, why;
+    THIP_RC(sg.check(h, count, 0, &row, &why));
+    if (row >= 0) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "problem %d: a value of A is not finite", first + row);
+        return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+    }
+    const unsigned char *const dev_head = sg.dev + sg.at_head();
+    return ob_dev_finish(h, first, count, [&]() { return launch(dev_head); });
+}
+
+// thip_NAME_set_iterates_dev.  shape(p, &n, &m); head, fill as above with at_p[k] where problem first + k's staged iterate begins;
+// launch(dev_head, dev_floats): the start kernel(s).  The iterates are copied into the staged layout (x then y per problem) by
+// ownbatch_copy_a_k, two rows per problem, and the start kernels read them as they read an upload
+template <class SHAPE, class FILL, class LAUNCH>
+int ob_set_iterates_dev_t(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_x, const float *dev_y, const SHAPE &shape,
+                          size_t head, const FILL &fill, const LAUNCH &launch)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    if (!dev_x || !dev_y) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    const size_t cnt = (size_t)count;
+    std::vector<long long> at_p(cnt);
+    size_t floats = 0, sum_x = 0, sum_y = 0, most = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+        size_t n, m;
+        shape(first + (int)k, &n, &m);
+        long long len[OB_DEV_KINDS];
+        ob_dev_lengths(n, m, len);
+        at_p[k] = (long long)floats;
+        floats += (size_t)(len[2] + len[3]); sum_x += (size_t)len[2]; sum_y += (size_t)len[3];
+        most = std::max(most, (size_t)len[2]);
+    }
+    THIP_RC(ob_dev_foreign(h, dev_x, sum_x * sizeof(float), "dev_x"));
+    THIP_RC(ob_dev_foreign(h, dev_y, sum_y * sizeof(float), "dev_y"));
+    ObDevStage sg;
+    sg.verdict = cnt * sizeof(int); sg.tables = 3 * cnt * sizeof(ObDevRow); sg.head = head; sg.floats = floats * sizeof(float);
+    THIP_RC(sg.reserve(h));
+    ObDevRow *rows = reinterpret_cast<ObDevRow *>(sg.rows());
+    float *const to = reinterpret_cast<float *>(sg.dev + sg.at_floats());
+    {
+        const float *x = dev_x, *y = dev_y;
+        for (size_t k = 0; k < cnt; ++k) {
+            size_t n, m;
+            shape(first + (int)k, &n, &m);
+            long long len[OB_DEV_KINDS];
+            ob_dev_lengths(n, m, len);
+            const size_t nx = (size_t)len[2], ny = (size_t)len[3];
+            rows[k] = ObDevRow{ x + nx - 1, const_cast<float *>(y + ny - 1), 1 };          // (the check's: tau, kappa)
+            rows[cnt + 2 * k] = ObDevRow{ x, to + at_p[k], (long long)nx };
+            rows[cnt + 2 * k + 1] = ObDevRow{ y, to + at_p[k] + nx, (long long)ny };
+            x += nx; y += ny;
+        }
+    }
+    fill(sg.pin + sg.at_head(), at_p);
+    THIP_RC(sg.upload(h));
+    int row, why;
+    THIP_RC(sg.check(h, count, 1, &row, &why));
+    if (row >= 0) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "problem %d: %s", first + row, why == 1 ? "a start's tau is finite and not negative"
+                                                                             : "a start's kappa is finite and not positive");
+        return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+    }
+    THIP_RC(ob_dev_copy(reinterpret_cast<const ObDevRow *>(sg.rows_dev()) + cnt, 2 * cnt, most));
+    const unsigned char *const dev_head = sg.dev + sg.at_head();
+    return ob_dev_finish(h, first, count, [&]() { return launch(dev_head, to); });
+}
+
+int ob_set_iterates_dev(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_x, const float *dev_y)
+{
+    const long long per = h ? (long long)(2 * h->n + 3 * h->m + 2) : 0;
+    return ob_set_iterates_dev_t(f, h, first, count, dev_x, dev_y, [&](int, size_t *n, size_t *m) { *n = h->n; *m = h->m; }, 0,
+                                 [](unsigned char *, const std::vector<long long> &) {},
+                                 [&](const unsigned char *, const float *staged) {
+                                     ObArgs a = ob_args(h);
+                                     a.first = first;
+                                     return f.start(h, a, ObStart{ staged, nullptr, per }, (unsigned)count);
+                                 });
+}
+
+// thip_NAME_set_bc_dev.  store(): the handle's b / c store is there (the host twin's rule).  ownbatch_stage_bc_k builds each problem's
+// staged part -- the word, b, c, the row sums -- from the three device arrays; the set_bc kernels run unchanged on it
+template <class SHAPE, class STORE, class FILL, class LAUNCH>
+int ob_set_bc_dev_t(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_r,
+                    const uint8_t *host_has, const SHAPE &shape, const STORE &store, size_t head, const FILL &fill, const LAUNCH &launch)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    if (!dev_b || !dev_c) return fail(THIP_E_INVALID, "null b or c", __FILE__, __LINE__);
+    const size_t cnt = (size_t)count;
+    std::vector<long long> at_p(cnt);
+    size_t floats = 0, sum_n = 0, sum_m = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+        size_t n, m;
+        shape(first + (int)k, &n, &m);
+        long long len[OB_DEV_KINDS];
+        ob_dev_lengths(n, m, len);
+        at_p[k] = (long long)floats;
+        floats += (size_t)(1 + 2 * len[1] + len[0]); sum_n += (size_t)len[0]; sum_m += (size_t)len[1];
+    }
+    THIP_RC(ob_dev_foreign(h, dev_b, sum_m * sizeof(float), "dev_b"));
+    THIP_RC(ob_dev_foreign(h, dev_c, sum_n * sizeof(float), "dev_c"));
+    THIP_RC(ob_dev_foreign(h, dev_r, sum_m * sizeof(float), "dev_b_rowabs"));
+    THIP_RC(store());
+    ObDevStage sg;
+    sg.tables = cnt * sizeof(ObBcRow); sg.head = head; sg.floats = floats * sizeof(float);
+    THIP_RC(sg.reserve(h));
+    ObBcRow *rows = reinterpret_cast<ObBcRow *>(sg.rows());
+    float *const to = reinterpret_cast<float *>(sg.dev + sg.at_floats());
+    {
+        const float *b = dev_b, *c = dev_c, *r = dev_r;
+        for (size_t k = 0; k < cnt; ++k) {
+            size_t n, m;
+            shape(first + (int)k, &n, &m);
+            const bool has = dev_r && (!host_has || host_has[k]);
+            rows[k] = ObBcRow{ b, c, has ? r : nullptr, to + at_p[k], (int)n, (int)m };
+            b += m; c += n;
+            if (r) r += m;
+        }
+    }
+    fill(sg.pin + sg.at_head(), at_p);
+    THIP_RC(sg.upload(h));
+    hipLaunchKernelGGL(ownbatch_stage_bc_k, dim3((unsigned)count), dim3(256), 0, ctx().stream,
+                       reinterpret_cast<const ObBcRow *>(sg.rows_dev()));
+    THIP_LAUNCH_CHECK();
+    const unsigned char *const dev_head = sg.dev + sg.at_head();
+    return ob_dev_finish(h, first, count, [&]() { return launch(dev_head, to); });
+}
+
+int ob_set_bc_dev(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_r,
+                  const uint8_t *host_has, int keep)
+{
+    return ob_set_bc_dev_t(f, h, first, count, dev_b, dev_c, dev_r, host_has, [&](int, size_t *n, size_t *m) { *n = h->n; *m = h->m; },
+                           [&]() { return ob_setbc_store(h, (2 * h->m + h->n) * h->n_prob, nullptr); }, 0,
+                           [](unsigned char *, const std::vector<long long> &) {},
+                           [&](const unsigned char *, const float *staged) {
+                               ObArgs a = ob_args(h);
+                               a.first = first;
+                               const ObSetBc s{ ObStart{ staged, nullptr, (long long)(1 + 2 * h->m + h->n) }, h->bc_store, nullptr,
+                                                (long long)(2 * h->m + h->n), keep != 0 };
+                               return f.setbc(h, a, s, (unsigned)count);
+                           });
+}
+
+// thip_NAME_solutions_dev: one launch, nothing comes down and nothing is waited for.  table: a handle of many shapes, whose table
+// of every problem goes up once, with the first call (block(p): where problem p's block of the arena begins, in floats)
+template <class SHAPE, class BLOCK>
+int ob_solutions_dev_t(const ObFamily &f, OwnBatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state, bool table,
+                       const SHAPE &shape, const BLOCK &block)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    size_t x0 = 0, y0 = 0, sum_n = 0, sum_m = 0;
+    for (size_t p = 0; p < (size_t)first + (size_t)count; ++p) {
+        size_t n, m;
+        shape((int)p, &n, &m);
+        if (p < (size_t)first) { x0 += n; y0 += m; } else { sum_n += n; sum_m += m; }
+    }
+    THIP_RC(ob_dev_foreign(h, dev_x, sum_n * sizeof(float), "dev_x"));
+    THIP_RC(ob_dev_foreign(h, dev_y, sum_m * sizeof(float), "dev_y"));
+    THIP_RC(ob_dev_foreign(h, dev_state, (size_t)count * sizeof(int32_t), "dev_state"));
+    if (!dev_x && !dev_y && !dev_state) return 0;
+    if (table && !h->sol_at_dev) {
+        std::vector<long long> at(5 * h->n_prob);
+        size_t ox = 0, oy = 0;
+        for (size_t p = 0; p < h->n_prob; ++p) {
+            size_t n, m;
+            shape((int)p, &n, &m);
+            at[5 * p] = block((int)p); at[5 * p + 1] = (long long)n; at[5 * p + 2] = (long long)m;
+            at[5 * p + 3] = (long long)ox; at[5 * p + 4] = (long long)oy;
+            ox += n; oy += m;
+        }
+        long long *dev = nullptr;
+        THIP_RC(ob_alloc(h, (void **)&dev, at.size() * sizeof(long long)));
+        h->sol_at_dev = dev;
+        THIP_TRY(hipMemcpy(dev, at.data(), at.size() * sizeof(long long), hipMemcpyHostToDevice));
+        h->last_h2d += at.size() * sizeof(long long);
+    }
+    const ObGatherDev g{ h->arena, h->dst, table ? h->sol_at_dev : nullptr, h->stride, (int)h->n, (int)h->m, first, (long long)x0,
+                         (long long)y0, dev_x, dev_y, dev_state };
+    hipLaunchKernelGGL(ownbatch_gather_final_k, dim3((unsigned)count), dim3(256), 0, ctx().stream, g);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int ob_solutions_dev(const ObFamily &f, OwnBatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)
+{
+    return ob_solutions_dev_t(f, h, first, count, dev_x, dev_y, dev_state, false, [&](int, size_t *n, size_t *m) { *n = h->n; *m = h->m; },
+                              [](int) { return 0ll; });
+}
+
 // the shape rules alone: the family's check (which fills *cones, *cls and *psd when they are given), its thread choice and the LDS of
 // one workgroup
 int ob_fits(const ObFamily &f, size_t n, size_t m, size_t n_seg, const int32_t *seg_type, const int64_t *seg_len, size_t *host_lds_bytes,
@@ -1181,6 +1704,59 @@ int ob_force_threads(const ObFamily &f, OwnBatch *h, int threads)
     int thip_##NAME##_set_a(thip_##NAME *h, int first, int count, const float *host_values, const int64_t *host_counts,             \
                             int keep_iterate)                                                                                       \
     { return ob_set_a(FAM, h, first, count, host_values, host_counts, keep_iterate); }                                              \
+    int thip_##NAME##_set_bc_dev(thip_##NAME *h, int first, int count, const float *dev_b, const float *dev_c,                      \
+                                 const float *dev_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate)                       \
+    { return ob_set_bc_dev(FAM, h, first, count, dev_b, dev_c, dev_b_rowabs, host_has_rowabs, keep_iterate); }                      \
+    int thip_##NAME##_set_a_dev(thip_##NAME *h, int first, int count, const float *dev_values, int keep_iterate)                    \
+    { return ob_set_a_dev(FAM, h, first, count, dev_values, keep_iterate); }                                                        \
+    int thip_##NAME##_set_iterates_dev(thip_##NAME *h, int first, int count, const float *dev_x, const float *dev_y)                \
+    { return ob_set_iterates_dev(FAM, h, first, count, dev_x, dev_y); }                                                             \
+    int thip_##NAME##_solutions_dev(thip_##NAME *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)           \
+    { return ob_solutions_dev(FAM, h, first, count, dev_x, dev_y, dev_state); }                                                     \
     int thip_##NAME##_info(const thip_##NAME *h, thip_##NAME##_info_t *host_info) { return ob_info_out(h, host_info, FILL()); }       \
     int thip_test_##NAME##_force_threads(thip_##NAME *h, int threads) { return ob_force_threads(FAM, h, threads); }                 \
     }
+
+// the test hooks every family shares (include/totsu_f32hip_test.h), defined by the one translation unit that asks for them.  h: a
+// handle of any own-A family -- each is an OwnBatch first, and every translation unit compiles this header's one definition of it
+#ifdef OB_DEFINE_HOOKS
+extern "C" {
+int thip_test_ownbatch_addresses(void *h, uint64_t *host_addr, uint64_t *host_bytes)
+{
+    const OwnBatch *b = static_cast<const OwnBatch *>(h);
+    if (!b || !host_addr || !host_bytes) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    const void *const what[3] = { b->arena, b->stage, b->bc_store };
+    for (int k = 0; k < 3; ++k) {
+        host_addr[k] = (uint64_t)(uintptr_t)what[k];
+        host_bytes[k] = 0;
+        for (const auto &o : b->owned)
+            if (what[k] && o.first == (uintptr_t)what[k]) host_bytes[k] = o.second;
+    }
+    return 0;
+}
+int thip_test_ownbatch_last_transfer(void *h, uint64_t *host_h2d_bytes, uint64_t *host_d2h_bytes)
+{
+    const OwnBatch *b = static_cast<const OwnBatch *>(h);
+    if (!b || !host_h2d_bytes || !host_d2h_bytes) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    *host_h2d_bytes = b->last_h2d; *host_d2h_bytes = b->last_d2h;
+    return 0;
+}
+int thip_test_ownbatch_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)
+{
+    return ob_overlap((uintptr_t)a, (size_t)a_bytes, (uintptr_t)b, (size_t)b_bytes) ? 1 : 0;
+}
+int thip_test_ownbatch_offsets(size_t count, const size_t *host_n, const size_t *host_m, int64_t *host_at)
+{
+    if (!host_n || !host_m || !host_at) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
+    long long sum[OB_DEV_KINDS] = { 0, 0, 0, 0, 0 }, len[OB_DEV_KINDS];
+    for (size_t k = 0; k <= count; ++k) {
+        for (int q = 0; q < OB_DEV_KINDS; ++q) host_at[(size_t)q * (count + 1) + k] = sum[q];
+        if (k == count) break;
+        ob_dev_lengths(host_n[k], host_m[k], len);
+        for (int q = 0; q < OB_DEV_KINDS; ++q) sum[q] += len[q];
+    }
+    return 0;
+}
+int thip_test_ownbatch_copy_chunk(void) { return OB_COPY_CHUNK; }
+}
+#endif

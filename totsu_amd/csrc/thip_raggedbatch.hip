@@ -432,6 +432,19 @@ int thip_raggedbatch_solutions(thip_raggedbatch *h, int first, int count, float 
 int thip_raggedbatch_set_a(thip_raggedbatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate)
 { return rg_set_a_dense(RB_FAMILY, h, first, count, host_values, host_counts, keep_iterate); }
 
+int thip_raggedbatch_set_bc_dev(thip_raggedbatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+                                const uint8_t *host_has_rowabs, int keep_iterate)
+{ return rg_set_bc_dev(RB_FAMILY, h, first, count, dev_b, dev_c, dev_b_rowabs, host_has_rowabs, keep_iterate); }
+
+int thip_raggedbatch_set_a_dev(thip_raggedbatch *h, int first, int count, const float *dev_values, int keep_iterate)
+{ return rg_set_a_dev_dense(RB_FAMILY, h, first, count, dev_values, keep_iterate); }
+
+int thip_raggedbatch_set_iterates_dev(thip_raggedbatch *h, int first, int count, const float *dev_x, const float *dev_y)
+{ return rg_set_iterates_dev(RB_FAMILY, h, first, count, dev_x, dev_y); }
+
+int thip_raggedbatch_solutions_dev(thip_raggedbatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)
+{ return rg_solutions_dev(RB_FAMILY, h, first, count, dev_x, dev_y, dev_state); }
+
 int thip_raggedbatch_info(const thip_raggedbatch *h, thip_raggedbatch_info_t *host_info) { return rb_info(h, host_info); }
 int thip_raggedbatch_destroy(thip_raggedbatch *h) { return rb_destroy(h); }
 

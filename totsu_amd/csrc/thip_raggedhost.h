@@ -287,6 +287,121 @@ int rg_set_a_sparse(const ObFamily &f, H *h, int first, int count, const float *
     });
 }
 
+// ---- the round calls on device memory (thip_ownbatch.h) of a handle that launches by class -----------------------------------------
+
+// the head of a range's staged layout, as the host calls above build it: where each workgroup's part lies, then the classes' lists
+size_t rg_head_bytes(size_t cnt) { return cnt * sizeof(long long) + ((cnt + 1) & ~(size_t)1) * sizeof(int); }
+
+// that head into pinned memory (at_p[k]: where problem first + k's part begins), and the classes' members of the range
+template <class H>
+void rg_head_fill(const H *h, int first, int count, const std::vector<long long> &at_p, unsigned char *pin, std::vector<int> *members)
+{
+    long long *const at = reinterpret_cast<long long *>(pin);
+    int *const list = reinterpret_cast<int *>(pin + (size_t)count * sizeof(long long));
+    members[0].clear(); members[1].clear();
+    rg_members(h, first, count, members);
+    size_t k = 0;
+    for (int c = 0; c < 2; ++c)
+        for (int p : members[c]) { list[k] = p; at[k] = at_p[(size_t)(p - first)]; ++k; }
+}
+
+// fn(c, the class's count, its list, its places) for each class with a member in the range, from the head on the device
+template <class FN>
+int rg_by_class(const std::vector<int> *members, size_t cnt, const unsigned char *dev_head, const FN &fn)
+{
+    size_t k = 0;
+    for (int c = 0; c < 2; ++c) {
+        if (members[c].empty()) continue;
+        THIP_RC(fn(c, (unsigned)members[c].size(), reinterpret_cast<const int *>(dev_head + cnt * sizeof(long long)) + k,
+                   reinterpret_cast<const long long *>(dev_head) + k));
+        k += members[c].size();
+    }
+    return 0;
+}
+
+template <class H>
+int rg_set_iterates_dev(const ObFamily &f, H *h, int first, int count, const float *dev_x, const float *dev_y)
+{
+    std::vector<int> members[2];
+    const size_t cnt = count > 0 ? (size_t)count : 0;
+    return ob_set_iterates_dev_t(f, h, first, count, dev_x, dev_y,
+                                 [&](int p, size_t *n, size_t *m) { *n = h->pl.prob[(size_t)p].n; *m = h->pl.prob[(size_t)p].m; },
+                                 rg_head_bytes(cnt),
+                                 [&](unsigned char *pin, const std::vector<long long> &at_p) { rg_head_fill(h, first, count, at_p, pin, members); },
+                                 [&](const unsigned char *dev_head, const float *staged) {
+                                     return rg_by_class(members, cnt, dev_head, [&](int c, unsigned n_c, const int *list, const long long *at) {
+                                         return rg_start(h, c, n_c, list, ObStart{ staged, at, 0 });
+                                     });
+                                 });
+}
+
+template <class H>
+int rg_set_bc_dev(const ObFamily &f, H *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_r,
+                  const uint8_t *host_has, int keep)
+{
+    std::vector<int> members[2];
+    const size_t cnt = count > 0 ? (size_t)count : 0;
+    return ob_set_bc_dev_t(f, h, first, count, dev_b, dev_c, dev_r, host_has,
+                           [&](int p, size_t *n, size_t *m) { *n = h->pl.prob[(size_t)p].n; *m = h->pl.prob[(size_t)p].m; },
+                           [&]() -> int {
+                               if (h->bc_store) return 0;
+                               std::vector<long long> store_at(h->n_prob);
+                               size_t total = 0;
+                               for (size_t p = 0; p < h->n_prob; ++p) { store_at[p] = (long long)total; total += 2 * h->pl.prob[p].m + h->pl.prob[p].n; }
+                               return ob_setbc_store(h, total, &store_at);
+                           },
+                           rg_head_bytes(cnt),
+                           [&](unsigned char *pin, const std::vector<long long> &at_p) { rg_head_fill(h, first, count, at_p, pin, members); },
+                           [&](const unsigned char *dev_head, const float *staged) {
+                               return rg_by_class(members, cnt, dev_head, [&](int c, unsigned n_c, const int *list, const long long *at) {
+                                   return rg_setbc(h, c, n_c, list, ObSetBc{ ObStart{ staged, at, 0 }, h->bc_store, h->bc_at_dev, 0, keep != 0 });
+                               });
+                           });
+}
+
+// (dense: the classes' lists go into live_dev as a run's do, and the host twin's)
+template <class H>
+int rg_set_a_dev_dense(const ObFamily &f, H *h, int first, int count, const float *dev_values, int keep)
+{
+    std::vector<int> members[2], list;                          // (list: read by its copy until ob_restarted synchronises)
+    return ob_set_a_dev_dense_t(f, h, first, count, dev_values,
+                                [&](int p) { return h->pl.prob[(size_t)p].m * h->pl.prob[(size_t)p].n; }, [&]() -> int {
+        rg_members(h, first, count, members);
+        for (int c = 0; c < 2; ++c) list.insert(list.end(), members[c].begin(), members[c].end());
+        THIP_TRY(hipMemcpyAsync(h->live_dev, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream));
+        h->last_h2d += list.size() * sizeof(int);
+        size_t k = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (members[c].empty()) continue;
+            THIP_RC(rg_seta(h, c, (unsigned)members[c].size(), h->live_dev + k, ObSetA{ ObStart{ nullptr, nullptr, 0 }, keep != 0 }));
+            k += members[c].size();
+        }
+        return 0;
+    });
+}
+
+template <class H, class NEED>
+int rg_set_a_dev_sparse(const ObFamily &f, H *h, int first, int count, const float *dev_values, int keep, const NEED &need)
+{
+    std::vector<int> members[2];
+    const size_t cnt = count > 0 ? (size_t)count : 0;
+    return ob_set_a_dev_sparse_t(f, h, first, count, dev_values, need, rg_head_bytes(cnt),
+                                 [&](unsigned char *pin, const std::vector<long long> &at_p) { rg_head_fill(h, first, count, at_p, pin, members); },
+                                 [&](const unsigned char *dev_head) {
+                                     return rg_by_class(members, cnt, dev_head, [&](int c, unsigned n_c, const int *list, const long long *at) {
+                                         return rg_seta(h, c, n_c, list, ObSetA{ ObStart{ dev_values, at, 0 }, keep != 0 });
+                                     });
+                                 });
+}
+
+template <class H>
+int rg_solutions_dev(const ObFamily &f, H *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)
+{
+    return ob_solutions_dev_t(f, h, first, count, dev_x, dev_y, dev_state, true,
+                              [&](int p, size_t *n, size_t *m) { *n = h->pl.prob[(size_t)p].n; *m = h->pl.prob[(size_t)p].m; },
+                              [&](int p) { return (long long)h->pl.desc[(size_t)p].arena_at; });
+}
+
 // thip_NAME_solutions of a handle of many shapes: the gather kernel by a table of the range's blocks, shapes and places
 template <class H>
 int rg_solutions(const ObFamily &f, H *h, int first, int count, float *host_x, float *host_y, thip_status *host_status)

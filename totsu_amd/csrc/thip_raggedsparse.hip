@@ -580,6 +580,22 @@ int thip_raggedsparse_set_a(thip_raggedsparse *h, int first, int count, const fl
                            [&](int p) { return h->pl.prob[(size_t)p].nnz; });
 }
 
+int thip_raggedsparse_set_bc_dev(thip_raggedsparse *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+                                 const uint8_t *host_has_rowabs, int keep_iterate)
+{ return rg_set_bc_dev(RS_FAMILY, h, first, count, dev_b, dev_c, dev_b_rowabs, host_has_rowabs, keep_iterate); }
+
+// (the values stay where the caller holds them: the scatter kernels read them there, by a table of the host's counts)
+int thip_raggedsparse_set_a_dev(thip_raggedsparse *h, int first, int count, const float *dev_values, int keep_iterate)
+{
+    return rg_set_a_dev_sparse(RS_FAMILY, h, first, count, dev_values, keep_iterate, [&](int p) { return h->pl.prob[(size_t)p].nnz; });
+}
+
+int thip_raggedsparse_set_iterates_dev(thip_raggedsparse *h, int first, int count, const float *dev_x, const float *dev_y)
+{ return rg_set_iterates_dev(RS_FAMILY, h, first, count, dev_x, dev_y); }
+
+int thip_raggedsparse_solutions_dev(thip_raggedsparse *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)
+{ return rg_solutions_dev(RS_FAMILY, h, first, count, dev_x, dev_y, dev_state); }
+
 int thip_raggedsparse_info(const thip_raggedsparse *h, thip_raggedsparse_info_t *host_info) { return rs_info(h, host_info); }
 int thip_raggedsparse_destroy(thip_raggedsparse *h) { return rs_destroy(h); }
 

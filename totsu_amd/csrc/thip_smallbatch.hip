@@ -17,6 +17,7 @@
 // This file: the LDS map, the products from LDS, the two kernels, the shape rule (sb_check), the thread choice and the family's
 // table.  The launch arguments, the status block, the slots, the init kernel's body, the criteria and status_eval, and the whole
 // host side behind the C API are shared with the streamed batches (thip_midbatch.hip, thip_sdpbatch.hip): thip_ownbatch.h.
+#define OB_DEFINE_HOOKS 1      // (thip_test_ownbatch_*: this translation unit defines them)
 #include "thip_ownbatch.h"
 
 using namespace thip;

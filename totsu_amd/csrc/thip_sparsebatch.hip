@@ -302,6 +302,29 @@ int thip_sparsebatch_set_a(thip_sparsebatch *h, int first, int count, const floa
     });
 }
 
+int thip_sparsebatch_set_bc_dev(thip_sparsebatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+                                const uint8_t *host_has_rowabs, int keep_iterate)
+{ return ob_set_bc_dev(SPB_FAMILY, h, first, count, dev_b, dev_c, dev_b_rowabs, host_has_rowabs, keep_iterate); }
+int thip_sparsebatch_set_iterates_dev(thip_sparsebatch *h, int first, int count, const float *dev_x, const float *dev_y)
+{ return ob_set_iterates_dev(SPB_FAMILY, h, first, count, dev_x, dev_y); }
+int thip_sparsebatch_solutions_dev(thip_sparsebatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state)
+{ return ob_solutions_dev(SPB_FAMILY, h, first, count, dev_x, dev_y, dev_state); }
+
+// the values stay where the caller holds them: only the table of where each workgroup's begin goes up, and the scatter reads them there
+int thip_sparsebatch_set_a_dev(thip_sparsebatch *h, int first, int count, const float *dev_values, int keep_iterate)
+{
+    const size_t cnt = count > 0 ? (size_t)count : 0;
+    return ob_set_a_dev_sparse_t(SPB_FAMILY, h, first, count, dev_values, [&](int p) { return (size_t)h->slot_nnz[(size_t)p]; },
+                                 cnt * sizeof(long long),
+                                 [&](unsigned char *pin, const std::vector<long long> &at_p) { memcpy(pin, at_p.data(), cnt * sizeof(long long)); },
+                                 [&](const unsigned char *dev_head) {
+                                     ObArgs a = ob_args(h);
+                                     a.first = first;
+                                     const ObSetA s{ ObStart{ dev_values, reinterpret_cast<const long long *>(dev_head), 0 }, keep_iterate != 0 };
+                                     return SPB_FAMILY.seta(h, a, s, (unsigned)count);
+                                 });
+}
+
 int thip_sparsebatch_replace(thip_sparsebatch *h, int i, const int64_t *host_colptr, const int32_t *host_rowidx, const float *host_values,
                              const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
 {

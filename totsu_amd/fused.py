@@ -39,6 +39,14 @@ class DeviceBuffer:
             lib.thip_d2h(out.ctypes.data, self.ptr, self.n)
         return out
 
+    @property
+    def __cuda_array_interface__(self):
+        """the buffer as a one-dimensional float32 array on the device: torch.as_tensor(buf, device="cuda") is a view of it (the
+        buffer has to outlive the view)"""
+        if self.ptr is None:
+            raise AttributeError("the DeviceBuffer has been freed")
+        return {"shape": (self.n,), "typestr": "<f4", "data": (int(self.ptr) if self.n else 0, False), "version": 2, "strides": None}
+
     def free(self):
         if self.ptr is not None:
             lib.thip_free(self.ptr)

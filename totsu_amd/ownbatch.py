@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, devmem
 from ._lib import lib
 from .fused import DeviceBuffer, FusedResult, _c_param, _checked, _raw, _start_scalars
 from .solver import SolverError, SolverParam
@@ -369,6 +369,99 @@ class OwnBatchSolver:
         st = (_lib.Status * count)()
         _checked(self._c("solutions"), self.h, first, count, None, None, st)
         return [FusedResult(s) for s in st]
+
+    # ---- the round calls on device memory: the four above for a caller whose round lives on the GPU ------------------------------
+
+    def _dev_arg(self, obj, what, want, torch_seen, out=False, typestr="<f4"):
+        """the address of the device array `obj`, which holds at least `want` elements (ValueError before the call says what was needed)"""
+        ptr, got = devmem.as_device(obj, what, out=out, typestr=typestr)
+        if got < want:
+            raise ValueError("%s: %d entries where %d are needed (the problems' parts one after another, each in its own length)"
+                             % (what, got, want))
+        if devmem.is_torch(obj):
+            torch_seen.append(obj)
+        return ptr
+
+    @staticmethod
+    def _torch_ordered(torch_seen):
+        """a torch tensor's producer ran on torch's current stream and the library runs on its own: that stream first"""
+        if torch_seen:
+            import torch
+            torch.cuda.current_stream(torch_seen[0].device).synchronize()
+
+    def _sums(self, first, count):
+        """the lengths of the range's packed arrays: (c / solution x, b / solution y, iterate x, iterate y) summed over its problems"""
+        sn = sm = sx = sy = 0
+        for k in range(count):
+            n, m = self._nm(first + k)
+            nx, ny = self._lengths(first + k)
+            sn, sm, sx, sy = sn + n, sm + m, sx + nx, sy + ny
+        return sn, sm, sx, sy
+
+    def set_bc_dev(self, b, c, b_rowabs=None, first=0, count=None, keep_iterate=False):
+        """set_bc with the new data taken from DEVICE memory -- a DeviceBuffer, a torch tensor on the GPU, anything with
+        __cuda_array_interface__: float32, the problems' b one after another (each its own m), c likewise (n), b_rowabs m per
+        problem or None.  The range is left bit for bit as set_bc leaves it when handed the same floats; nothing but a table of a
+        few dozen bytes per problem goes up.  ValueError: as set_bc, and an array that is too short, of another dtype, not
+        contiguous, on the host, or overlapping memory the batch owns."""
+        first, count = self._range(first, count)
+        sn, sm, _, _ = self._sums(first, count)
+        seen = []
+        pb, pc = self._dev_arg(b, "set_bc_dev: b", sm, seen), self._dev_arg(c, "set_bc_dev: c", sn, seen)
+        pr = None if b_rowabs is None else self._dev_arg(b_rowabs, "set_bc_dev: b_rowabs", sm, seen)
+        self._torch_ordered(seen)
+        _checked(self._c("set_bc_dev"), self.h, first, count, pb, pc, pr, None, 1 if keep_iterate else 0)
+
+    def set_a_dev(self, values=None, first=0, count=None, keep_iterate=False):
+        """set_a with the new values taken from DEVICE memory: the problems' values one after another -- m n floats each,
+        column-major, in a dense family (copied device to device into the memory the slots read, in place); the entries in the CSC
+        order of each slot's present pattern in a sparse one (read where they lie).  values=None, a dense family only: the caller
+        has ALREADY rewritten A in the buffer the batch was built over, nothing is copied and the batch initialises again from
+        what lies there -- the zero-copy form; a `values` that overlaps that buffer is refused (write None).  Bit for bit what
+        set_a does with the same floats.  ValueError, the batch unchanged: a value that is not finite (found by a kernel before
+        anything is touched; the message names the problem), an array that is too short, of another dtype, not contiguous, on the
+        host, or overlapping memory the batch owns."""
+        first, count = self._range(first, count)
+        seen = []
+        pv = None
+        if values is not None:
+            pv = self._dev_arg(values, "set_a_dev: values", sum(int(self._a_size(first + k)) for k in range(count)), seen)
+        self._torch_ordered(seen)
+        _checked(self._c("set_a_dev"), self.h, first, count, pv, 1 if keep_iterate else 0)
+
+    def set_iterates_dev(self, x, y, first=0, count=None):
+        """set_iterates with the iterates taken from DEVICE memory: x the problems' (x_x x_y x_s tau) one after another, y their
+        (u v kappa), in the lengths iterate() returns.  Bit for bit what set_iterates does with the same floats.  ValueError, the
+        batch unchanged: a tau that is negative or not finite, a kappa that is positive or not finite (found by a kernel; the
+        message names the problem), and what set_bc_dev refuses of an array."""
+        first, count = self._range(first, count)
+        _, _, sx, sy = self._sums(first, count)
+        seen = []
+        px, py = self._dev_arg(x, "set_iterates_dev: x", sx, seen), self._dev_arg(y, "set_iterates_dev: y", sy, seen)
+        self._torch_ordered(seen)
+        _checked(self._c("set_iterates_dev"), self.h, first, count, px, py)
+
+    def solutions_dev(self, first=0, count=None, out_x=None, out_y=None, out_state=None, sync=True):
+        """solutions() left ON THE DEVICE: (x, y, state) -- the problems' x one after another (each its own n), their y (m), and one
+        int32 state code per problem -- bit for bit what solutions() and statuses() return, the final 1/tau scaling applied by the
+        kernel.  out_x / out_y / out_state: where to write (float32, float32, int32 device arrays, or a DeviceBuffer for any; long
+        enough), else freshly allocated DeviceBuffers (the state's 4-byte words are int32: to_host().view(numpy.int32)).  Nothing
+        comes to the host.  sync=True waits for the library's stream before returning; sync=False returns after the launch, and
+        the caller orders its readers behind that stream."""
+        first, count = self._range(first, count)
+        sn, sm, _, _ = self._sums(first, count)
+        seen = []
+        x = DeviceBuffer(sn) if out_x is None else out_x
+        y = DeviceBuffer(sm) if out_y is None else out_y
+        st = DeviceBuffer(count) if out_state is None else out_state
+        px = self._dev_arg(x, "solutions_dev: out_x", sn, seen, out=True)
+        py = self._dev_arg(y, "solutions_dev: out_y", sm, seen, out=True)
+        ps = self._dev_arg(st, "solutions_dev: out_state", count, seen, out=True, typestr="<i4")
+        self._torch_ordered(seen)
+        _checked(self._c("solutions_dev"), self.h, first, count, px, py, ps)
+        if sync:
+            lib.thip_sync()
+        return x, y, st
 
     def raw_iterate(self, i):
         """iterate(i) with the read-out's final scaling undone: a problem that stopped with kind 0 in state OK / ExcessIter has its

@@ -125,7 +125,7 @@ def pack(problems, kinds=_KINDS):
 
 
 class RaggedBatchSolver(OwnBatchSolver):
-    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / set_a / solutions / statuses / precond /
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / set_a / solutions / the _dev round calls / statuses / precond /
     replace / reinit / set_param / info / solve / destroy of OwnBatchSolver, on thip_raggedbatch_*, with every length the problem's own.  `shapes`: [(n_p, m_p)].  force_threads: test hook
     (256, 1024: every problem in that one class)."""
     _prefix, _force_hook, _what = "thip_raggedbatch_", "thip_test_raggedbatch_force_threads", "ragged"

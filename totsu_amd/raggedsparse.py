@@ -135,7 +135,7 @@ def plan(problems, nnz_caps=None, force_threads=None, force_resident=None):
 
 
 class RaggedSparseBatchSolver(SparseSetA, RaggedBatchSolver):
-    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / set_a / solutions / precond / replace /
+    """run / run_until_any / status / solution / iterate / raw_iterate / set_iterate(s) / set_bc / set_a / solutions / the _dev round calls / precond / replace /
     reinit / set_param / info / solve / destroy of OwnBatchSolver, on thip_raggedsparse_*, with every length the problem's own.  `shapes`: [(n_p, m_p)]; `nnz_caps`: the entries
     each slot can take.  force_threads (256, 1024: every problem in that one class) and force_resident (0: nobody resident, 1:
     everybody who fits) are test hooks.

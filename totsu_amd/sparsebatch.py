@@ -150,7 +150,7 @@ class SparseSetA:
 
 
 class SparseBatchSolver(SparseSetA, OwnBatchSolver):
-    """run / run_until_any / status / solution / iterate / precond / set_iterate(s) / set_bc / set_a / solutions / reinit / set_param /
+    """run / run_until_any / status / solution / iterate / precond / set_iterate(s) / set_bc / set_a / solutions / the _dev round calls / reinit / set_param /
     info / solve / destroy of OwnBatchSolver, on thip_sparsebatch_*.  force_threads (256, 1024) and force_resident (0: read the entries from memory, 1: from LDS) are test
     hooks.  info() adds nnz_cap, nnz_total, blob_bytes, resident and the PSD fields of the SDP batch; a_bytes_per_iter is 0 when
     resident."""
