@@ -766,6 +766,69 @@ int thip_midbatch_info(const thip_midbatch *h, thip_midbatch_info_t *host_info);
 int thip_midbatch_destroy(thip_midbatch *h);
 
 /* ---------------------------------------------------------------------------------------------
+ * The mid batch over a LIBRARY-OWNED 16-BIT COPY of every problem's A (thip_mid16batch.hip): thip_midbatch's shapes
+ * (thip_mid16batch_fits is thip_midbatch_fits), cones, iteration and interface, half the bytes of A per pass and half the memory.
+ * The stored form is a property of the handle, fixed at create: a_kind = THIP_A_BF16 or THIP_A_F16 (thip_mid16batch_create: f16);
+ * THIP_A_F32 is refused -- that is thip_midbatch.  dev_mats_a is the f32 stack thip_midbatch_create takes; it is converted by one
+ * launch and NOT referenced after create returns.  replace / set_a / set_a_dev take f32 values and convert them into the slot's
+ * block; set_a_dev(NULL), the in-place form, is refused: no f32 A lies in place.
+ * The store, per problem: n columns of ld16 = roundup4(m) 16-bit words, column-major, the pad rows zero; THIP_A_F16: n floats inv_s
+ * behind the matrix; the block padded to a multiple of 16 bytes.  bf16: the f32 rounded to nearest even to its upper 16 bits.
+ * f16: inv_s[c] = 2^(e - 14), e the exponent frexp gives the column's largest finite |a| (1 for a column of zeros), and the word
+ * f16(a / inv_s[c]), round to nearest even (the roundings of thip_solver_set_a_dtype).
+ * The contract: with W the WIDENED matrix -- W(r, c) the bf16 word shifted left 16 bits, or float(h(r, c)) * inv_s[c] in f32 -- the
+ * batch is BIT FOR BIT a thip_midbatch created over W in f32: preconditioner, iterates, compensation terms, status blocks and
+ * verdicts, at every workgroup size, in both state arithmetics, however the iterations are cut into launches.  The problem solved
+ * is the one with the rounded matrix; its end iterate is a start (thip_midbatch_set_iterates) for the exact one.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_mid16batch thip_mid16batch;
+typedef struct thip_mid16batch_info_t {
+    int32_t n_prob, threads;          /* as thip_midbatch_info_t ... */
+    int32_t lds_bytes, live;
+    size_t  arena_bytes;
+    size_t  device_bytes;             /* everything this object allocated on the device, the store included */
+    size_t  device_bytes_all;
+    int64_t launches, workgroups;
+    int32_t load_bytes, a_dtype;      /* 8 for every shape: a lane's 4 rows of a column are one load; THIP_A_BF16 / THIP_A_F16 */
+    size_t  a_bytes_per_iter;         /* bytes of the store read per problem-iteration: 2 (2 ld16 n + (f16: 4 n)) */
+    size_t  a_store_bytes;            /* the store: n_prob blocks */
+} thip_mid16batch_info_t;
+int thip_mid16batch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                         size_t *host_lds_bytes, int *host_threads);
+/* the bytes of one problem's block of the store (needs no device) */
+int thip_mid16batch_store_bytes(size_t n, size_t m, int a_kind, size_t *host_bytes);
+int thip_mid16batch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                           const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                           const int64_t *host_seg_len, const thip_param *par, thip_mid16batch **out);
+int thip_mid16batch_create_kind(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                                const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                                const int64_t *host_seg_len, const thip_param *par, int a_kind, thip_mid16batch **out);
+int thip_mid16batch_set_param(thip_mid16batch *h, const thip_param *par);
+int thip_mid16batch_init(thip_mid16batch *h);
+int thip_mid16batch_run(thip_mid16batch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_mid16batch_run_until_any(thip_mid16batch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_mid16batch_status(thip_mid16batch *h, int i, thip_status *host_status);
+int thip_mid16batch_solution(thip_mid16batch *h, int i, float *host_x, float *host_y);
+int thip_mid16batch_iterate(thip_mid16batch *h, int i, float *host_x, float *host_y);
+int thip_mid16batch_precond(thip_mid16batch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_mid16batch_replace(thip_mid16batch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                            const float *dev_vec_b_rowabs);
+int thip_mid16batch_set_iterates(thip_mid16batch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_mid16batch_set_bc(thip_mid16batch *h, int first, int count, const float *host_b, const float *host_c,
+                           const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_mid16batch_solutions(thip_mid16batch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_mid16batch_set_a(thip_mid16batch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_mid16batch_set_bc_dev(thip_mid16batch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_mid16batch_set_a_dev(thip_mid16batch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_mid16batch_set_iterates_dev(thip_mid16batch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_mid16batch_solutions_dev(thip_mid16batch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
+/* problem i's block as it lies in the store: n ld16 words, and (THIP_A_F16; else untouched) the n column scales.  Either may be NULL */
+int thip_mid16batch_stored(thip_mid16batch *h, int i, uint16_t *host_words, float *host_inv_scale);
+int thip_mid16batch_info(const thip_mid16batch *h, thip_mid16batch_info_t *host_info);
+int thip_mid16batch_destroy(thip_mid16batch *h);
+
+/* ---------------------------------------------------------------------------------------------
  * Many small SDPs (or mixed programs with PSD blocks), each with its own A: the mid batch's iteration with every PSD cone projected
  * on chip by the problem's own workgroup, between the two passes over A (thip_sdpbatch.hip).  The interface is
  * thip_midbatch's, one for one, and a layout without PSD segments gives thip_midbatch's iterates bit for bit.

@@ -238,6 +238,10 @@ int thip_test_smallbatch_force_threads(thip_smallbatch *h, int threads);
  * thip_midbatch_init. */
 int thip_test_midbatch_force_threads(thip_midbatch *h, int threads);
 
+/* TEST HOOK: the workgroup size of a mid16 batch (thip_mid16batch.hip): 256 or 1024 threads, 0 = by shape.  Before
+ * thip_mid16batch_init. */
+int thip_test_mid16batch_force_threads(thip_mid16batch *h, int threads);
+
 /* TEST HOOK: the workgroup size of an SDP batch (thip_sdpbatch.hip): 256 or 1024 threads, 0 = by shape.  Before
  * thip_sdpbatch_init. */
 int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads);

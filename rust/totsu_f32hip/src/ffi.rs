@@ -53,6 +53,16 @@ pub struct thip_midbatch_info_t {
 }
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
+pub struct thip_mid16batch_info_t {
+    pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub load_bytes: i32, pub a_dtype: i32,
+    pub a_bytes_per_iter: usize,
+    pub a_store_bytes: usize,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
 pub struct thip_sdpbatch_info_t {
     pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
     pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
@@ -165,6 +175,7 @@ pub enum thip_solver {}
 pub enum thip_batch {}
 pub enum thip_smallbatch {}
 pub enum thip_midbatch {}
+pub enum thip_mid16batch {}
 pub enum thip_sdpbatch {}
 pub enum thip_raggedbatch {}
 pub enum thip_sparsebatch {}
@@ -394,6 +405,38 @@ extern "C" {
     pub fn thip_midbatch_info(h: *const thip_midbatch, host_info: *mut thip_midbatch_info_t) -> c_int;
     pub fn thip_midbatch_destroy(h: *mut thip_midbatch) -> c_int;
     pub fn thip_test_midbatch_force_threads(h: *mut thip_midbatch, threads: c_int) -> c_int;
+    // the mid batch over a library-owned 16-bit copy of every A (thip_mid16batch.hip)
+    pub fn thip_mid16batch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                              host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;
+    pub fn thip_mid16batch_create(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                host_seg_len: *const i64, par: *const thip_param, out: *mut *mut thip_mid16batch) -> c_int;
+    pub fn thip_mid16batch_set_param(h: *mut thip_mid16batch, par: *const thip_param) -> c_int;
+    pub fn thip_mid16batch_init(h: *mut thip_mid16batch) -> c_int;
+    pub fn thip_mid16batch_run(h: *mut thip_mid16batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_mid16batch_run_until_any(h: *mut thip_mid16batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_mid16batch_status(h: *mut thip_mid16batch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_mid16batch_solution(h: *mut thip_mid16batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_mid16batch_iterate(h: *mut thip_mid16batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_mid16batch_precond(h: *mut thip_mid16batch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_mid16batch_replace(h: *mut thip_mid16batch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
+                                 dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_mid16batch_set_iterates(h: *mut thip_mid16batch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
+    pub fn thip_mid16batch_set_bc(h: *mut thip_mid16batch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_mid16batch_solutions(h: *mut thip_mid16batch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_mid16batch_set_a(h: *mut thip_mid16batch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_mid16batch_set_bc_dev(h: *mut thip_mid16batch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_mid16batch_set_a_dev(h: *mut thip_mid16batch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_mid16batch_set_iterates_dev(h: *mut thip_mid16batch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_mid16batch_solutions_dev(h: *mut thip_mid16batch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
+    pub fn thip_mid16batch_info(h: *const thip_mid16batch, host_info: *mut thip_mid16batch_info_t) -> c_int;
+    pub fn thip_mid16batch_destroy(h: *mut thip_mid16batch) -> c_int;
+    pub fn thip_test_mid16batch_force_threads(h: *mut thip_mid16batch, threads: c_int) -> c_int;
+    pub fn thip_mid16batch_create_kind(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                       dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                       host_seg_len: *const i64, par: *const thip_param, a_kind: c_int, out: *mut *mut thip_mid16batch) -> c_int;
+    pub fn thip_mid16batch_store_bytes(n: usize, m: usize, a_kind: c_int, host_bytes: *mut usize) -> c_int;
+    pub fn thip_mid16batch_stored(h: *mut thip_mid16batch, i: c_int, host_words: *mut u16, host_inv_scale: *mut f32) -> c_int;
 
     // many small SDPs, each with its own A: the mid batch's iteration with the PSD cones projected on chip (thip_sdpbatch.hip)
     pub fn thip_sdpbatch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,

@@ -25,6 +25,12 @@ in flight per lane, with up to 1024 threads:
 
     midbatch_k and midbatch_init_k: the same -- no scratch at all, and >= 4 waves per SIMD.
 
+The mid16 batch (thip_mid16batch.hip, --family mid16batch) is the mid batch's iteration over a library-owned 16-bit copy of A, two
+chunks of eight columns in flight per lane, in one instance per stored form (bf16, f16):
+
+    mid16batch_k, _init_k, _start_k, _setbc_k, _seta_k (and mid16batch_convert_k): no scratch at all, at most 128 VGPRs and >= 4 waves
+    per SIMD.
+
 The SDP batch (thip_sdpbatch.hip, --family sdpbatch) is the mid batch's iteration with the PSD cones projected between the two passes
 by the workgroup itself (f32 MFMAs on operands in LDS), with up to 1024 threads:
 
@@ -51,7 +57,7 @@ Every family's translation unit also carries the four kernels of the round calls
 ownbatch_copy_a_k, ownbatch_stage_bc_k, ownbatch_gather_final_k): required, no scratch, at most 64 VGPRs, >= 4 waves per SIMD.
 
 usage: check_kernel_resources.py <remarks file> [--report]
-                                 [--family sweep|gemv_multi|smallbatch|midbatch|sdpbatch|raggedbatch|sparsebatch|
+                                 [--family sweep|gemv_multi|smallbatch|midbatch|mid16batch|sdpbatch|raggedbatch|sparsebatch|
                                           raggedsparse]"""
 import re
 import sys
@@ -111,6 +117,8 @@ def check_gemv_multi(res):
 OWNBATCH = {
     "smallbatch": (r"smallbatch(_init|_start|_seta)?_k", ("smallbatch_k", "smallbatch_init_k", "smallbatch_start_k", "smallbatch_seta_k"), None, "on-chip small-batch", "thip_smallbatch.hip"),
     "midbatch": (r"midbatch(_init|_start|_seta)?_k", ("midbatch_k", "midbatch_init_k", "midbatch_start_k", "midbatch_seta_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
+    "mid16batch": (r"mid16batch(_init|_start|_setbc|_seta|_convert)?_k", ("mid16batch_k", "mid16batch_init_k", "mid16batch_start_k", "mid16batch_setbc_k", "mid16batch_seta_k", "mid16batch_convert_k"), 128, "mid batch over a 16-bit A",
+                   "thip_mid16batch.hip"),
     "sdpbatch": (r"sdpbatch(_init|_project|_start|_seta)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k", "sdpbatch_seta_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
     "raggedbatch": (r"raggedbatch(_init|_start|_seta)?_k", ("raggedbatch_k", "raggedbatch_init_k", "raggedbatch_start_k", "raggedbatch_seta_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
     "sparsebatch": (r"sparsebatch(_init|_start|_seta|_scatter)?_k", ("sparsebatch_k", "sparsebatch_init_k", "sparsebatch_start_k", "sparsebatch_seta_k", "sparsebatch_scatter_k"), 128, "sparse batch", "thip_sparsebatch.hip"),

@@ -78,6 +78,11 @@ class MidBatchInfo(C.Structure):
     _fields_ = SmallBatchInfo._fields_ + [("load_bytes", C.c_int32), ("reserved", C.c_int32), ("a_bytes_per_iter", C.c_size_t)]
 
 
+class Mid16BatchInfo(C.Structure):
+    _fields_ = SmallBatchInfo._fields_ + [("load_bytes", C.c_int32), ("a_dtype", C.c_int32), ("a_bytes_per_iter", C.c_size_t),
+                                          ("a_store_bytes", C.c_size_t)]
+
+
 class SdpBatchInfo(C.Structure):
     _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
 
@@ -301,7 +306,8 @@ PROTOTYPES = {
 }
 
 # the own-A batch families share one C API (totsu_amd/csrc/thip_ownbatch.h): the same signatures under each prefix
-for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo), ("sdpbatch", SdpBatchInfo)):
+for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo), ("sdpbatch", SdpBatchInfo),
+                     ("mid16batch", Mid16BatchInfo)):
     _p = "thip_%s_" % _name
     PROTOTYPES.update({
         _p + "fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
@@ -328,6 +334,14 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         _p + "destroy": (_i, [_vp]),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
     })
+
+# what the mid16 batch adds: a create that carries the stored form, the size of a problem's block, the read-back of a block
+PROTOTYPES.update({
+    "thip_mid16batch_create_kind": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(Param), _i, C.POINTER(_vp)]),
+    "thip_mid16batch_store_bytes": (_i, [_sz, _sz, _i, C.POINTER(_sz)]),
+    "thip_mid16batch_stored": (_i, [_vp, _i, _vp, _vp]),
+})
 
 # the ragged batch: the same methods on a handle whose problems each have their own shape (totsu_amd/csrc/thip_raggedbatch.hip)
 _psz, _p32, _p64 = C.POINTER(_sz), C.POINTER(C.c_int32), C.POINTER(C.c_int64)

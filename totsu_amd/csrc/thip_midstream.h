@@ -1,10 +1,11 @@
 // thip_midstream.h -- what the batches that STREAM each problem's own A share (thip_midbatch.hip: the zero, nonnegative and
 // second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip; thip_raggedbatch.hip: the same on problems of
 // different shapes, through the locator seam of the bodies; thip_sparsebatch.hip: a sparse A held as packed entries, through the
-// matrix-policy seam; thip_raggedsparse.hip: both seams at once): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
+// matrix-policy seam; thip_raggedsparse.hip: both seams at once; thip_mid16batch.hip: the mid batch over a 16-bit copy of A, through the
+// matrix-policy seam): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
 // two passes per iteration, every vector in LDS -- with one hook in the block-cone phase between the two passes, the thread choice
 // and what they add to the info record.  The init kernel's body, the criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
-// Included once by each of the five translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// Included once by each of the six translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
 // A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when
@@ -156,6 +157,156 @@ __device__ __forceinline__ void mb_pass(const float *A, bool vec, int m, int n, 
 
 __device__ __forceinline__ bool mb_vec(const float *a, int m) { return (m & 3) == 0 && ((uintptr_t)a & 15u) == 0; }
 
+// ---- the pass over a 16-bit store (thip_mid16batch.hip) --------------------------------------------------------------------------
+// A problem's block of the store: n columns of ld16 = roundup4(m) 16-bit words, column-major, the pad rows zero; KIND THIP_A_F16: n
+// floats inv_s behind the matrix; the block a multiple of 16 bytes.  The WIDENED matrix W is what a pass works on: THIP_A_BF16 the word
+// shifted left 16 bits, THIP_A_F16 float(h) * inv_s[c] (one f32 multiply per entry, at widen time).  mb16_pass_t is mb_pass_t on W:
+// the same lanes hold the same entries (a lane's 4 consecutive rows are one 8-byte load: ld16 is a multiple of 4 and the block is
+// aligned, so there is no other path), the same chunks go to the same slices and every sum is formed in mb_pass_t's order -- a pad
+// entry is +0 and adds what that pass's unloaded zero adds.  A unit keeps two chunks of 8 columns in flight (128 bytes per lane, as
+// the f32 pass holds) and works them off one after the other, in the chunk order of mb_pass_t.
+constexpr size_t mb16_ld(size_t m) { return (m + 3) & ~(size_t)3; }
+__host__ __device__ inline size_t mb16_block_bytes(size_t n, size_t m, int kind)
+{
+    return (2 * mb16_ld(m) * n + (kind == THIP_A_F16 ? 4 * n : 0) + 15) & ~(size_t)15;
+}
+
+// the store is global memory: said to the compiler, which does not see it of a pointer that went through the slot and a cast of its
+// element type (the loads would be flat ones)
+typedef unsigned mb16_u2 __attribute__((ext_vector_type(2)));
+typedef const mb16_u2 __attribute__((address_space(1))) *mb16_gword;
+typedef const float __attribute__((address_space(1))) *mb16_gscale;
+
+template <int KIND>
+__device__ __forceinline__ float4 mb16_widen(const mb16_u2 r, float sc)
+{
+    float4 q;
+    if (KIND == THIP_A_BF16) {
+        q.x = __uint_as_float(r.x << 16); q.y = __uint_as_float(r.x & 0xffff0000u);
+        q.z = __uint_as_float(r.y << 16); q.w = __uint_as_float(r.y & 0xffff0000u);
+    } else {
+        // W is the ROUNDED product: the multiply must not be contracted into an addition that follows it after inlining (the |A|
+        // pass adds q * 1, which the compiler would otherwise turn into one fma of the word, the scale and the sum)
+#pragma clang fp contract(off)
+        typedef _Float16 mb16_h2 __attribute__((ext_vector_type(2)));
+        const unsigned rx = r.x, ry = r.y;                 // (scalars: a bit cast of a vector's element would read element 0 for both)
+        const mb16_h2 lo = __builtin_bit_cast(mb16_h2, rx), hi = __builtin_bit_cast(mb16_h2, ry);
+        q.x = (float)lo.x * sc; q.y = (float)lo.y * sc; q.z = (float)hi.x * sc; q.w = (float)hi.y * sc;
+    }
+    return q;
+}
+
+// A: the block as 8-byte words (a column is ld2 = ld16 / 4 of them), inv_s: the f16 column scales (unused for bf16)
+template <int KIND, bool ABS>
+__device__ __forceinline__ void mb16_pass_t(const uint2 *__restrict__ A, const float *__restrict__ inv_s, int ld2, int m, int n,
+                                            const float *xn, const float *xt, float *h, float *g, float *hp, float *gp)
+{
+    const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63, nw = T >> 6;
+    // (the wave's index in a scalar register: units, chunks and column bases are then uniform to the compiler too, and a load is a
+    // scalar base plus the lane's 32-bit offset, not a 64-bit address per lane and column)
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int R = (m + MB_ROWS - 1) / MB_ROWS;
+    const int S = R >= nw ? 1 : nw / R;
+    const int CB = max(MB_CK, (MB_SCRG / R) & ~(MB_CK - 1));
+    __syncthreads();
+    for (int cb0 = 0; cb0 < n; cb0 += CB) {
+        const int cbn = min(CB, n - cb0);
+        const int nch = (cbn + MB_CK - 1) / MB_CK;
+        for (int unit = w; unit < R * S; unit += nw) {
+            const int r = unit % R, s = unit / R;
+            const int row = r * MB_ROWS + lane * 4;
+            const bool in0 = row < m, in1 = row + 1 < m, in2 = row + 2 < m, in3 = row + 3 < m;
+            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f;
+            if (ABS) {
+                t0 = t1 = t2 = t3 = 1.0f;
+            } else {
+                if (in0) t0 = xt[row];
+                if (in1) t1 = xt[row + 1];
+                if (in2) t2 = xt[row + 2];
+                if (in3) t3 = xt[row + 3];
+            }
+            const char *const tile = reinterpret_cast<const char *>(A + r * (MB_ROWS / 4));      // (uniform)
+            const unsigned voff = (unsigned)lane * 8u;
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+            // the 8 columns from j0 on (nj of them exist) as they were loaded
+            auto fetch = [&](mb16_u2 (&raw)[MB_CK], int j0, int nj) {
+                if (nj == MB_CK) {                                                        // (uniform: the loads go out together)
+#pragma unroll
+                    for (int k = 0; k < MB_CK; ++k) {
+                        raw[k] = mb16_u2{ 0u, 0u };
+                        if (in0) raw[k] = *(mb16_gword)(tile + (size_t)(j0 + k) * (size_t)ld2 * 8u + voff);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < MB_CK; ++k) {
+                        raw[k] = mb16_u2{ 0u, 0u };
+                        if (in0 && k < nj)                                               // (row < m: the whole word lies in the column)
+                            raw[k] = *(mb16_gword)(tile + (size_t)(j0 + k) * (size_t)ld2 * 8u + voff);
+                    }
+                }
+            };
+            auto work = [&](const mb16_u2 (&raw)[MB_CK], int j0, int nj) {
+                const int ju = j0;                                                        // (the chunk is the wave's: a uniform index)
+#pragma unroll
+                for (int k = 0; k < MB_CK; ++k) {
+                    float xjk = 0.0f, sck = 1.0f;
+                    if (k < nj) {
+                        xjk = ABS ? 1.0f : xn[ju + k];
+                        if (KIND == THIP_A_F16) sck = ((mb16_gscale)inv_s)[ju + k];
+                    }
+                    float4 q = mb16_widen<KIND>(raw[k], sck);
+                    if (ABS) { q.x = fabsf(q.x); q.y = fabsf(q.y); q.z = fabsf(q.z); q.w = fabsf(q.w); }
+                    a0 = fmaf(q.x, xjk, a0); a1 = fmaf(q.y, xjk, a1);
+                    a2 = fmaf(q.z, xjk, a2); a3 = fmaf(q.w, xjk, a3);
+                    float d = q.x * t0;
+                    d = fmaf(q.y, t1, d); d = fmaf(q.z, t2, d); d = fmaf(q.w, t3, d);
+                    d = wave_sum_dpp(d);
+                    if (lane == 0 && k < nj) gp[r * CB + (ju + k - cb0)] = d;
+                }
+            };
+            for (int ch = s; ch < nch; ch += 2 * S) {
+                const int jA = cb0 + ch * MB_CK, jB = jA + S * MB_CK;
+                const int njA = min(MB_CK, cb0 + cbn - jA);
+                const bool two = ch + S < nch;                                            // (uniform)
+                const int njB = two ? min(MB_CK, cb0 + cbn - jB) : 0;
+                mb16_u2 ra[MB_CK], rb[MB_CK];
+                fetch(ra, jA, njA);
+                fetch(rb, jB, njB);
+                __builtin_amdgcn_sched_barrier(0);                                        // (every load issued before the first use;
+                work(ra, jA, njA);                                                        // the second chunk's words stay packed until
+                __builtin_amdgcn_sched_barrier(0);                                        // the first is worked off: registers)
+                if (two) work(rb, jB, njB);
+            }
+            // the unit's row sums: (s, row) is this lane's alone
+            float *hs = hp + s * m + row;
+            if (cb0 == 0) {
+                if (in0) hs[0] = a0;
+                if (in1) hs[1] = a1;
+                if (in2) hs[2] = a2;
+                if (in3) hs[3] = a3;
+            } else {
+                if (in0) hs[0] += a0;
+                if (in1) hs[1] += a1;
+                if (in2) hs[2] += a2;
+                if (in3) hs[3] += a3;
+            }
+        }
+        __syncthreads();
+        for (int t = tid; t < cbn; t += T) {
+            float acc = gp[t];
+            for (int r = 1; r < R; ++r) acc += gp[r * CB + t];
+            g[cb0 + t] = acc;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < m; i += T) {
+        float acc = hp[i];
+        for (int s = 1; s < S; ++s) acc += hp[s * m + i];
+        h[i] = acc;
+    }
+    __syncthreads();
+}
+
 extern __shared__ float mb_lds[];
 
 // the block-cone phase of a family without PSD cones: nothing beside the second-order cones
@@ -175,6 +326,25 @@ struct MbDenseA {
                                          float *gp) const
     {
         mb_pass<ABS>(M.A, M.vec, m, n, xn, xt, h, g, hp, gp);
+    }
+};
+
+// MbDenseA16<KIND>: the pointer is the problem's block of a 16-bit store (above), nothing is loaded, the pass streams the block and
+// works on the widened matrix (mb16_pass_t) -- the |A| sums of the preconditioner included, so they are those of W
+template <int KIND>
+struct MbDenseA16 {
+    struct Mat { const uint2 *A; const float *inv_s; int ld2; };
+    __device__ __forceinline__ Mat open(const float *a, int m, int n, float *) const
+    {
+        const int ld16 = (m + 3) & ~3;
+        const uint16_t *const words = reinterpret_cast<const uint16_t *>(a);
+        return Mat{ reinterpret_cast<const uint2 *>(a), reinterpret_cast<const float *>(words + (size_t)n * (size_t)ld16), ld16 >> 2 };
+    }
+    template <bool ABS>
+    __device__ __forceinline__ void pass(const Mat &M, int m, int n, const float *xn, const float *xt, float *h, float *g, float *hp,
+                                         float *gp) const
+    {
+        mb16_pass_t<KIND, ABS>(M.A, M.inv_s, M.ld2, m, n, xn, xt, h, g, hp, gp);
     }
 };
 
@@ -382,6 +552,19 @@ struct MbInfo {
         ObInfo()(h, o);
         o.load_bytes = ((h->m & 3) == 0 && h->n_unaligned == 0) ? 16 : 4;
         o.a_bytes_per_iter = 2 * h->m * h->n * sizeof(float);
+    }
+};
+
+// the same for a family over a 16-bit store (thip_mid16batch_info_t): one load path, the stored bytes read twice per iteration
+struct Mb16Info {
+    template <class INFO>
+    void operator()(const OwnBatch *h, INFO &o) const
+    {
+        ObInfo()(h, o);
+        o.load_bytes = 8;
+        o.a_bytes_per_iter = 2 * (2 * mb16_ld(h->m) * h->n + (h->a_kind == THIP_A_F16 ? 4 * h->n : 0));
+        o.a_dtype = h->a_kind;
+        o.a_store_bytes = h->a_block * h->n_prob;
     }
 };
 

@@ -1,5 +1,6 @@
 // thip_ownbatch.h -- what the "every problem has its OWN A" batches share (thip_smallbatch.hip: A in LDS; thip_midbatch.hip,
-// thip_sdpbatch.hip and thip_raggedbatch.hip: A streamed from memory, thip_midstream.h).
+// thip_sdpbatch.hip and thip_raggedbatch.hip: A streamed from memory, thip_midstream.h; thip_mid16batch.hip: a 16-bit copy of A that the
+// family owns, streamed -- ObStore).
 //   device: the launch arguments (ObArgs), the status block and the slot of a problem, the problem's scalars (ObScalars), the
 //           init kernel's body (ob_init_body), the criteria sums and status_eval (ob_criteria_sums, ob_status_eval), and the
 //           functions of the iteration that do not touch A (block_sums; thip_step.h: the arithmetic every loop shares).  The two recurrences -- three passes
@@ -477,6 +478,18 @@ struct ObPsd { int max_k = 0, n_psd = 0; size_t tail_bytes = 0; };
 
 struct OwnBatch;
 
+// a family that owns its matrix store -- a converted copy of every problem's A (the mid16 batch: 16-bit words) -- hands in these
+// three.  create: allocates the whole store with ob_alloc (so no array handed to a _dev call may overlap it), records it in the
+// handle (a_store, a_block, a_kind: `arg` is the create call's word for the stored form), converts every problem from the f32 stack
+// at dev_mats_a and points every slot at its block; called once, behind ob_build, and the f32 stack is not referenced after it
+// returns.  convert: the problems first .. first + count - 1 again, from `count` f32 matrices (m n floats each, column-major) that
+// lie one after another in device memory at dev_src -- one launch for the range.  slot: the pointer problem p's slot holds
+struct ObStore {
+    int (*create)(OwnBatch *h, const float *dev_mats_a, int arg);
+    int (*convert)(OwnBatch *h, int first, int count, const float *dev_src);
+    const float *(*slot)(const OwnBatch *h, size_t p);
+};
+
 // a family: everything the generic API bodies below need to know about it
 struct ObFamily {
     ObText text;
@@ -494,7 +507,9 @@ struct ObFamily {
     int (*setbc)(const OwnBatch *h, const ObArgs &a, const ObSetBc &s, unsigned count);      // the set_bc kernel (NULL: by class)
     // the set_a kernel (a sparse family: the scatter launch ahead of it; NULL: by class)
     int (*seta)(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count);
-    const void *kernels[6];                 // every kernel that asks for more than 64 KiB of LDS
+    const void *kernels[12];                // every kernel that asks for more than 64 KiB of LDS
+    // NULL, or the family OWNS its matrix store (ObStore, below): the slots' `a` point into it, never at caller memory
+    const ObStore *store = nullptr;
     size_t total = 0;                       // device memory held by every handle of the family
     std::once_flag attr_once;
     hipError_t attr_err = hipSuccess;
@@ -540,6 +555,8 @@ struct OwnBatch {
     // call which moves A in place allocates none
     void *tab_host = nullptr, *tab_dev = nullptr; size_t tab_bytes = 0;
     size_t last_h2d = 0, last_d2h = 0;      // what the last _dev call moved between host and device (thip_test_ownbatch_last_transfer)
+    // a family that owns its matrix store (ObStore): the store, the bytes of one problem's block and the stored form
+    void *a_store = nullptr; size_t a_block = 0; int a_kind = 0;
 };
 
 // the cone segments (no device needed).  On success *cones holds (beg, end, kind) per block cone -- kind 0: second-order, 1: rotated,
@@ -717,7 +734,7 @@ int ob_destroy(H *h)
     if (!h) return 0;
     if (ctx().inited) hipStreamSynchronize(ctx().stream);
     hipFree(h->arena); hipFree(h->dst); hipFree(h->slots); hipFree(h->live_dev); hipFree(h->cones_dev); hipFree(h->cls_dev);
-    hipFree(h->stage); hipFree(h->bc_store); hipFree(h->bc_at_dev); hipFree(h->sol_at_dev);
+    hipFree(h->stage); hipFree(h->bc_store); hipFree(h->bc_at_dev); hipFree(h->sol_at_dev); hipFree(h->a_store);
     if (h->stage_host) hipHostFree(h->stage_host);
     if (h->tab_host) hipHostFree(h->tab_host);
     if (h->hst) hipHostFree(h->hst);
@@ -845,6 +862,8 @@ int ob_precond(const ObFamily &f, OwnBatch *h, int i, float *host_dp_tau, float 
     return ob_precond_at(h, i, h->arena + (size_t)i * h->stride, h->n, h->m, host_dp_tau, host_dp_sigma);
 }
 
+int ob_dev_foreign(const OwnBatch *h, const void *p, size_t bytes, const char *what);      // (below, with the _dev calls)
+
 int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c, const float *dev_vec_b_rowabs)
 {
     THIP_NEED_INIT();
@@ -852,6 +871,11 @@ int ob_replace(const ObFamily &f, OwnBatch *h, int i, const float *dev_mat_a, co
     if (!dev_mat_a || !dev_vec_b || !dev_vec_c) return fail(THIP_E_INVALID, "null A, b or c", __FILE__, __LINE__);
     if (((uintptr_t)dev_mat_a | (uintptr_t)dev_vec_b | (uintptr_t)dev_vec_c | (uintptr_t)dev_vec_b_rowabs) & 3u)
         return fail(THIP_E_INVALID, "the arrays hold floats: 4-byte alignment", __FILE__, __LINE__);
+    if (f.store) {                          // the new A goes into slot i's block of the store, which the slot keeps pointing at
+        THIP_RC(ob_dev_foreign(h, dev_mat_a, h->m * h->n * sizeof(float), "dev_mat_a"));
+        THIP_RC(f.store->convert(h, i, 1, dev_mat_a));
+        dev_mat_a = f.store->slot(h, (size_t)i);
+    }
     const SbSlot s{ dev_mat_a, dev_vec_b, dev_vec_c, dev_vec_b_rowabs };
     THIP_TRY(hipMemcpyAsync(h->slots + i, &s, sizeof(SbSlot), hipMemcpyHostToDevice, ctx().stream));
     THIP_TRY(hipStreamSynchronize(ctx().stream));           // (s is a local)
@@ -1106,7 +1130,16 @@ int ob_set_a(const ObFamily &f, OwnBatch *h, int first, int count, const float *
     const size_t per = h ? h->m * h->n : 0;
     size_t total = 0;
     THIP_RC(ob_seta_check(f, h, first, count, host_values, host_counts, [&](int) { return per; }, OB_SETA_DENSE, &total));
-    int rc = ob_seta_copy(h, first, count, host_values, [&](int) { return per; });
+    int rc = 0;
+    if (f.store) {                          // the sparse families' route: up to the handle's stage, a convert launch of its own
+        void *pinned = nullptr;
+        THIP_RC(ob_stage_reserve(h, total * sizeof(float), &pinned));
+        memcpy(pinned, host_values, total * sizeof(float));
+        THIP_TRY(hipMemcpyAsync(h->stage, pinned, total * sizeof(float), hipMemcpyHostToDevice, ctx().stream));
+        rc = f.store->convert(h, first, count, static_cast<const float *>(h->stage));
+    } else {
+        rc = ob_seta_copy(h, first, count, host_values, [&](int) { return per; });
+    }
     if (rc == 0) {
         ObArgs a = ob_args(h);
         a.first = first;
@@ -1350,8 +1383,43 @@ int ob_set_a_dev_dense_t(const ObFamily &f, OwnBatch *h, int first, int count, c
     return ob_dev_finish(h, first, count, launch);
 }
 
+// thip_NAME_set_a_dev of a family that owns its matrix store: the values are converted from where they lie into the slots' blocks, one
+// launch, behind the check kernel's verdict.  There is no in-place form: no f32 A lies behind the slots
+template <class LAUNCH>
+int ob_set_a_dev_store(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_values, const LAUNCH &launch)
+{
+    THIP_NEED_INIT();
+    THIP_RC(ob_dev_range(f, h, first, count));
+    if (!dev_values)
+        return fail(THIP_E_INVALID, "null values of A: this batch holds a converted copy of every A and no f32 A lies in place to be read "
+                                    "again (hand the values in)", __FILE__, __LINE__);
+    const size_t cnt = (size_t)count, per = h->m * h->n;
+    THIP_RC(ob_dev_foreign(h, dev_values, cnt * per * sizeof(float), "dev_values"));
+    ObDevStage sg;
+    sg.verdict = cnt * sizeof(int); sg.tables = cnt * sizeof(ObDevRow);
+    THIP_RC(sg.reserve(h));
+    ObDevRow *rows = reinterpret_cast<ObDevRow *>(sg.rows());
+    for (size_t k = 0; k < cnt; ++k) rows[k] = ObDevRow{ dev_values + k * per, nullptr, (long long)per };
+    THIP_RC(sg.upload(h));
+    int row, why;
+    THIP_RC(sg.check(h, count, 0, &row, &why));
+    if (row >= 0) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "problem %d: a value of A is not finite", first + row);
+        return fail(THIP_E_INVALID, msg, __FILE__, __LINE__);
+    }
+    THIP_RC(f.store->convert(h, first, count, dev_values));
+    return ob_dev_finish(h, first, count, launch);
+}
+
 int ob_set_a_dev(const ObFamily &f, OwnBatch *h, int first, int count, const float *dev_values, int keep)
 {
+    if (f.store)
+        return ob_set_a_dev_store(f, h, first, count, dev_values, [&]() {
+            ObArgs a = ob_args(h);
+            a.first = first;
+            return f.seta(h, a, ObSetA{ ObStart{ nullptr, nullptr, 0 }, keep != 0 }, (unsigned)count);
+        });
     const size_t per = h ? h->m * h->n : 0;
     return ob_set_a_dev_dense_t(f, h, first, count, dev_values, [&](int) { return per; }, [&]() {
         ObArgs a = ob_args(h);
@@ -1597,7 +1665,7 @@ int ob_fits(const ObFamily &f, size_t n, size_t m, size_t n_seg, const int32_t *
 template <class H>
 int ob_create(ObFamily &f, size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b, const float *dev_vecs_c,
               const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
-              const thip_param *par, H **out)
+              const thip_param *par, H **out, int store_arg = 0)
 {
     if (!out) return fail(THIP_E_INVALID, "null argument", __FILE__, __LINE__);
     *out = nullptr;
@@ -1626,6 +1694,7 @@ int ob_create(ObFamily &f, size_t n, size_t m, size_t n_prob, const float *dev_m
     }
     rc = ob_attr(f);
     if (rc == 0) rc = ob_build(h, dev_mats_a, dev_vecs_b, dev_vecs_c, dev_vecs_b_rowabs);
+    if (rc == 0 && f.store) rc = f.store->create(h, dev_mats_a, store_arg);
     if (rc != 0) { ob_destroy(h); return rc; }
     *out = h;
     return 0;

@@ -156,10 +156,10 @@ class OwnBatchSolver:
             self.vecs_b_rowabs = None if vecs_b_rowabs is None else self._dev(vecs_b_rowabs)
             par = _c_param(self.param)
             h = C.c_void_p()
-            self._c("create")(self.n, self.m, self.n_prob, self.mats_a.ptr, self.vecs_b.ptr, self.vecs_c.ptr,
-                              None if self.vecs_b_rowabs is None else self.vecs_b_rowabs.ptr, len(self._st),
-                              self._st.ctypes.data_as(C.POINTER(C.c_int32)), self._sl.ctypes.data_as(C.POINTER(C.c_int64)),
-                              C.byref(par), C.byref(h))
+            self._create(self.n, self.m, self.n_prob, self.mats_a.ptr, self.vecs_b.ptr, self.vecs_c.ptr,
+                         None if self.vecs_b_rowabs is None else self.vecs_b_rowabs.ptr, len(self._st),
+                         self._st.ctypes.data_as(C.POINTER(C.c_int32)), self._sl.ctypes.data_as(C.POINTER(C.c_int64)),
+                         C.byref(par), C.byref(h))
             self.h = h
             if force_threads is not None:
                 getattr(lib, self._force_hook)(self.h, int(force_threads))
@@ -167,6 +167,10 @@ class OwnBatchSolver:
         except Exception:
             self.destroy()
             raise
+
+    def _create(self, *args):
+        """the family's create call on the arguments of thip_NAME_create (a family whose create takes more overrides this)"""
+        self._c("create")(*args)
 
     @staticmethod
     def _count(vecs_b, m, name):
