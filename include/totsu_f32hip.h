@@ -880,6 +880,62 @@ int thip_sdpbatch_info(const thip_sdpbatch *h, thip_sdpbatch_info_t *host_info);
 int thip_sdpbatch_destroy(thip_sdpbatch *h);
 
 /* ---------------------------------------------------------------------------------------------
+ * The WIDE batch: thip_sdpbatch's iteration on every shape up to 4096 x 4096 (thip_widebatch.hip).  Only what a pass
+ * over A touches lies in LDS -- the iterates x_x u x_y v, the pass results, the class bytes --; every other vector of the iteration is
+ * read and written in place in the problem's block of the arena (6 n + 11 m floats), so the shape rule is no longer the vectors'.
+ * The interface is thip_sdpbatch's, one for one, and on a shape that thip_midbatch / thip_sdpbatch also takes the iterates, the status
+ * blocks and the first 6 n + 10 m floats of a problem's arena block are theirs bit for bit.
+ * Accepted: 1 <= m, n <= 4096, segments of all five cones that cover m, every PSD segment of k (k + 1) / 2 rows with 1 <= k <= 64, an
+ * LDS map of at most 163 840 bytes -- 4 (6208 + 3 n + 3 m) + roundup4(m), plus 49 920 when the largest PSD order exceeds 32: without
+ * such an order every shape fits (4096 x 4096 takes 127 232 bytes), with one 12 (n + m) + roundup4(m) <= 89 088 --,
+ * 1 <= n_prob <= 1 048 576.  Everything else is THIP_E_INVALID before anything is allocated.  No chooser returns this family: whether
+ * it beats one thip_solver per problem in turn depends on the number of problems (README.md).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_widebatch thip_widebatch;
+typedef struct thip_widebatch_info_t {
+    int32_t n_prob, threads;          /* as thip_sdpbatch_info_t ... */
+    int32_t lds_bytes, live;
+    size_t  arena_bytes;
+    size_t  device_bytes;
+    size_t  device_bytes_all;         /* summed over every thip_widebatch alive in the process */
+    int64_t launches, workgroups;
+    int32_t load_bytes, reserved;
+    size_t  a_bytes_per_iter;
+    int32_t max_psd_order, n_psd;
+    size_t  psd_lds_bytes;
+    size_t  lds_bytes_per_problem;    /* ... and: the LDS of one problem's workgroup in the iteration (what thip_widebatch_fits reports) */
+    size_t  arena_bytes_per_problem;  /* one problem's block of the arena: 4 (6 n + 11 m) */
+} thip_widebatch_info_t;
+/* the shape rules alone (needs no device): 0 and the LDS bytes / threads of one workgroup, or THIP_E_INVALID */
+int thip_widebatch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                        size_t *host_lds_bytes, int *host_threads);
+int thip_widebatch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                          const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                          const int64_t *host_seg_len, const thip_param *par, thip_widebatch **out);
+int thip_widebatch_set_param(thip_widebatch *h, const thip_param *par);
+int thip_widebatch_init(thip_widebatch *h);
+int thip_widebatch_run(thip_widebatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_widebatch_run_until_any(thip_widebatch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_widebatch_status(thip_widebatch *h, int i, thip_status *host_status);
+int thip_widebatch_solution(thip_widebatch *h, int i, float *host_x, float *host_y);
+int thip_widebatch_iterate(thip_widebatch *h, int i, float *host_x, float *host_y);
+int thip_widebatch_precond(thip_widebatch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_widebatch_replace(thip_widebatch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                           const float *dev_vec_b_rowabs);
+int thip_widebatch_set_iterates(thip_widebatch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_widebatch_set_bc(thip_widebatch *h, int first, int count, const float *host_b, const float *host_c,
+                          const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_widebatch_solutions(thip_widebatch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_widebatch_set_a(thip_widebatch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_widebatch_set_bc_dev(thip_widebatch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_widebatch_set_a_dev(thip_widebatch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_widebatch_set_iterates_dev(thip_widebatch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_widebatch_solutions_dev(thip_widebatch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
+int thip_widebatch_info(const thip_widebatch *h, thip_widebatch_info_t *host_info);
+int thip_widebatch_destroy(thip_widebatch *h);
+
+/* ---------------------------------------------------------------------------------------------
  * The RAGGED batch: many conic programs, each with its own dense f32 A, its own n_p, m_p and its own cone layout, in one batch
  * (thip_raggedbatch.hip).  The iteration is thip_sdpbatch's on every problem -- one workgroup per running problem,
  * its vectors in LDS, its A streamed twice per iteration, its PSD cones projected on chip --, and a problem's iterates are, bit for

@@ -74,6 +74,18 @@ pub struct thip_sdpbatch_info_t {
 }
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
+pub struct thip_widebatch_info_t {
+    pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub load_bytes: i32, pub reserved: i32,
+    pub a_bytes_per_iter: usize,
+    pub max_psd_order: i32, pub n_psd: i32,
+    pub psd_lds_bytes: usize,
+    pub lds_bytes_per_problem: usize, pub arena_bytes_per_problem: usize,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
 pub struct thip_sparsebatch_info_t {
     pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
     pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
@@ -177,6 +189,7 @@ pub enum thip_smallbatch {}
 pub enum thip_midbatch {}
 pub enum thip_mid16batch {}
 pub enum thip_sdpbatch {}
+pub enum thip_widebatch {}
 pub enum thip_raggedbatch {}
 pub enum thip_sparsebatch {}
 pub enum thip_raggedsparse {}
@@ -466,6 +479,33 @@ extern "C" {
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
     pub fn thip_test_sdpbatch_project(k: c_int, count: c_int, dev_packed: *mut f32, dev_rx_or_null: *mut f32) -> c_int;
+    // the SDP batch's iteration on every shape to 4096 x 4096: all but the pass vectors left in the arena (thip_widebatch.hip)
+    pub fn thip_widebatch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                              host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;
+    pub fn thip_widebatch_create(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                host_seg_len: *const i64, par: *const thip_param, out: *mut *mut thip_widebatch) -> c_int;
+    pub fn thip_widebatch_set_param(h: *mut thip_widebatch, par: *const thip_param) -> c_int;
+    pub fn thip_widebatch_init(h: *mut thip_widebatch) -> c_int;
+    pub fn thip_widebatch_run(h: *mut thip_widebatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_widebatch_run_until_any(h: *mut thip_widebatch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_widebatch_status(h: *mut thip_widebatch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_widebatch_solution(h: *mut thip_widebatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_widebatch_iterate(h: *mut thip_widebatch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_widebatch_precond(h: *mut thip_widebatch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_widebatch_replace(h: *mut thip_widebatch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
+                                 dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_widebatch_set_iterates(h: *mut thip_widebatch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
+    pub fn thip_widebatch_set_bc(h: *mut thip_widebatch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_widebatch_solutions(h: *mut thip_widebatch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_widebatch_set_a(h: *mut thip_widebatch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_widebatch_set_bc_dev(h: *mut thip_widebatch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_widebatch_set_a_dev(h: *mut thip_widebatch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_widebatch_set_iterates_dev(h: *mut thip_widebatch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_widebatch_solutions_dev(h: *mut thip_widebatch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
+    pub fn thip_widebatch_info(h: *const thip_widebatch, host_info: *mut thip_widebatch_info_t) -> c_int;
+    pub fn thip_widebatch_destroy(h: *mut thip_widebatch) -> c_int;
+    pub fn thip_test_widebatch_force_threads(h: *mut thip_widebatch, threads: c_int) -> c_int;
 
     // problems of different shapes and cone layouts in one batch: the SDP batch's iteration on a problem the workgroup looks up
     // (thip_raggedbatch.hip)

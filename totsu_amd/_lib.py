@@ -87,6 +87,10 @@ class SdpBatchInfo(C.Structure):
     _fields_ = MidBatchInfo._fields_ + [("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t)]
 
 
+class WideBatchInfo(C.Structure):
+    _fields_ = SdpBatchInfo._fields_ + [("lds_bytes_per_problem", C.c_size_t), ("arena_bytes_per_problem", C.c_size_t)]
+
+
 class SparseBatchInfo(C.Structure):
     _fields_ = SmallBatchInfo._fields_ + [("a_bytes_per_iter", C.c_size_t), ("max_psd_order", C.c_int32), ("n_psd", C.c_int32),
                                           ("psd_lds_bytes", C.c_size_t), ("nnz_cap", C.c_size_t), ("nnz_total", C.c_size_t),
@@ -307,7 +311,7 @@ PROTOTYPES = {
 
 # the own-A batch families share one C API (totsu_amd/csrc/thip_ownbatch.h): the same signatures under each prefix
 for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo), ("sdpbatch", SdpBatchInfo),
-                     ("mid16batch", Mid16BatchInfo)):
+                     ("mid16batch", Mid16BatchInfo), ("widebatch", WideBatchInfo)):
     _p = "thip_%s_" % _name
     PROTOTYPES.update({
         _p + "fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),

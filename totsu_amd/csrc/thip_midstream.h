@@ -2,10 +2,11 @@
 // second-order cones; thip_sdpbatch.hip: those and PSD cones projected on chip; thip_raggedbatch.hip: the same on problems of
 // different shapes, through the locator seam of the bodies; thip_sparsebatch.hip: a sparse A held as packed entries, through the
 // matrix-policy seam; thip_raggedsparse.hip: both seams at once; thip_mid16batch.hip: the mid batch over a 16-bit copy of A, through the
-// matrix-policy seam): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
+// matrix-policy seam; thip_widebatch.hip: the SDP batch's iteration with all but the pass vectors left in the arena, through the
+// vector-placement seam): the LDS map of a problem's vectors, the pass over A (mb_pass), the iteration's body -- the carried recurrence,
 // two passes per iteration, every vector in LDS -- with one hook in the block-cone phase between the two passes, the thread choice
 // and what they add to the info record.  The init kernel's body, the criteria, status_eval, the launch arguments and the whole host side are every family's: thip_ownbatch.h.
-// Included once by each of the six translation units (on top of thip_ownbatch.h): everything here is internal to the one that
+// Included once by each of the seven translation units (on top of thip_ownbatch.h): everything here is internal to the one that
 // includes it.
 //
 // A pass (mb_pass): the rows are cut into tiles of MB_ROWS = 256 (a lane holds 4 consecutive rows: one 16-byte load per column when
@@ -307,12 +308,42 @@ __device__ __forceinline__ void mb16_pass_t(const uint2 *__restrict__ A, const f
     __syncthreads();
 }
 
+// ---- the vector placement: the third seam of the bodies (beside AT and MAT) -------------------------------------------------------
+// Where each vector of an iteration lives.  MbInLds, every family's but one: all of them in LDS by MbMap, the arena block copied in
+// at launch entry and out at exit -- the bodies hold that text themselves, under `if constexpr (VP::in_lds)`, as they held it before
+// the seam (a helper per phase would be optimised on its own before it is inlined, and the kernels would no longer be the ones they
+// were).  Any other placement hands the body an MbVecs -- every vector as the body addresses it, wherever it lies (vecs: those in
+// LDS, from its map alone; place: those in the problem's arena block or behind its slot, once the body knows them) -- and says what
+// the load phase copies into LDS (load), what the store phase copies back (store_mut), where a start puts the iterate it is handed
+// (start_fill), and which map the init-time bodies lay b c g h Ty Ts out by (InitMap; sync_maps: the barrier between a use of that
+// map and one of the iteration's where the two overlap).  The arithmetic between those phases is one text for every placement.
+// thip_widebatch.hip hands in the placement that leaves all but the pass's inputs and outputs in the arena.
+// Vectors that are NOT in LDS are exchanged between lanes only across __syncthreads() -- a workgroup-scope release and acquire, which
+// covers the plain global stores and loads of one workgroup -- and are never read through __restrict__ or non-temporal paths.
+struct MbVecs {
+    float *lds;                                                                 // the map's base (the PSD tail lies behind the map)
+    float *sh, *hp, *gp;
+    float *xx, *u, *kx, *ku, *xy, *xs, *v, *ky, *ks, *kv;
+    const float *Tx, *Ty, *Ts, *Sv;
+    float *hx, *gx;
+    const float *b, *c;
+    float *rxs, *g, *h;
+    unsigned char *cls;
+};
+
+struct MbInLds {
+    static constexpr bool in_lds = true;
+    using Map = MbMap;
+    using InitMap = MbMap;
+};
+
 extern __shared__ float mb_lds[];
 
 // the block-cone phase of a family without PSD cones: nothing beside the second-order cones
 struct MbNoPsd {
     static constexpr bool psd = false;
     __device__ __forceinline__ void operator()(float *, const MbMap &, const ObArgs &) const {}
+    __device__ __forceinline__ void placed(const MbVecs &, const ObArgs &) const {}
 };
 
 // the matrix policy of the two bodies: what the slot's `a` pointer means and what is loaded at launch entry (open: called by every
@@ -349,11 +380,11 @@ struct MbDenseA16 {
 };
 
 // ob_init_body with the |A| sums from one pass
-template <class AT = ObUniform, class MAT = MbDenseA>
-__device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT(), const MAT &mat = MAT())
+template <class AT = ObUniform, class MAT = MbDenseA, class VP = MbInLds>
+__device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT(), const MAT &mat = MAT(), const VP & = VP())
 {
     const int n = a.n, m = a.m;
-    const MbMap L(n, m);
+    const typename VP::InitMap L(n, m);
     float *S = mb_lds;
     ob_init_body(a, at.problem(a), L, S, [&](const float *A) {
         mat.template pass<true>(mat.open(A, m, n, S), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
@@ -361,11 +392,12 @@ __device__ __forceinline__ void mb_init_body(const ObArgs &a, const AT &at = AT(
 }
 
 // ob_init_body on a staged (b, c), the |A| sums from the same pass: a problem takes a new (b, c) and keeps the A its slot points at
-template <class AT = ObUniform, class MAT = MbDenseA>
-__device__ __forceinline__ void mb_setbc_body(const ObArgs &a, const ObSetBc &sb, const AT &at = AT(), const MAT &mat = MAT())
+template <class AT = ObUniform, class MAT = MbDenseA, class VP = MbInLds>
+__device__ __forceinline__ void mb_setbc_body(const ObArgs &a, const ObSetBc &sb, const AT &at = AT(), const MAT &mat = MAT(),
+                                              const VP & = VP())
 {
     const int n = a.n, m = a.m;
-    const MbMap L(n, m);
+    const typename VP::InitMap L(n, m);
     float *S = mb_lds;
     ob_init_body(a, at.problem(a), L, S, [&](const float *A) {
         mat.template pass<true>(mat.open(A, m, n, S), m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
@@ -374,9 +406,11 @@ __device__ __forceinline__ void mb_setbc_body(const ObArgs &a, const ObSetBc &sb
 
 // `steps` whole iterations of one problem by one workgroup.  PSD: what the family does with its PSD cones between the two passes
 // (called by every thread, after the second-order cones; hp, gp and g are dead there).  AT: which problem and where its arena block
-// lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor).  MAT: the matrix policy (above)
-template <class PSD, class AT = ObUniform, class MAT = MbDenseA>
-__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones, const AT &at = AT(), const MAT &mat = MAT())
+// lies (thip_ownbatch.h: ObUniform, or the ragged batch's descriptor).  MAT: the matrix policy (above).  VP: the vector placement
+// (above)
+template <class PSD, class AT = ObUniform, class MAT = MbDenseA, class VP = MbInLds>
+__device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_cones, const AT &at = AT(), const MAT &mat = MAT(),
+                                                const VP &vp = VP())
 {
     const int p = at.problem(a);
     SbStatus *const gst = a.st + p;
@@ -384,27 +418,47 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6, nw = T >> 6;
     const bool comp = a.comp != 0;
-    const MbMap L(n, m);
+    const typename VP::Map L(n, m);
     float *S = mb_lds;
-    float *const sh = S + L.sh, *const hp = S + L.hp, *const gp = S + L.gp;
-    float *const xx = S + L.xx, *const u = S + L.u, *const kx = S + L.kx, *const ku = S + L.ku;
-    float *const xy = S + L.xy, *const xs = S + L.xs, *const v = S + L.v, *const ky = S + L.ky, *const ks = S + L.ks, *const kv = S + L.kv;
-    const float *const Tx = S + L.Tx, *const Ty = S + L.Ty, *const Ts = S + L.Ts, *const Sv = S + L.Sv;
-    float *const hx = S + L.hx, *const gx = S + L.gx;
-    const float *const b = S + L.b, *const c = S + L.c;
-    float *const rxs = S + L.rxs, *const g = S + L.g, *const h = S + L.h;
-    unsigned char *const cls = reinterpret_cast<unsigned char *>(S + L.cls);
+    float *sh, *hp, *gp, *xx, *u, *kx, *ku, *xy, *xs, *v, *ky, *ks, *kv, *hx, *gx, *rxs, *g, *h;
+    const float *Tx, *Ty, *Ts, *Sv, *b, *c;
+    unsigned char *cls;
+    if constexpr (VP::in_lds) {
+        sh = S + L.sh; hp = S + L.hp; gp = S + L.gp;
+        xx = S + L.xx; u = S + L.u; kx = S + L.kx; ku = S + L.ku;
+        xy = S + L.xy; xs = S + L.xs; v = S + L.v; ky = S + L.ky; ks = S + L.ks; kv = S + L.kv;
+        Tx = S + L.Tx; Ty = S + L.Ty; Ts = S + L.Ts; Sv = S + L.Sv;
+        hx = S + L.hx; gx = S + L.gx;
+        b = S + L.b; c = S + L.c;
+        rxs = S + L.rxs; g = S + L.g; h = S + L.h;
+        cls = reinterpret_cast<unsigned char *>(S + L.cls);
+    }
 
     // ---- load ----
     const SbSlot sl = a.slots[p];
     const auto A = mat.open(sl.a, m, n, S);
     float *const ar = at.block(a, p);
-    {
-        const int nstate = 6 * n + 10 * m;                 // the arena's order is the LDS order from xx on
-        for (int i = tid; i < nstate; i += T) xx[i] = ar[i];
+    [[maybe_unused]] MbVecs V{};                           // (a placement other than LDS alone uses it: where each vector lies)
+    if constexpr (VP::in_lds) {
+        {
+            const int nstate = 6 * n + 10 * m;             // the arena's order is the LDS order from xx on
+            for (int i = tid; i < nstate; i += T) xx[i] = ar[i];
+        }
+        for (int i = tid; i < m; i += T) { S[L.b + i] = sl.b[i]; cls[i] = a.cls[i]; }
+        for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
+    } else {
+        V = vp.vecs(S, L);
+        vp.place(V, ar, sl, n, m);
+        sh = V.sh; hp = V.hp; gp = V.gp;
+        xx = V.xx; u = V.u; kx = V.kx; ku = V.ku;
+        xy = V.xy; xs = V.xs; v = V.v; ky = V.ky; ks = V.ks; kv = V.kv;
+        Tx = V.Tx; Ty = V.Ty; Ts = V.Ts; Sv = V.Sv;
+        hx = V.hx; gx = V.gx;
+        b = V.b; c = V.c;
+        rxs = V.rxs; g = V.g; h = V.h;
+        cls = V.cls;
+        vp.load(V, ar, a.cls, n, m, T, tid);
     }
-    for (int i = tid; i < m; i += T) { S[L.b + i] = sl.b[i]; cls[i] = a.cls[i]; }
-    for (int i = tid; i < n; i += T) S[L.c + i] = sl.c[i];
     ObScalars s;
     s.load(gst);
     __syncthreads();
@@ -444,7 +498,8 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
                 sb_soc(xs, rxs, beg, end, rot, lane);
             }
         }
-        psd_cones(S, L, a);
+        if constexpr (VP::in_lds) psd_cones(S, L, a);
+        else psd_cones.placed(V, a);
         // ---- h = A x_x, g = A^T x_y of the new iterate: the criteria, and K rx = K x_k - 2 K x_{k+1} ----
         mat.template pass<false>(A, m, n, xx, xy, h, g, hp, gp);
         ob_criteria_sums(q, n, m, s.tau, a.eps_zero, b, c, xx, xy, xs, h, g, sh);
@@ -468,11 +523,13 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
 
     // ---- store ----
     __syncthreads();
-    {
+    if constexpr (VP::in_lds) {
         const int nmut = 4 * n + 6 * m;
         for (int i = tid; i < nmut; i += T) ar[i] = xx[i];
         float *const gcar = ar + 5 * n + 9 * m;
         for (int i = tid; i < m + n; i += T) gcar[i] = hx[i];      // (gx follows hx)
+    } else {
+        vp.store_mut(V, ar, n, m, T, tid);                 // (everything else was updated where it lies)
     }
     if (tid == 0) s.store(gst);
 }
@@ -480,31 +537,43 @@ __device__ __forceinline__ void mb_iterate_body(const ObArgs &a, const PSD &psd_
 // a problem starts from a given iterate (thip_NAME_set_iterates): its workgroup loads the staged (x, y) at `it` into the map, forms the
 // carried pair of that iterate -- h = A x_x, g = A^T x_y, the call the iteration's second pass makes, so a run that is handed
 // its own iterate continues bit for bit -- and writes the mutable part of the arena (Kahan terms zero), the pair and the status
-// block.  The slot's data, the preconditioner and the norms stay as init left them.  AT, MAT: the seams of the two bodies above
-template <class AT = ObUniform, class MAT = MbDenseA>
-__device__ __forceinline__ void mb_start_body(const ObArgs &a, const float *it, const AT &at = AT(), const MAT &mat = MAT())
+// block.  The slot's data, the preconditioner and the norms stay as init left them.  AT, MAT, VP: the seams of the two bodies above
+template <class AT = ObUniform, class MAT = MbDenseA, class VP = MbInLds>
+__device__ __forceinline__ void mb_start_body(const ObArgs &a, const float *it, const AT &at = AT(), const MAT &mat = MAT(),
+                                              const VP &vp = VP())
 {
     const int p = at.problem(a);
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
-    const MbMap L(n, m);
+    const typename VP::Map L(n, m);
     float *S = mb_lds;
-    float *const xx = S + L.xx, *const xy = S + L.xy, *const h = S + L.h, *const g = S + L.g;
+    float *const xx = S + L.xx, *const xy = S + L.xy, *const h = S + L.h, *const g = S + L.g;       // (in LDS under every placement)
     const float *const x = it, *const y = it + n + 2 * m + 1;       // x_x x_y x_s tau | u v kappa
     const SbSlot sl = a.slots[p];
     const auto A = mat.open(sl.a, m, n, S);
-    for (int i = tid; i < n; i += T) {
-        xx[i] = x[i]; S[L.u + i] = y[i];
-        S[L.kx + i] = 0.0f; S[L.ku + i] = 0.0f;
-    }
-    for (int i = tid; i < m; i += T) {
-        xy[i] = x[n + i]; S[L.xs + i] = x[n + m + i]; S[L.v + i] = y[n + i];
-        S[L.ky + i] = 0.0f; S[L.ks + i] = 0.0f; S[L.kv + i] = 0.0f;
+    [[maybe_unused]] MbVecs V{};                           // (a placement other than LDS alone uses it)
+    if constexpr (VP::in_lds) {
+        for (int i = tid; i < n; i += T) {
+            xx[i] = x[i]; S[L.u + i] = y[i];
+            S[L.kx + i] = 0.0f; S[L.ku + i] = 0.0f;
+        }
+        for (int i = tid; i < m; i += T) {
+            xy[i] = x[n + i]; S[L.xs + i] = x[n + m + i]; S[L.v + i] = y[n + i];
+            S[L.ky + i] = 0.0f; S[L.ks + i] = 0.0f; S[L.kv + i] = 0.0f;
+        }
+    } else {
+        V = vp.vecs(S, L);
+        vp.place(V, at.block(a, p), sl, n, m);
+        vp.start_fill(V, x, y, n, m, T, tid);
     }
     mat.template pass<false>(A, m, n, xx, xy, h, g, S + L.hp, S + L.gp);
     float *const ar = at.block(a, p);
     {
-        const int nmut = 4 * n + 6 * m;                    // the arena's order is the LDS order from xx on
-        for (int i = tid; i < nmut; i += T) ar[i] = xx[i];
+        if constexpr (VP::in_lds) {
+            const int nmut = 4 * n + 6 * m;                // the arena's order is the LDS order from xx on
+            for (int i = tid; i < nmut; i += T) ar[i] = xx[i];
+        } else {
+            vp.store_mut(V, ar, n, m, T, tid);
+        }
         float *const gcar = ar + 5 * n + 9 * m;
         for (int i = tid; i < m; i += T) gcar[i] = h[i];
         for (int i = tid; i < n; i += T) gcar[m + i] = g[i];
@@ -518,23 +587,25 @@ __device__ __forceinline__ void mb_start_body(const ObArgs &a, const float *it, 
 // x_y into the map, then h = A x_x, g = A^T x_y by the call the iteration's second pass makes, as mb_start_body forms it (restated
 // here: that body is left as it compiles) -- and written behind the preconditioner.  The matrix is opened once, ahead of the body:
 // a resident blob stays in LDS for both passes (the body touches neither its place nor the PSD tail in front of it)
-template <class AT = ObUniform, class MAT = MbDenseA>
-__device__ __forceinline__ void mb_seta_body(const ObArgs &a, int keep, const AT &at = AT(), const MAT &mat = MAT())
+template <class AT = ObUniform, class MAT = MbDenseA, class VP = MbInLds>
+__device__ __forceinline__ void mb_seta_body(const ObArgs &a, int keep, const AT &at = AT(), const MAT &mat = MAT(), const VP &vp = VP())
 {
     const int n = a.n, m = a.m, T = (int)blockDim.x, tid = (int)threadIdx.x;
     const int p = at.problem(a);
-    const MbMap L(n, m);
+    const typename VP::InitMap L(n, m);
     float *S = mb_lds;
     const auto A = mat.open(a.slots[p].a, m, n, S);
     ob_init_body(a, p, L, S, [&](const float *) {
         mat.template pass<true>(A, m, n, nullptr, nullptr, S + L.h, S + L.g, S + L.hp, S + L.gp);
     }, at, ObKeepA{ keep });
     if (keep == 0) return;                                  // (uniform: a launch argument)
-    float *const xx = S + L.xx, *const xy = S + L.xy, *const h = S + L.h, *const g = S + L.g;
+    const typename VP::Map Li(n, m);                        // (the iteration's map; MbInLds: the same one)
+    float *const xx = S + Li.xx, *const xy = S + Li.xy, *const h = S + Li.h, *const g = S + Li.g;
     float *const ar = at.block(a, p);
+    if constexpr (!VP::in_lds) vp.sync_maps();
     for (int i = tid; i < n; i += T) xx[i] = ar[i];         // (the body's keep ending writes the Kahan terms alone)
     for (int i = tid; i < m; i += T) xy[i] = ar[4 * n + i];
-    mat.template pass<false>(A, m, n, xx, xy, h, g, S + L.hp, S + L.gp);
+    mat.template pass<false>(A, m, n, xx, xy, h, g, S + Li.hp, S + Li.gp);
     float *const gcar = ar + 5 * n + 9 * m;
     for (int i = tid; i < m; i += T) gcar[i] = h[i];
     for (int i = tid; i < n; i += T) gcar[m + i] = g[i];

@@ -1,8 +1,9 @@
 // thip_sdpcones.h -- the PSD cones of the streamed own-A batches, shared by the SDP batch (thip_sdpbatch.hip) and the ragged batch
 // (thip_raggedbatch.hip): the projection of one cone of order k <= 64 by the problem's own workgroup (sp_project; described at the
 // top of thip_sdpbatch.hip), the hook of the block-cone phase that walks a problem's PSD cones (SpCones), and the shape rule both
-// batches take a problem by (sp_check, sp_lds_for: no device needed).
-// Included once by each of the two translation units (on top of thip_midstream.h): everything here is internal to the one that
+// batches take a problem by (sp_check, sp_lds_for: no device needed).  thip_widebatch.hip runs the same cones on vectors that lie in
+// the arena (SpCones::placed) under a rule of its own.
+// Included once by each of the translation units that run PSD cones (on top of thip_midstream.h): everything here is internal to the one that
 // includes it.
 #pragma once
 
@@ -136,7 +137,9 @@ __device__ __forceinline__ void sp_project_any(float *x, float *rx, int k, float
     else sp_project<64>(x, rx, k, scr, tail, tail + SP_OP64, tail + 2 * SP_OP64, shd);
 }
 
-// the PSD cones of the block-cone phase: one after another, x_y (whose reflection is not needed) then x_s
+// the PSD cones of the block-cone phase: one after another, x_y (whose reflection is not needed) then x_s.  operator(): every vector
+// in LDS by MbMap; placed: x_y, x_s and rx_s where the body's vector placement says they lie (thip_midstream.h: MbVecs) -- the same
+// walk (restated: the first form is left as it compiles)
 struct SpCones {
     static constexpr bool psd = true;
     int tail;                               // where the operands behind the class bytes begin, in floats
@@ -150,6 +153,18 @@ struct SpCones {
             for (int which = 0; which < 2; ++which)
                 sp_project_any(S + (which ? L.xs : L.xy) + beg, which ? S + L.rxs + beg : nullptr, kind - 1, S + L.hp, S + tail,
                                reinterpret_cast<double *>(S + L.sh));
+        }
+    }
+    __device__ __forceinline__ void placed(const MbVecs &V, const ObArgs &a) const
+    {
+        for (int c = 0; c < a.n_cones; ++c) {
+            const int kind = a.cones[3 * c + 2];
+            if (kind < 2) continue;
+            const int beg = a.cones[3 * c];
+#pragma unroll 1
+            for (int which = 0; which < 2; ++which)
+                sp_project_any((which ? V.xs : V.xy) + beg, which ? V.rxs + beg : nullptr, kind - 1, V.hp, V.lds + tail,
+                               reinterpret_cast<double *>(V.sh));
         }
     }
 };
