@@ -936,6 +936,68 @@ int thip_widebatch_info(const thip_widebatch *h, thip_widebatch_info_t *host_inf
 int thip_widebatch_destroy(thip_widebatch *h);
 
 /* ---------------------------------------------------------------------------------------------
+ * The wide batch over a LIBRARY-OWNED 16-BIT COPY of every problem's A (thip_wide16batch.hip): thip_widebatch's shapes
+ * (thip_wide16batch_fits is thip_widebatch_fits, PSD cones included), cones, iteration and interface; the store, its two rounding rules,
+ * a_kind and the calls that convert are thip_mid16batch's, word for word (thip_wide16batch_create: f16; THIP_A_F32 is refused -- that
+ * is thip_widebatch; dev_mats_a is NOT referenced after create returns; set_a_dev(NULL) is refused: no f32 A lies in place).
+ * The contract: with W the WIDENED matrix (as thip_mid16batch defines it) the batch is BIT FOR BIT a thip_widebatch created over W in
+ * f32: the whole arena block (6 n + 11 m floats), preconditioner, iterates, compensation terms, status blocks and verdicts, at both
+ * workgroup sizes, in both state arithmetics, however the iterations are cut into launches.  The problem solved is the one with the
+ * rounded matrix; its end iterate is a start (thip_widebatch_set_iterates) for the exact one.  No chooser returns this family.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct thip_wide16batch thip_wide16batch;
+typedef struct thip_wide16batch_info_t {
+    int32_t n_prob, threads;          /* as thip_widebatch_info_t ... */
+    int32_t lds_bytes, live;
+    size_t  arena_bytes;
+    size_t  device_bytes;             /* everything this object allocated on the device, the store included */
+    size_t  device_bytes_all;         /* summed over every thip_wide16batch alive in the process */
+    int64_t launches, workgroups;
+    int32_t load_bytes, a_dtype;      /* 8 for every shape: a lane's 4 rows of a column are one load; THIP_A_BF16 / THIP_A_F16 */
+    size_t  a_bytes_per_iter;         /* bytes of the store read per problem-iteration: 2 (2 ld16 n + (f16: 4 n)) */
+    int32_t max_psd_order, n_psd;
+    size_t  psd_lds_bytes;
+    size_t  lds_bytes_per_problem;    /* what thip_wide16batch_fits reports */
+    size_t  arena_bytes_per_problem;  /* one problem's block of the arena: 4 (6 n + 11 m) */
+    size_t  a_store_bytes;            /* ... and the store: n_prob blocks */
+} thip_wide16batch_info_t;
+/* the shape rules alone (needs no device): thip_widebatch_fits' */
+int thip_wide16batch_fits(size_t n, size_t m, size_t n_seg, const int32_t *host_seg_type, const int64_t *host_seg_len,
+                          size_t *host_lds_bytes, int *host_threads);
+/* the bytes of one problem's block of the store (needs no device): thip_mid16batch_store_bytes' */
+int thip_wide16batch_store_bytes(size_t n, size_t m, int a_kind, size_t *host_bytes);
+int thip_wide16batch_create(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                            const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                            const int64_t *host_seg_len, const thip_param *par, thip_wide16batch **out);
+int thip_wide16batch_create_kind(size_t n, size_t m, size_t n_prob, const float *dev_mats_a, const float *dev_vecs_b,
+                                 const float *dev_vecs_c, const float *dev_vecs_b_rowabs, size_t n_seg, const int32_t *host_seg_type,
+                                 const int64_t *host_seg_len, const thip_param *par, int a_kind, thip_wide16batch **out);
+int thip_wide16batch_set_param(thip_wide16batch *h, const thip_param *par);
+int thip_wide16batch_init(thip_wide16batch *h);
+int thip_wide16batch_run(thip_wide16batch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_wide16batch_run_until_any(thip_wide16batch *h, int64_t max_steps, int64_t poll_every, thip_status *host_status);
+int thip_wide16batch_status(thip_wide16batch *h, int i, thip_status *host_status);
+int thip_wide16batch_solution(thip_wide16batch *h, int i, float *host_x, float *host_y);
+int thip_wide16batch_iterate(thip_wide16batch *h, int i, float *host_x, float *host_y);
+int thip_wide16batch_precond(thip_wide16batch *h, int i, float *host_dp_tau, float *host_dp_sigma);
+int thip_wide16batch_replace(thip_wide16batch *h, int i, const float *dev_mat_a, const float *dev_vec_b, const float *dev_vec_c,
+                             const float *dev_vec_b_rowabs);
+int thip_wide16batch_set_iterates(thip_wide16batch *h, int first, int count, const float *host_x, const float *host_y);
+int thip_wide16batch_set_bc(thip_wide16batch *h, int first, int count, const float *host_b, const float *host_c,
+                            const float *host_b_rowabs, const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_wide16batch_solutions(thip_wide16batch *h, int first, int count, float *host_x, float *host_y, thip_status *host_status);
+int thip_wide16batch_set_a(thip_wide16batch *h, int first, int count, const float *host_values, const int64_t *host_counts, int keep_iterate);
+int thip_wide16batch_set_bc_dev(thip_wide16batch *h, int first, int count, const float *dev_b, const float *dev_c, const float *dev_b_rowabs,
+    const uint8_t *host_has_rowabs, int keep_iterate);
+int thip_wide16batch_set_a_dev(thip_wide16batch *h, int first, int count, const float *dev_values, int keep_iterate);
+int thip_wide16batch_set_iterates_dev(thip_wide16batch *h, int first, int count, const float *dev_x, const float *dev_y);
+int thip_wide16batch_solutions_dev(thip_wide16batch *h, int first, int count, float *dev_x, float *dev_y, int32_t *dev_state);
+/* problem i's block as it lies in the store: n ld16 words, and (THIP_A_F16; else untouched) the n column scales.  Either may be NULL */
+int thip_wide16batch_stored(thip_wide16batch *h, int i, uint16_t *host_words, float *host_inv_scale);
+int thip_wide16batch_info(const thip_wide16batch *h, thip_wide16batch_info_t *host_info);
+int thip_wide16batch_destroy(thip_wide16batch *h);
+
+/* ---------------------------------------------------------------------------------------------
  * The RAGGED batch: many conic programs, each with its own dense f32 A, its own n_p, m_p and its own cone layout, in one batch
  * (thip_raggedbatch.hip).  The iteration is thip_sdpbatch's on every problem -- one workgroup per running problem,
  * its vectors in LDS, its A streamed twice per iteration, its PSD cones projected on chip --, and a problem's iterates are, bit for

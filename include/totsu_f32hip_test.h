@@ -250,6 +250,10 @@ int thip_test_sdpbatch_force_threads(thip_sdpbatch *h, int threads);
  * thip_widebatch_init. */
 int thip_test_widebatch_force_threads(thip_widebatch *h, int threads);
 
+/* TEST HOOK: the workgroup size of a wide16 batch (thip_wide16batch.hip): 256 or 1024 threads, 0 = by shape.  Before
+ * thip_wide16batch_init. */
+int thip_test_wide16batch_force_threads(thip_wide16batch *h, int threads);
+
 /* TEST HOOK: the SDP batch kernel's own PSD projection alone: `count` packed matrices of order k (1 .. 64; k (k + 1) / 2 floats each,
  * one after another at dev_packed, off-diagonals times sqrt 2) are projected in place, one workgroup each, in ONE launch;
  * dev_rx_or_null != NULL: rx <- rx - 2 x of the same layout rides in the pack. */

@@ -86,6 +86,19 @@ pub struct thip_widebatch_info_t {
 }
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
+pub struct thip_wide16batch_info_t {
+    pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
+    pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
+    pub launches: i64, pub workgroups: i64,
+    pub load_bytes: i32, pub a_dtype: i32,
+    pub a_bytes_per_iter: usize,
+    pub max_psd_order: i32, pub n_psd: i32,
+    pub psd_lds_bytes: usize,
+    pub lds_bytes_per_problem: usize, pub arena_bytes_per_problem: usize,
+    pub a_store_bytes: usize,
+}
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
 pub struct thip_sparsebatch_info_t {
     pub n_prob: i32, pub threads: i32, pub lds_bytes: i32, pub live: i32,
     pub arena_bytes: usize, pub device_bytes: usize, pub device_bytes_all: usize,
@@ -190,6 +203,7 @@ pub enum thip_midbatch {}
 pub enum thip_mid16batch {}
 pub enum thip_sdpbatch {}
 pub enum thip_widebatch {}
+pub enum thip_wide16batch {}
 pub enum thip_raggedbatch {}
 pub enum thip_sparsebatch {}
 pub enum thip_raggedsparse {}
@@ -506,6 +520,38 @@ extern "C" {
     pub fn thip_widebatch_info(h: *const thip_widebatch, host_info: *mut thip_widebatch_info_t) -> c_int;
     pub fn thip_widebatch_destroy(h: *mut thip_widebatch) -> c_int;
     pub fn thip_test_widebatch_force_threads(h: *mut thip_widebatch, threads: c_int) -> c_int;
+    // the wide batch over a library-owned 16-bit copy of every A (thip_wide16batch.hip)
+    pub fn thip_wide16batch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
+                              host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;
+    pub fn thip_wide16batch_create(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                host_seg_len: *const i64, par: *const thip_param, out: *mut *mut thip_wide16batch) -> c_int;
+    pub fn thip_wide16batch_set_param(h: *mut thip_wide16batch, par: *const thip_param) -> c_int;
+    pub fn thip_wide16batch_init(h: *mut thip_wide16batch) -> c_int;
+    pub fn thip_wide16batch_run(h: *mut thip_wide16batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_wide16batch_run_until_any(h: *mut thip_wide16batch, max_steps: i64, poll_every: i64, host_status: *mut thip_status) -> c_int;
+    pub fn thip_wide16batch_status(h: *mut thip_wide16batch, i: c_int, host_status: *mut thip_status) -> c_int;
+    pub fn thip_wide16batch_solution(h: *mut thip_wide16batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_wide16batch_iterate(h: *mut thip_wide16batch, i: c_int, host_x: *mut f32, host_y: *mut f32) -> c_int;
+    pub fn thip_wide16batch_precond(h: *mut thip_wide16batch, i: c_int, host_dp_tau: *mut f32, host_dp_sigma: *mut f32) -> c_int;
+    pub fn thip_wide16batch_replace(h: *mut thip_wide16batch, i: c_int, dev_mat_a: *const f32, dev_vec_b: *const f32,
+                                 dev_vec_c: *const f32, dev_vec_b_rowabs: *const f32) -> c_int;
+    pub fn thip_wide16batch_set_iterates(h: *mut thip_wide16batch, first: c_int, count: c_int, host_x: *const f32, host_y: *const f32) -> c_int;
+    pub fn thip_wide16batch_set_bc(h: *mut thip_wide16batch, first: c_int, count: c_int, host_b: *const f32, host_c: *const f32, host_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_wide16batch_solutions(h: *mut thip_wide16batch, first: c_int, count: c_int, host_x: *mut f32, host_y: *mut f32, host_status: *mut thip_status) -> c_int;
+    pub fn thip_wide16batch_set_a(h: *mut thip_wide16batch, first: c_int, count: c_int, host_values: *const f32, host_counts: *const i64, keep_iterate: c_int) -> c_int;
+    pub fn thip_wide16batch_set_bc_dev(h: *mut thip_wide16batch, first: c_int, count: c_int, dev_b: *const f32, dev_c: *const f32, dev_b_rowabs: *const f32, host_has_rowabs: *const u8, keep_iterate: c_int) -> c_int;
+    pub fn thip_wide16batch_set_a_dev(h: *mut thip_wide16batch, first: c_int, count: c_int, dev_values: *const f32, keep_iterate: c_int) -> c_int;
+    pub fn thip_wide16batch_set_iterates_dev(h: *mut thip_wide16batch, first: c_int, count: c_int, dev_x: *const f32, dev_y: *const f32) -> c_int;
+    pub fn thip_wide16batch_solutions_dev(h: *mut thip_wide16batch, first: c_int, count: c_int, dev_x: *mut f32, dev_y: *mut f32, dev_state: *mut i32) -> c_int;
+    pub fn thip_wide16batch_info(h: *const thip_wide16batch, host_info: *mut thip_wide16batch_info_t) -> c_int;
+    pub fn thip_wide16batch_destroy(h: *mut thip_wide16batch) -> c_int;
+    pub fn thip_test_wide16batch_force_threads(h: *mut thip_wide16batch, threads: c_int) -> c_int;
+    pub fn thip_wide16batch_create_kind(n: usize, m: usize, n_prob: usize, dev_mats_a: *const f32, dev_vecs_b: *const f32,
+                                       dev_vecs_c: *const f32, dev_vecs_b_rowabs: *const f32, n_seg: usize, host_seg_type: *const i32,
+                                       host_seg_len: *const i64, par: *const thip_param, a_kind: c_int, out: *mut *mut thip_wide16batch) -> c_int;
+    pub fn thip_wide16batch_store_bytes(n: usize, m: usize, a_kind: c_int, host_bytes: *mut usize) -> c_int;
+    pub fn thip_wide16batch_stored(h: *mut thip_wide16batch, i: c_int, host_words: *mut u16, host_inv_scale: *mut f32) -> c_int;
 
     // problems of different shapes and cone layouts in one batch: the SDP batch's iteration on a problem the workgroup looks up
     // (thip_raggedbatch.hip)

@@ -42,6 +42,12 @@ problem's block of the arena and worked on in place, with up to 1024 threads:
     widebatch_k, _init_k, _start_k, _setbc_k, _seta_k: the SDP batch's bounds -- no scratch at all, at most 128 VGPRs and >= 4 waves
     per SIMD (without them a 1024-thread workgroup does not launch).
 
+The wide16 batch (thip_wide16batch.hip, --family wide16batch) is the wide batch's iteration over the mid16 batch's 16-bit store, two
+chunks of eight packed columns in flight per lane, in one instance per stored form (bf16, f16):
+
+    wide16batch_k, _init_k, _start_k, _setbc_k, _seta_k (and its copy of mid16batch_convert_k): the same bounds -- no scratch at all,
+    at most 128 VGPRs and >= 4 waves per SIMD.
+
 The ragged batch (thip_raggedbatch.hip, --family raggedbatch) is the SDP batch's iteration on a problem of its own shape and cone
 layout that the workgroup looks up in a table:
 
@@ -63,7 +69,7 @@ Every family's translation unit also carries the four kernels of the round calls
 ownbatch_copy_a_k, ownbatch_stage_bc_k, ownbatch_gather_final_k): required, no scratch, at most 64 VGPRs, >= 4 waves per SIMD.
 
 usage: check_kernel_resources.py <remarks file> [--report]
-                                 [--family sweep|gemv_multi|smallbatch|midbatch|mid16batch|sdpbatch|widebatch|raggedbatch|
+                                 [--family sweep|gemv_multi|smallbatch|midbatch|mid16batch|sdpbatch|widebatch|wide16batch|raggedbatch|
                                           sparsebatch|raggedsparse]"""
 import re
 import sys
@@ -128,6 +134,8 @@ OWNBATCH = {
     "sdpbatch": (r"sdpbatch(_init|_project|_start|_seta)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k", "sdpbatch_seta_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
     "widebatch": (r"widebatch(_init|_start|_setbc|_seta)?_k", ("widebatch_k", "widebatch_init_k", "widebatch_start_k", "widebatch_setbc_k", "widebatch_seta_k"), 128, "wide batch",
                   "thip_widebatch.hip"),
+    "wide16batch": (r"wide16batch(_init|_start|_setbc|_seta)?_k|mid16batch_convert_k", ("wide16batch_k", "wide16batch_init_k", "wide16batch_start_k", "wide16batch_setbc_k", "wide16batch_seta_k", "mid16batch_convert_k"), 128,
+                    "wide batch over a 16-bit A", "thip_wide16batch.hip"),
     "raggedbatch": (r"raggedbatch(_init|_start|_seta)?_k", ("raggedbatch_k", "raggedbatch_init_k", "raggedbatch_start_k", "raggedbatch_seta_k"), 128, "ragged batch", "thip_raggedbatch.hip"),
     "sparsebatch": (r"sparsebatch(_init|_start|_seta|_scatter)?_k", ("sparsebatch_k", "sparsebatch_init_k", "sparsebatch_start_k", "sparsebatch_seta_k", "sparsebatch_scatter_k"), 128, "sparse batch", "thip_sparsebatch.hip"),
     "raggedsparse": (r"raggedsparse(_init|_start|_seta|_scatter)?_k", ("raggedsparse_k", "raggedsparse_init_k", "raggedsparse_start_k", "raggedsparse_seta_k", "raggedsparse_scatter_k"), 128, "ragged sparse batch",

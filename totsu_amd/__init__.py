@@ -17,6 +17,7 @@ from .midbatch import MidBatchSolver, own_a_batch
 from .mid16batch import Mid16BatchSolver
 from .sdpbatch import SdpBatchSolver, conic_batch
 from .widebatch import WideBatchSolver
+from .wide16batch import Wide16BatchSolver
 from .raggedbatch import RaggedBatchSolver, ragged_batch
 from .sparsebatch import SparseBatchSolver
 from .raggedsparse import RaggedSparseBatchSolver
@@ -25,5 +26,5 @@ from .sparse import SparseMatOp, SpTile
 
 __all__ = ["MatOp", "MatType", "Solver", "SolverError", "SolverParam", "F32HIP", "F32HIPSlice", "splitm",
            "ConeZero", "ConeRPos", "ConeSOC", "ConeRotSOC", "ConePSD", "MatBuild", "ProbLP", "ProbSOCP",
-           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "solve_many", "SmallBatchSolver", "MidBatchSolver", "Mid16BatchSolver", "own_a_batch", "SdpBatchSolver", "conic_batch", "WideBatchSolver", "RaggedBatchSolver", "ragged_batch", "SparseBatchSolver", "RaggedSparseBatchSolver", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
+           "ProbSDP", "ProbQP", "ProbQCQP", "FusedSolver", "BatchSolver", "solve_many", "SmallBatchSolver", "MidBatchSolver", "Mid16BatchSolver", "own_a_batch", "SdpBatchSolver", "conic_batch", "WideBatchSolver", "Wide16BatchSolver", "RaggedBatchSolver", "ragged_batch", "SparseBatchSolver", "RaggedSparseBatchSolver", "DeviceBuffer", "Bf16Matrix", "ShardedSolver", "TorchComm",
            "shard_segments", "SparseMatOp", "SpTile"]

@@ -91,6 +91,13 @@ class WideBatchInfo(C.Structure):
     _fields_ = SdpBatchInfo._fields_ + [("lds_bytes_per_problem", C.c_size_t), ("arena_bytes_per_problem", C.c_size_t)]
 
 
+class Wide16BatchInfo(C.Structure):
+    _fields_ = SmallBatchInfo._fields_ + [("load_bytes", C.c_int32), ("a_dtype", C.c_int32), ("a_bytes_per_iter", C.c_size_t),
+                                          ("max_psd_order", C.c_int32), ("n_psd", C.c_int32), ("psd_lds_bytes", C.c_size_t),
+                                          ("lds_bytes_per_problem", C.c_size_t), ("arena_bytes_per_problem", C.c_size_t),
+                                          ("a_store_bytes", C.c_size_t)]
+
+
 class SparseBatchInfo(C.Structure):
     _fields_ = SmallBatchInfo._fields_ + [("a_bytes_per_iter", C.c_size_t), ("max_psd_order", C.c_int32), ("n_psd", C.c_int32),
                                           ("psd_lds_bytes", C.c_size_t), ("nnz_cap", C.c_size_t), ("nnz_total", C.c_size_t),
@@ -311,7 +318,7 @@ PROTOTYPES = {
 
 # the own-A batch families share one C API (totsu_amd/csrc/thip_ownbatch.h): the same signatures under each prefix
 for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo), ("sdpbatch", SdpBatchInfo),
-                     ("mid16batch", Mid16BatchInfo), ("widebatch", WideBatchInfo)):
+                     ("mid16batch", Mid16BatchInfo), ("widebatch", WideBatchInfo), ("wide16batch", Wide16BatchInfo)):
     _p = "thip_%s_" % _name
     PROTOTYPES.update({
         _p + "fits": (_i, [_sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_sz), C.POINTER(_i)]),
@@ -339,13 +346,15 @@ for _name, _info in (("smallbatch", SmallBatchInfo), ("midbatch", MidBatchInfo),
         "thip_test_%s_force_threads" % _name: (_i, [_vp, _i]),
     })
 
-# what the mid16 batch adds: a create that carries the stored form, the size of a problem's block, the read-back of a block
-PROTOTYPES.update({
-    "thip_mid16batch_create_kind": (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                         C.POINTER(Param), _i, C.POINTER(_vp)]),
-    "thip_mid16batch_store_bytes": (_i, [_sz, _sz, _i, C.POINTER(_sz)]),
-    "thip_mid16batch_stored": (_i, [_vp, _i, _vp, _vp]),
-})
+# what the families over a 16-bit store add: a create that carries the stored form, the size of a problem's block, the read-back of
+# a block
+for _name in ("mid16batch", "wide16batch"):
+    PROTOTYPES.update({
+        "thip_%s_create_kind" % _name: (_i, [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                             C.POINTER(Param), _i, C.POINTER(_vp)]),
+        "thip_%s_store_bytes" % _name: (_i, [_sz, _sz, _i, C.POINTER(_sz)]),
+        "thip_%s_stored" % _name: (_i, [_vp, _i, _vp, _vp]),
+    })
 
 # the ragged batch: the same methods on a handle whose problems each have their own shape (totsu_amd/csrc/thip_raggedbatch.hip)
 _psz, _p32, _p64 = C.POINTER(_sz), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
