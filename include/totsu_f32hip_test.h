@@ -259,6 +259,12 @@ int thip_test_wide16batch_force_threads(thip_wide16batch *h, int threads);
  * dev_rx_or_null != NULL: rx <- rx - 2 x of the same layout rides in the pack. */
 int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_rx_or_null);
 
+/* TEST HOOK: the same projection in the forms the own-A batches run it in (same contract as thip_test_sdpbatch_project), from a
+ * kernel compiled for 1024-thread workgroups as the iteration kernels are.  threads: 256 or 1024.  in_lds 0: on the device arrays
+ * themselves (the wide batches: the vectors lie in the arena); 1: the workgroup copies its matrix (and rx) into LDS behind the
+ * operands, projects there (the other batches: every vector in LDS) and copies the result back.  Anything else is refused. */
+int thip_test_sdpbatch_project_form(int k, int count, int threads, int in_lds, float *dev_packed, float *dev_rx_or_null);
+
 /* TEST HOOK: the workgroup size of a ragged batch (thip_raggedbatch.hip): 256 or 1024 threads put every problem in that one
  * class, 0 = by shape.  Before thip_raggedbatch_init. */
 int thip_test_raggedbatch_force_threads(thip_raggedbatch *h, int threads);

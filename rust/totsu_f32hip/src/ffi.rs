@@ -493,6 +493,7 @@ extern "C" {
     pub fn thip_sdpbatch_destroy(h: *mut thip_sdpbatch) -> c_int;
     pub fn thip_test_sdpbatch_force_threads(h: *mut thip_sdpbatch, threads: c_int) -> c_int;
     pub fn thip_test_sdpbatch_project(k: c_int, count: c_int, dev_packed: *mut f32, dev_rx_or_null: *mut f32) -> c_int;
+    pub fn thip_test_sdpbatch_project_form(k: c_int, count: c_int, threads: c_int, in_lds: c_int, dev_packed: *mut f32, dev_rx_or_null: *mut f32) -> c_int;
     // the SDP batch's iteration on every shape to 4096 x 4096: all but the pass vectors left in the arena (thip_widebatch.hip)
     pub fn thip_widebatch_fits(n: usize, m: usize, n_seg: usize, host_seg_type: *const i32, host_seg_len: *const i64,
                               host_lds_bytes: *mut usize, host_threads: *mut c_int) -> c_int;

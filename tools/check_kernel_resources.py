@@ -34,7 +34,7 @@ chunks of eight columns in flight per lane, in one instance per stored form (bf1
 The SDP batch (thip_sdpbatch.hip, --family sdpbatch) is the mid batch's iteration with the PSD cones projected between the two passes
 by the workgroup itself (f32 MFMAs on operands in LDS), with up to 1024 threads:
 
-    sdpbatch_k, sdpbatch_init_k (and the test hook's sdpbatch_project_k): no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
+    sdpbatch_k, sdpbatch_init_k (and the test hooks' sdpbatch_project_k, sdpbatch_project_form_k): no scratch at all, at most 128 VGPRs and >= 4 waves per SIMD.
 
 The wide batch (thip_widebatch.hip, --family widebatch) is the SDP batch's iteration with all but the vectors of a pass left in the
 problem's block of the arena and worked on in place, with up to 1024 threads:
@@ -131,7 +131,7 @@ OWNBATCH = {
     "midbatch": (r"midbatch(_init|_start|_seta)?_k", ("midbatch_k", "midbatch_init_k", "midbatch_start_k", "midbatch_seta_k"), None, "streamed mid-size batch", "thip_midbatch.hip"),
     "mid16batch": (r"mid16batch(_init|_start|_setbc|_seta|_convert)?_k", ("mid16batch_k", "mid16batch_init_k", "mid16batch_start_k", "mid16batch_setbc_k", "mid16batch_seta_k", "mid16batch_convert_k"), 128, "mid batch over a 16-bit A",
                    "thip_mid16batch.hip"),
-    "sdpbatch": (r"sdpbatch(_init|_project|_start|_seta)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k", "sdpbatch_seta_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
+    "sdpbatch": (r"sdpbatch(_init|_project|_project_form|_start|_seta)?_k", ("sdpbatch_k", "sdpbatch_init_k", "sdpbatch_start_k", "sdpbatch_seta_k"), 128, "SDP batch", "thip_sdpbatch.hip"),
     "widebatch": (r"widebatch(_init|_start|_setbc|_seta)?_k", ("widebatch_k", "widebatch_init_k", "widebatch_start_k", "widebatch_setbc_k", "widebatch_seta_k"), 128, "wide batch",
                   "thip_widebatch.hip"),
     "wide16batch": (r"wide16batch(_init|_start|_setbc|_seta)?_k|mid16batch_convert_k", ("wide16batch_k", "wide16batch_init_k", "wide16batch_start_k", "wide16batch_setbc_k", "wide16batch_seta_k", "mid16batch_convert_k"), 128,

@@ -299,6 +299,7 @@ PROTOTYPES = {
     "thip_test_gemv_multi": (_i, [_sz, _sz, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_i), _i, _i, _i, C.POINTER(_f)]),
     "thip_test_sdpbatch_project": (_i, [_i, _i, _vp, _vp]),
+    "thip_test_sdpbatch_project_form": (_i, [_i, _i, _i, _i, _vp, _vp]),
     "thip_test_dual_gemv": (_i, [C.POINTER(GemvTest), C.POINTER(GemvPlanRec)]),
     "thip_test_gemv_plan": (_i, [_sz, _sz, _i, _i, _i, _sz, _sz, C.POINTER(GemvPlanRec), C.POINTER(_sz), C.POINTER(_sz)]),
     "thip_test_solver_pin_gemv_plan": (_i, [_vp, _i]),

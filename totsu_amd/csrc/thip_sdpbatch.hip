@@ -63,6 +63,31 @@ __global__ __launch_bounds__(256) void sdpbatch_project_k(int k, float *packed, 
                    reinterpret_cast<double *>(S));
 }
 
+// thip_test_sdpbatch_project_form: the projection in the forms the batches run it in, from a kernel built for 1024-thread workgroups
+// as the iteration kernels are.  LDS false: x (and rx) where they lie in device memory (SpCones::placed); true: copied behind the
+// operands and projected there (SpCones::operator()), the result copied back.  LDS: [shd 64][operands][x][rx]
+template <bool LDS>
+__global__ __launch_bounds__(1024) void sdpbatch_project_form_k(int k, float *packed, float *rx)
+{
+    const int len = k * (k + 1) / 2, ops = 64 + (k <= 32 ? 4 * SP_OP32 : 4 * SP_OP64);
+    float *S = mb_lds, *x = packed + (size_t)blockIdx.x * len, *r = rx != nullptr ? rx + (size_t)blockIdx.x * len : nullptr;
+    if (!LDS) {
+        sp_project_any(x, r, k, S + 64, S + 64 + SP_OP64, reinterpret_cast<double *>(S));
+        return;
+    }
+    float *xl = S + ops, *rl = r != nullptr ? xl + len : nullptr;
+    for (int e = (int)threadIdx.x; e < len; e += (int)blockDim.x) {
+        xl[e] = x[e];
+        if (r != nullptr) rl[e] = r[e];
+    }
+    __syncthreads();
+    sp_project_any(xl, rl, k, S + 64, S + 64 + SP_OP64, reinterpret_cast<double *>(S));
+    for (int e = (int)threadIdx.x; e < len; e += (int)blockDim.x) {
+        x[e] = xl[e];
+        if (r != nullptr) r[e] = rl[e];
+    }
+}
+
 int sp_launch(const OwnBatch *h, bool run, const ObArgs &a, unsigned count)
 {
     if (!run) return ob_launch(h, sdpbatch_init_k, a, count);
@@ -84,11 +109,12 @@ int sp_seta(const OwnBatch *h, const ObArgs &a, const ObSetA &s, unsigned count)
     return ob_launch(h, sdpbatch_seta_k, SpSetAArgs{ a, s.keep }, count);
 }
 
-// (the sixth entry of the table's kernels is this family's: the projection probe asks for the large LDS too)
+// (the third entry of the table's kernels and the last two are this family's: the projection probes ask for the large LDS too)
 ObFamily SP_FAMILY = { SP_TEXT, { 256, 1024, 0 }, true, sp_check, mb_threads_for, sp_lds_for, mb_stride, sp_launch, sp_start, sp_setbc,
                        sp_seta,
                        { (const void *)sdpbatch_k, (const void *)sdpbatch_init_k, (const void *)sdpbatch_project_k,
-                         (const void *)sdpbatch_start_k, (const void *)sdpbatch_setbc_k, (const void *)sdpbatch_seta_k } };
+                         (const void *)sdpbatch_start_k, (const void *)sdpbatch_setbc_k, (const void *)sdpbatch_seta_k,
+                         (const void *)sdpbatch_project_form_k<false>, (const void *)sdpbatch_project_form_k<true> } };
 
 // thip_midbatch_info_t's fields, and the PSD cones'
 struct SpInfo {
@@ -116,6 +142,27 @@ int thip_test_sdpbatch_project(int k, int count, float *dev_packed, float *dev_r
     THIP_RC(ob_attr(SP_FAMILY));
     const size_t lds = (64 + (k <= 32 ? 4 * (size_t)SP_OP32 : 4 * (size_t)SP_OP64)) * sizeof(float);
     hipLaunchKernelGGL(sdpbatch_project_k, dim3((unsigned)count), dim3(256), lds, ctx().stream, k, dev_packed, dev_rx_or_null);
+    THIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int thip_test_sdpbatch_project_form(int k, int count, int threads, int in_lds, float *dev_packed, float *dev_rx_or_null)
+{
+    THIP_NEED_INIT();
+    if (k < 1 || k > SP_MAX_ORDER) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project_form: 1 <= k <= 64", __FILE__, __LINE__);
+    if (count < 1 || !dev_packed) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project_form: no matrix", __FILE__, __LINE__);
+    if (threads != 256 && threads != 1024)
+        return fail(THIP_E_INVALID, "thip_test_sdpbatch_project_form: the workgroup size is 256 or 1024", __FILE__, __LINE__);
+    if (in_lds != 0 && in_lds != 1) return fail(THIP_E_INVALID, "thip_test_sdpbatch_project_form: in_lds is 0 or 1", __FILE__, __LINE__);
+    THIP_RC(ob_attr(SP_FAMILY));
+    const size_t len = (size_t)k * (size_t)(k + 1) / 2;
+    const size_t lds = (64 + (k <= 32 ? 4 * (size_t)SP_OP32 : 4 * (size_t)SP_OP64) + (in_lds ? 2 * len : 0)) * sizeof(float);
+    if (in_lds)
+        hipLaunchKernelGGL(sdpbatch_project_form_k<true>, dim3((unsigned)count), dim3((unsigned)threads), lds, ctx().stream, k,
+                           dev_packed, dev_rx_or_null);
+    else
+        hipLaunchKernelGGL(sdpbatch_project_form_k<false>, dim3((unsigned)count), dim3((unsigned)threads), lds, ctx().stream, k,
+                           dev_packed, dev_rx_or_null);
     THIP_LAUNCH_CHECK();
     return 0;
 }
